@@ -6,6 +6,18 @@ their pyramids, run every pyramid level coarse->fine against the previous frames
 reference.  The stream path hands the session a tick of frames per step (one launch), the pair-at-a-time paths one pair.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 4k|1080p|8k|vga] [--iters I] [--mode lk_float|compat_cpu]
+                  [--full] [--dump-outputs DIR]
+
+A plain run does only what the headline figure needs: set-up, the untimed clock ramp, W warm-up steps, exactly K timed steps,
+the outputs of the last timed step if --dump-outputs is given, and the line (metric, value, unit, ms_per_step, ...).  Everything
+below that the line describes besides the headline -- roofline, power, self_check, extra, cpu_baseline -- is measured only
+with --full.
+
+--dump-outputs DIR: after the timed steps, the flows the last step completed (every level of each of its pairs, what a caller
+reads with ofx_session_flow_of / ofx_session_flow) go to DIR/flow_pair<j>_level<k>.npy as float32, j counted within the step.
+An array larger than its share of the 48 MiB budget is replaced by a fixed, seeded sample of its pixels ([n, 2]: u, v).  With
+the same arguments the frames of the last step are the same from run to run, so two builds can be compared file for file.
+At N > 1 rank 0 writes its own rows.
 
 The timed configuration is BASELINE.json's config as it is WRITTEN (4K: 5 levels, 9x9, 5 iterations, streamed); the
 reference-defined pipeline (iters = 1: the only value the reference has) is measured in the same process and reported as
@@ -15,7 +27,7 @@ N > 1: the SAME frame pairs are row-sharded over the ranks (cuda_optical_flow_2_
 either by torch.distributed.run (one rank per GPU) or plainly as `python bench.py --gpus N`, which then starts
 torch.distributed.run itself as a child process, before anything touches the GPU, and exits with its code.
 
-The line carries, besides the contract's fields: `roofline` (dominant kernel, HIP events on its stream), `self_check`
+With --full the line carries, besides the contract's fields: `roofline` (dominant kernel, HIP events on its stream), `self_check`
 (flows of the timed session compared with an independent plain session after the timed region; the run fails when they
 differ), `extra` (further legs measured in the same process, one function each below: every BASELINE configuration as it is
 written -- with its iterations -- and with iters = 1, a uniform-random pair, cache-cold inputs, the bug-for-bug compat_cpu
@@ -49,6 +61,8 @@ LK_ACC_BYTES_PER_PX = 18   # refinement launch: the same + the 8-byte flow read 
 WARP_BYTES_PER_PX = 10     # bilinear warp: 1 u8 + 8 flow read, 1 u8 written
 PYR_BYTES_PER_DST_PX = 5   # downsample: 4 u8 read + 1 written per destination pixel
 MAX_LK_ITEMS = 80          # OFX_MAX_LK_ITEMS: (pair, level) items one launch carries
+DUMP_BUDGET_BYTES = 48 << 20   # --dump-outputs: all files together stay below this
+DUMP_SEED = 1234               # --dump-outputs: seed of the pixel sample of level k is DUMP_SEED + k
 
 
 # ---- sizes and bytes ------------------------------------------------------------------------------------------------------
@@ -273,9 +287,15 @@ def parse_args():
     ap.add_argument("--iters", type=int, default=0,
                     help="refinement iterations per level: 0 (default) = what BASELINE.json's config says (4K / 1080p: 5, 8K: 10, vga: 3: the "
                          "lk_iter extension); 1 = the reference's own algorithm (no iteration exists there)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the event-timed roofline pass, the power reading, the self-check against a plain session, "
+                         "the extra legs and the CPU baseline (--no-extras / --no-cpu-baseline leave those two out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the flows the last timed step completed to DIR/<name>.npy (float32; arrays above their share of 48 MiB "
+                         "as a fixed, seeded sample of their pixels)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the additional legs reported under extra (profiling runs: only the timed configuration's launches)")
+                    help="--full: skip the additional legs reported under extra (profiling runs: only the timed configuration's launches)")
     ap.add_argument("--frames", default="texture", choices=["texture", "random"],
                     help="texture: SURVEY 8d's smooth texture translating by (2,1) px per frame (default); random: uniform-random u8 "
                          "frames (seed 1), the worst case for value ranges")
@@ -301,6 +321,8 @@ def parse_args():
                     help="stream paths: distinct frame buffers of the input ring; 0 = as many as the pipeline needs and at least enough "
                          "that the ring exceeds the 256 MiB Infinity Cache (a frame never comes round again while still cached)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.iters <= 0:
         args.iters = BASELINE_ITERS[args.workload]
     return args
@@ -408,18 +430,19 @@ class StreamFeed:
         from cuda_optical_flow_2_amd import engine
 
         self.submit, self.batch, self.frames_in = submit_frames, batch, 0
+        self.done = -1   # the highest pair complete after the last submit
         n = len(ring)
         self.groups = [engine.FrameGroup([ring[(j * batch + k) % n] for k in range(batch)]) for j in range(math.lcm(n, batch) // batch)]
 
     def step(self, _i=None):   # one frame
         self.frames_in += 1
         if self.frames_in % self.batch == 0:
-            self.submit(self.groups[(self.frames_in // self.batch - 1) % len(self.groups)])
+            self.done = self.submit(self.groups[(self.frames_in // self.batch - 1) % len(self.groups)])
 
     def tick(self, _i=None):   # a whole tick: self.batch frames, one launch
         assert self.frames_in % self.batch == 0
         self.frames_in += self.batch
-        self.submit(self.groups[(self.frames_in // self.batch - 1) % len(self.groups)])
+        self.done = self.submit(self.groups[(self.frames_in // self.batch - 1) % len(self.groups)])
 
 
 class OwnRowsFeed:
@@ -427,9 +450,10 @@ class OwnRowsFeed:
 
     def __init__(self, submit, groups, batch):
         self.submit, self.groups, self.batch, self.ticks = submit, groups, batch, 0
+        self.done = -1
 
     def tick(self, _i=None):
-        self.submit(self.groups[self.ticks % len(self.groups)])
+        self.done = self.submit(self.groups[self.ticks % len(self.groups)])
         self.ticks += 1
 
 
@@ -587,8 +611,9 @@ class Run:
             self.step = lambda i: driver.step(self.d_frames[(i + 1) % self.nframes])
 
     def time_headline(self):
-        """untimed clock ramp, W warm-up steps, pass 1 (exactly K steps, nothing else in the region), pass 2 (events per launch)"""
-        args, torch, sess, step = self.args, self.torch, self.sess, self.step
+        """untimed clock ramp, W warm-up steps, exactly K timed steps (nothing else in the region); then, outside it, the outputs of
+        the last step when --dump-outputs asks for them"""
+        args, torch, step = self.args, self.torch, self.step
         # Untimed clock ramp: the first ~10 ms of a kernel stream run 15-20 % slower than the sustained rate on MI355X (a
         # 200-step run right after start-up measured 175-180k Mpix/s, the same steps after 0.1 s of load 210k+), and the default
         # timed region is only tens of ms long.  So the device first works for OFX_BENCH_RAMP_S seconds on the very steps that
@@ -597,8 +622,12 @@ class Run:
         t_ramp = time.perf_counter() + self.ramp_s
         i_ramp = 0
         self.fps = fps = args.batch if self.feed is not None else 1   # frames (pairs) per step
+        # (a multiple of four frames per round of the ramp: the frames repeat every four, so however long the ramp runs, the
+        # last timed step takes the same frames -- what --dump-outputs writes is the same from run to run)
+        ramp_round = max(8, 64 // fps)
+        ramp_round += -ramp_round % 4
         while time.perf_counter() < t_ramp:
-            for _ in range(max(8, 64 // fps)):
+            for _ in range(ramp_round):
                 step(i_ramp)
                 i_ramp += 1
             torch.cuda.synchronize()
@@ -610,8 +639,53 @@ class Run:
             step(args.warmup + i)
         self.fence()
         dt = time.perf_counter() - t0
-        # pass 2 -- the dominant kernel's duration: the same steps again with a pair of HIP events recorded around every
-        # launch on the stream it runs on (two extra packets per launch, so this pass is not the one timed above)
+        self.dt = self.max_over_ranks(dt)
+        self.outputs = self.last_step_outputs() if args.dump_outputs and self.rank == 0 else None
+
+    def last_step_outputs(self):
+        """{name: float32 array} of the flows the last timed step completed, as a caller of the timed path reads them: the newest
+        `batch` pairs of a stream tick (ofx_session_flow_of), the one pair of a pair-at-a-time step.  Arrays above their share of
+        DUMP_BUDGET_BYTES become a sample of their pixels, the same pixels (seeded by level) in every run and every pair."""
+        import numpy as np
+
+        torch, levels = self.torch, self.levels
+        torch.cuda.synchronize()
+        if self.feed is not None:
+            done, B = self.feed.done, self.args.batch
+            if done < B - 1:
+                raise SystemExit(f"bench.py --dump-outputs: the last step completed no full tick of pairs (highest pair {done})")
+            flows = [[self.sess.flow_of(done - B + 1 + j, k)[0] for k in range(levels)] for j in range(B)]
+        elif self.driver is not None:
+            flows = [[self.driver.backend.flow(k) for k in range(levels)]]
+        else:
+            flows = [[self.sess.flow(k)[0] for k in range(levels)]]
+        cap_px = DUMP_BUDGET_BYTES // (8 * len(flows) * levels)   # (u, v): 8 bytes a pixel
+        out = {}
+        for k in range(levels):
+            px = flows[0][k].shape[0] * flows[0][k].shape[1]
+            idx = None
+            if px > cap_px:
+                rng = np.random.default_rng(DUMP_SEED + k)
+                idx = torch.from_numpy(np.unique(rng.integers(0, px, cap_px))).to(flows[0][k].device)
+            for j, pair in enumerate(flows):
+                f = pair[k]
+                if idx is not None:
+                    f = f.reshape(px, 2).index_select(0, idx)
+                out[f"flow_pair{j}_level{k}"] = f.float().cpu().numpy()
+        return out
+
+    def write_outputs(self):
+        import numpy as np
+
+        d = self.args.dump_outputs
+        os.makedirs(d, exist_ok=True)
+        for name, a in self.outputs.items():
+            np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, np.float32))
+
+    def time_launches(self):
+        """--full, pass 2 -- the dominant kernel's duration: the same steps again with a pair of HIP events recorded around every
+        launch on the stream it runs on (two extra packets per launch, so this pass is not the one timed above)"""
+        args, sess, step = self.args, self.sess, self.step
         # (at least ~100 launches, so that a short driver run -- K = 20 -- still gives a stable average)
         self.roof_steps = roof_steps = max(args.steps, -(-400 // args.batch) if self.feed is not None else 400)
         sess.timing(roof_steps * (2 * max(1, args.iters) + 3))
@@ -621,7 +695,6 @@ class Run:
         self.kinds = {k: sess.timing_read_kind(k) for k in self.engine.Session.TIME_KINDS}
         self.k_avg_us, self.k_min_us, self.k_n = sess.timing_read()
         sess.timing(0)
-        self.dt = self.max_over_ranks(dt)
 
     # ---- board power and clock while the timed steps run (outside the timed region) -----------------------------------------
     def sample_power(self):
@@ -1221,17 +1294,12 @@ class Run:
         except Exception:
             return None, {}
 
-    def line(self, check_msg, extra):
-        args, driver, fps = self.args, self.driver, self.fps
-        w, h, levels, window = self.w, self.h, self.levels, self.window
-        ms = self.dt / args.steps * 1e3
-        stream_like = self.feed is not None
-        own_rows = None if driver is None else driver.plan.own
-        pairs_per_launch = args.batch if stream_like else 1   # a stream tick carries args.batch frames / pairs
+    def roofline(self, pairs_per_launch, own_rows):
+        """--full: the pair as a whole (every launch of the second pass, event-timed and tagged) and the launch kind it spends most of
+        its time in: the roofline object is the latter's -- algorithmic bytes of ONE launch as it runs / its average duration"""
+        args, w, h, levels = self.args, self.w, self.h, self.levels
         kinds = {k: v for k, v in self.kinds.items() if v[2]}
-        # the pair as a whole (every launch of the second pass, event-timed and tagged) and the launch kind it spends most of its
-        # time in: the roofline object is the latter's -- algorithmic bytes of ONE launch as it runs / its average duration
-        whole = pair_roofline(kinds, self.roof_steps * fps, w, h, levels, args.iters, own_rows, pairs_per_launch)
+        whole = pair_roofline(kinds, self.roof_steps * self.fps, w, h, levels, args.iters, own_rows, pairs_per_launch)
         dom = dominant_block(kinds, pairs_per_launch, w, h, levels, args.iters, own_rows)
         tkey = {"stream": "stream_kernel", "lk": "lk_level_kernel", "lk_acc_warp": "lk_iter_kernel_iter2", "lk_acc": "lk_iter_kernel_iter1"}.get(dom["kind"], dom["kind"])
         if args.mode != "lk_float":
@@ -1239,6 +1307,17 @@ class Run:
         traffic, traffic_src = self.traffic(tkey)
         if traffic is not None and traffic_src.get("traffic_pairs_per_launch") not in (None, pairs_per_launch):
             traffic = traffic * pairs_per_launch / traffic_src["traffic_pairs_per_launch"]   # (profiled at another tick size: per pair it is the same launch)
+        out = dict(dom, timed_in="second pass over the same steps with hipEventRecord around each launch on its stream", traffic=traffic, **traffic_src)
+        out["whole_pair"] = whole
+        return out
+
+    def line(self, check_msg, extra):
+        args, driver, fps = self.args, self.driver, self.fps
+        w, h, levels, window = self.w, self.h, self.levels, self.window
+        ms = self.dt / args.steps * 1e3
+        stream_like = self.feed is not None
+        own_rows = None if driver is None else driver.plan.own
+        pairs_per_launch = args.batch if stream_like else 1   # a stream tick carries args.batch frames / pairs
         borrowed = args.borrow and ((driver is None and args.path == "stream") or
                                     (driver is not None and args.shard_corner == "local" and args.shard_halo != "exchange"))
         frames_what = ("SURVEY 8d's smooth texture translating by (2,1) px per frame" if args.frames == "texture"
@@ -1291,7 +1370,7 @@ class Run:
             "vs_baseline": None,
             "dtype": "i32/f64",
             "data": "synthetic",
-            "self_check": "skipped" if check_msg.startswith("SKIPPED") else "ok",
+            "self_check": "not run (--full runs it)" if check_msg is None else "skipped" if check_msg.startswith("SKIPPED") else "ok",
             "config": {
                 "workload": f"{w}x{h} pair, {levels}-level pyramid, {window}x{window} window, iters={args.iters} "
                             f"({'the only value the reference defines' if args.iters <= 1 else 'BASELINE.json config as written; iterations = extension lk_iter: bilinear-warp refinement, iteration 1 = the reference bit for bit'}), "
@@ -1304,9 +1383,9 @@ class Run:
                 "sharding": sharding,
                 "self_check": check_msg,
             },
-            "roofline": dict(dom, timed_in="second pass over the same steps with hipEventRecord around each launch on its stream", traffic=traffic, **traffic_src),
         }
-        out["roofline"]["whole_pair"] = whole
+        if getattr(self, "kinds", None) is not None:
+            out["roofline"] = self.roofline(pairs_per_launch, own_rows)
         if getattr(self, "power", None):
             out["power"] = self.power
         if self.rccl_world is not None:
@@ -1328,19 +1407,24 @@ def main():
     run = Run(args)
     run.build_headline()
     run.time_headline()
-    run.power = run.sample_power()
-    # (timing experiments with ablated kernels, OFX_BUILD_DEFS=-DOFX_X_*: their results are wrong by construction)
-    check_msg = "SKIPPED (OFX_BENCH_SKIP_CHECK)" if os.environ.get("OFX_BENCH_SKIP_CHECK") == "1" else run.self_check()
-    if run.distributed:
-        run.dist.barrier()
-    extra = {}
-    if run.driver is not None:
-        extra.update(run.extras_distributed())
+    if run.outputs is not None:
+        run.write_outputs()
+    check_msg, extra = None, {}
+    if args.full:
+        # everything the line reports besides the headline: event-timed launches, power, the self-check, the extra legs
+        run.time_launches()
+        run.power = run.sample_power()
+        # (timing experiments with ablated kernels, OFX_BUILD_DEFS=-DOFX_X_*: their results are wrong by construction)
+        check_msg = "SKIPPED (OFX_BENCH_SKIP_CHECK)" if os.environ.get("OFX_BENCH_SKIP_CHECK") == "1" else run.self_check()
+        if run.distributed:
+            run.dist.barrier()
+        if run.driver is not None:
+            extra.update(run.extras_distributed())
     if run.rank == 0:
-        if run.driver is None and not args.no_extras:
+        if args.full and run.driver is None and not args.no_extras:
             extra.update(run.extras_single_gpu())
         out = run.line(check_msg, extra)
-        if run.driver is None and not args.no_cpu_baseline:
+        if args.full and run.driver is None and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.workload, run.w, run.h, run.levels, run.window)
         print(json.dumps(out), flush=True)
     if run.distributed:

@@ -129,7 +129,23 @@ def surface():
     save("surface", **d)
 
 
+def ref_calls():
+    """tests/test_oracle_vs_ref.py's calls into the reference, one file per test under ref_calls/: that module records them
+    itself when RECORD_ENV is set (the differential tests then run where oracle/_ref is absent)"""
+    import subprocess
+
+    env = dict(os.environ, OFX_RECORD_REF_CALLS="1")
+    subprocess.check_call([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", os.path.join(ROOT, "tests", "test_oracle_vs_ref.py")],
+                          env=env, cwd=ROOT)
+    d = os.path.join(OUT, "ref_calls")
+    for f in sorted(os.listdir(d)):
+        print(f"ref_calls/{f}  {os.path.getsize(os.path.join(d, f))} bytes")
+
+
 if __name__ == "__main__":
+    if "--only-ref-calls" in sys.argv:
+        ref_calls()
+        sys.exit(0)
     surface()
     if "--only-surface" in sys.argv:
         sys.exit(0)
@@ -137,3 +153,4 @@ if __name__ == "__main__":
     shifts()
     levels_and_pairs()
     bilateral()
+    ref_calls()

@@ -1,10 +1,13 @@
 """bench.py --gpus N outside torch.distributed.run: the driver starts the N > 1 bench exactly as it starts
 --gpus 1.  bench.py must then start torch.distributed.run itself, as a CHILD process, before anything touches the GPU, and pass
-the child's exit code on.  No GPU here: the ranks report how far they got (OFX_BENCH_RANK_PROBE) or fail at torch.cuda."""
+the child's exit code on.  No GPU here: the ranks report how far they got (OFX_BENCH_RANK_PROBE) or fail at torch.cuda.
+Also: what a plain run is (no --full) and, on the GPU, what --dump-outputs writes."""
 import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -101,3 +104,62 @@ def test_power_reading_is_parsed_from_rocm_smi_text():
         "GPU[0]\\t\\t: Max Graphics Package Power (W): 1400.0\\n")
     assert bench.parse_rocm_smi(text) == (1374.0, 1400.0, 2184)
     assert bench.parse_rocm_smi("no such tool") == (None, None, None)
+
+
+def test_a_plain_run_is_the_headline_and_steps_are_the_timed_steps():
+    """--full (roofline pass, power, self-check, extra legs, CPU baseline) is off by default; --steps is the number of timed steps"""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    old = sys.argv
+    try:
+        sys.argv = ["bench.py"]
+        a = bench.parse_args()
+        assert not a.full and a.dump_outputs is None
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "out", "--steps", "7", "--warmup", "0"]
+        a = bench.parse_args()
+        assert a.full and a.dump_outputs == "out" and a.steps == 7 and a.warmup == 0
+    finally:
+        sys.argv = old
+    r = _run(["--steps", "0"], {})
+    assert r.returncode != 0 and "--steps" in r.stderr, r.stderr[-2000:]
+
+
+@pytest.mark.gpu
+def test_dumped_outputs_are_the_flows_of_the_last_timed_step(tmp_path):
+    """--dump-outputs: a plain run writes every level of the pairs its last step completed, float32, within 64 MB -- and they are
+    the flows a plain session computes for the same frames (pair j of the step: frame j - 1 -> frame j of the four that repeat)"""
+    import numpy as np
+    import torch
+
+    from conftest import assert_same
+    from cuda_optical_flow_2_amd import engine, synth
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    d = tmp_path / "out"
+    r = _run(["--workload", "vga", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)], {})
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and "roofline" not in line and "extra" not in line
+    w, h, levels, window = bench.WORKLOADS["vga"]
+    B = line["frames_per_step"]
+    files = sorted(os.listdir(d))
+    assert files == sorted(f"flow_pair{j}_level{k}.npy" for j in range(B) for k in range(levels))
+    assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+    frames = [torch.from_numpy(synth.smooth_pair(w, h, 2.0 * i, 1.0 * i)[1]).cuda() for i in range(4)]
+    s = engine.Session(w, h, levels, window, "lk_float", iters=bench.BASELINE_ITERS["vga"])
+    cap = bench.DUMP_BUDGET_BYTES // (8 * B * levels)
+    for j in range(B):
+        s.set_frame_device(frames[(j - 1) % 4]); s.build_pyramid(); s.swap()
+        s.set_frame_device(frames[j % 4]); s.build_pyramid(); s.run_flow()
+        for k in range(levels):
+            want = s.flow(k)[0].cpu().numpy()
+            px = want.shape[0] * want.shape[1]
+            if px > cap:
+                want = want.reshape(px, 2)[np.unique(np.random.default_rng(bench.DUMP_SEED + k).integers(0, px, cap))]
+            got = np.load(d / f"flow_pair{j}_level{k}.npy")
+            assert got.dtype == np.float32
+            assert_same(got, want, f"pair {j} level {k}")
+    s.close()

@@ -1,10 +1,98 @@
 """CPU: differential test of the oracle restatement against the reference's own CPU sources compiled in the build
-container (oracle/_ref/libref_cpu.so).  Skipped where that build is absent."""
+container (oracle/_ref/libref_cpu.so).  Where that build is absent, the tests run against what it returned for exactly
+these calls, recorded under tests/golden/ref_calls/ (tests/golden/make_golden.py); where it is present, they call it and
+check that it still returns what was recorded."""
+import os
+import re
+
 import numpy as np
 import pytest
 
-from conftest import assert_same
+from conftest import GOLDEN, assert_same
 from cuda_optical_flow_2_amd import synth
+
+RECORDED = os.path.join(GOLDEN, "ref_calls")
+RECORD_ENV = "OFX_RECORD_REF_CALLS"   # set by make_golden.py: the live reference's results are written instead of checked
+
+
+def _encode(out, key, v):
+    if v is None:
+        out[key + "__none"] = np.zeros(0)
+    elif isinstance(v, (list, tuple)):
+        out[key + "__seq"] = np.array(len(v))
+        for i, x in enumerate(v):
+            _encode(out, f"{key}_{i}", x)
+    else:
+        out[key] = np.asarray(v)
+
+
+def _decode(store, key):
+    if key + "__none" in store:
+        return None
+    if key + "__seq" in store:
+        return [_decode(store, f"{key}_{i}") for i in range(int(store[key + "__seq"]))]
+    return store[key]
+
+
+class _Recording:
+    """The live reference; every result is kept, keyed by the order of the calls and the name called"""
+
+    def __init__(self, live):
+        self.live, self.out, self.n = live, {}, 0
+
+    def __getattr__(self, name):
+        v = getattr(self.live, name)
+        if not callable(v):
+            _encode(self.out, f"attr__{name}", v)
+            return v
+
+        def call(*args, **kw):
+            r = v(*args, **kw)
+            _encode(self.out, f"call{self.n}__{name}", r)
+            self.n += 1
+            return r
+        return call
+
+
+class _Replay:
+    """What the reference returned for the same calls in the same order"""
+
+    def __init__(self, store):
+        self.store, self.n = store, 0
+
+    def __getattr__(self, name):
+        if f"attr__{name}" in self.store:
+            return _decode(self.store, f"attr__{name}")
+
+        def call(*args, **kw):
+            key = f"call{self.n}__{name}"
+            assert key in self.store or key + "__seq" in self.store or key + "__none" in self.store, \
+                f"no recorded result for call {self.n} ({name}): tests/golden/make_golden.py records them"
+            self.n += 1
+            return _decode(self.store, key)
+        return call
+
+
+@pytest.fixture
+def ref(request):
+    """(overrides conftest's) the reference's own CPU build when it is here, else its recorded results for this test"""
+    import oracle as orc
+
+    path = os.path.join(RECORDED, re.sub(r"[^A-Za-z0-9_]+", "_", request.node.name).strip("_") + ".npz")
+    if not orc.have_reference():
+        with np.load(path) as z:
+            yield _Replay({k: z[k] for k in z.files})
+        return
+    rec = _Recording(orc.Reference())
+    yield rec
+    if os.environ.get(RECORD_ENV) == "1":
+        os.makedirs(RECORDED, exist_ok=True)
+        np.savez_compressed(path, **rec.out)
+        return
+    with np.load(path) as z:
+        assert sorted(z.files) == sorted(rec.out), f"{path}: the calls differ from the recorded ones (tests/golden/make_golden.py)"
+        for k in z.files:
+            assert_same(rec.out[k], z[k], f"live reference vs {os.path.basename(path)}[{k}]")
 
 
 @pytest.mark.parametrize("seed", [0, 1])

@@ -10,7 +10,7 @@ mkdir -p $O
 : > $O/summary.txt
 grep -v '^\s*#' "$PLAN" | grep -v '^\s*$' | while IFS='|' read -r name envs args; do
   name=$(echo $name); 
-  env $envs python bench.py --no-cpu-baseline --no-extras $args > $O/$name.json 2> $O/$name.err || echo "fail $name" | tee -a $O/summary.txt
+  env $envs python bench.py --full --no-cpu-baseline --no-extras $args > $O/$name.json 2> $O/$name.err || echo "fail $name" | tee -a $O/summary.txt
   python - "$name" "$O/$name.json" "$envs $args" >> $O/summary.txt <<'PY'
 import json, sys
 try:

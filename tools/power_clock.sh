@@ -2,7 +2,7 @@
 #   gpurun -- 'bash tools/power_clock.sh gpurun_out/pc_i5 [bench.py args...]'
 O=${1:?out prefix}; shift
 cd ${GRAFT_REPO_ROOT:-.}
-python bench.py --no-extras --no-cpu-baseline --steps ${STEPS:-5000} "$@" > $O.json 2> $O.err &
+python bench.py --full --no-extras --no-cpu-baseline --steps ${STEPS:-5000} "$@" > $O.json 2> $O.err &
 BP=$!
 sleep ${LEAD:-14}   # (import torch + session set-up: the timed region starts ~12 s in on a fresh box)
 for i in $(seq 1 ${N:-10}); do

@@ -57,7 +57,7 @@ fi
 stats() { # name, bench args...
   n=$1; shift
   want $n || return 0
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$n -- python bench.py --no-cpu-baseline --no-extras "$@" > $O/summary/${TAG}_bench4k_$n.json 2> $O/$n.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$n -- python bench.py --full --no-cpu-baseline --no-extras "$@" > $O/summary/${TAG}_bench4k_$n.json 2> $O/$n.err
   f=$(find $O/$n -name "*kernel_stats.csv" | head -1); cp "$f" $O/summary/${TAG}_bench4k_${n}_kernel_stats.csv
   echo "== $n"; head -4 "$f"
 }
@@ -71,7 +71,7 @@ stats random --iters 1 --frames random
 # the other BASELINE configurations as written: file names say which
 stats8() { n=$1; shift
   want $n || return 0
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$n -- python bench.py --no-cpu-baseline --no-extras "$@" > $O/summary/${TAG}_bench_$n.json 2> $O/$n.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$n -- python bench.py --full --no-cpu-baseline --no-extras "$@" > $O/summary/${TAG}_bench_$n.json 2> $O/$n.err
   f=$(find $O/$n -name "*kernel_stats.csv" | head -1); cp "$f" $O/summary/${TAG}_bench_${n}_kernel_stats.csv
   echo "== $n"; head -4 "$f"
 }
