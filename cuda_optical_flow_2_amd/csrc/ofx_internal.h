@@ -81,3 +81,17 @@ int ofx_pyramid_corner_1ch(const uint8_t *d_level0, int pitch0, int w, int h, ui
 // sharded sessions whose shift vectors come from another rank: raise status bit 8 + k when level k's vertical shift sends the
 // shard's reads (rows [need0, need1) before the shift) to image rows outside [valid0, valid1); shard_rows = 4 ints per level
 int ofx_shard_margin_check(const float *d_uv, int levels, const int *heights, const int *shard_rows, int *d_status, void *stream);
+
+// the stream pipeline's output stage (compose_ring.hip): the dense field (main.cu:138-147, = ofx_compose_flow at `level`) of
+// n <= OFX_STREAM_MAX_BATCH pairs in one launch.  Pair i reads lv[i][k] (k = level .. levels-1; each points at global row own0[k]
+// of its level, rows tightly packed, w >> (k - level) wide) and writes its rows x w x 2 floats tightly packed at dst[i]
+// (16-byte aligned).  Own row y of the output reads row ((own0[level] + y) >> (k - level)) - own0[k] of level k: the caller
+// sees that every such row is one the pair's level k holds.
+struct ofx_compose_batch {
+    const float *lv[OFX_STREAM_MAX_BATCH][OFX_MAX_LEVELS];
+    float *dst[OFX_STREAM_MAX_BATCH];
+    int own0[OFX_MAX_LEVELS];
+    int n, w, rows, levels, level;
+    unsigned n_px; // w * rows
+};
+int ofx_compose_batch_launch(const ofx_compose_batch *a, void *stream);

@@ -95,6 +95,11 @@ struct ofx_session {
     size_t ev_used = 0;
     hipEvent_t ev_frame = nullptr; // staged path: the caller's frame is complete (caller's stream -> aux)
     int n_sets = 0;                // image sets allocated (3B + 2; the pair-at-a-time paths rotate the first three)
+    // ofx_session_stream_compose: the caller's ring of composed fields (nullptr: off), and the newest pair composed into it
+    float *ring = nullptr;
+    size_t ring_stride = 0; // bytes from slot to slot
+    int ring_slots = 0, ring_level = 0;
+    long composed = 0;
 };
 
 // Runs `launch` bracketed by a pair of timing events of kind `kind` when the session is armed (ofx_session_timing).
@@ -102,7 +107,8 @@ template <typename F>
 static int timed_launch(ofx_session *s, int kind, void *stream, F &&launch)
 {
     static const char *const names[OFX_TIME_KINDS] = {"ofx.lk_levels", "ofx.lk_levels_accumulate", "ofx.warp_levels", "ofx.stream_tick",
-                                                      "ofx.shift_levels", "ofx.corner_flows", "ofx.pyramid", "ofx.lk_levels_accumulate_warp"};
+                                                      "ofx.shift_levels", "ofx.corner_flows", "ofx.pyramid", "ofx.lk_levels_accumulate_warp",
+                                                      "ofx.compose_ring"};
     OfxRange range(names[kind]); // (roctx, OFX_ROCTX=1: the launch's enqueue on the host side of a --marker-trace timeline)
     const bool timed = s->timing && s->ev_used + 2 <= s->ev.size();
     if (timed) OFX_HIP(hipEventRecord(s->ev[s->ev_used], ofx_stream(stream)));
@@ -929,6 +935,26 @@ extern "C" int ofx_session_pair_status(ofx_session *s, int pair, int *h_status, 
 // tick every pair <= f0-B-1 is done.
 static int stream_batch_of(const ofx_session *s) { return s->p.stream_batch >= 2 ? s->p.stream_batch : 1; }
 
+// One launch composing pairs first .. last (the pairs a call of the pipeline completes) into their ring slots.
+static int compose_ring(ofx_session *s, long first, long last, void *stream)
+{
+    const int B = stream_batch_of(s), lv = s->ring_level;
+    static thread_local ofx_compose_batch cb; // (1.7 KB)
+    memset(&cb, 0, sizeof cb);
+    cb.w = s->w[lv];
+    cb.rows = s->own1[lv] - s->own0[lv];
+    cb.n_px = (unsigned)((size_t)cb.w * (size_t)cb.rows);
+    cb.levels = s->p.levels;
+    cb.level = lv;
+    for (int k = 0; k < s->p.levels; ++k) cb.own0[k] = s->own0[k];
+    for (long p = first; p <= last; ++p, ++cb.n) {
+        for (int k = lv; k < s->p.levels; ++k) cb.lv[cb.n][k] = s->flowset[p % B][k] + s->flow_own_offset(k);
+        cb.dst[cb.n] = reinterpret_cast<float *>(reinterpret_cast<char *>(s->ring) + (size_t)((p - 1) % s->ring_slots) * s->ring_stride);
+    }
+    s->composed = last;
+    return timed_launch(s, OFX_TIME_COMPOSE, stream, [&] { return ofx_compose_batch_launch(&cb, stream); });
+}
+
 static int stream_tick(ofx_session *s, const uint8_t *const *frames, const int *pitches, int n_frames, void *stream, int *completed_pair)
 {
     const int B = stream_batch_of(s);
@@ -1065,7 +1091,7 @@ static int stream_tick(ofx_session *s, const uint8_t *const *frames, const int *
             }
         }
     }
-    long newest = -1;
+    long newest = -1, oldest = -1; // the pairs this call completes: oldest .. newest
     static thread_local ofx_shift_desc sd0[OFX_MAX_LK_ITEMS];
     int ns0 = 0;
     for (long pl = f0 - D * B; pl <= f0 - D * B + B - 1; ++pl) { // LK(pair pl), reading next through the shift vectors the previous tick wrote
@@ -1095,6 +1121,7 @@ static int stream_tick(ofx_session *s, const uint8_t *const *frames, const int *
                 if (s->p.sharded) d.d_warp_status = s->corner_status, d.warp_status_bit = 16 + k; // (a tap row beyond the halo rows)
             }
         }
+        if (oldest < 0) oldest = pl;
         newest = pl;
     }
     if (ns0) OFX_TRY(timed_launch(s, OFX_TIME_SHIFT, stream, [&] { return ofx_shift_levels(sd0, ns0, stream); }));
@@ -1171,6 +1198,9 @@ static int stream_tick(ofx_session *s, const uint8_t *const *frames, const int *
             OFX_TRY(timed_launch(s, wout ? OFX_TIME_LK_ACC_WARP : OFX_TIME_LK_ACC, stream, [&] { return ofx_lk_levels(ld, nw, s->p.window, s->p.mode, stream); }));
         }
     }
+    // the output stage (ofx_session_stream_compose): behind the tick's last launch on the same stream, before the next tick
+    // rewrites flow set p mod B
+    if (s->ring && newest >= 1) OFX_TRY(compose_ring(s, oldest, newest, stream));
     s->stream_n = f0 + B;
     return OFX_OK;
 }
@@ -1191,6 +1221,7 @@ extern "C" int ofx_session_stream_begin(ofx_session *s)
     s->n_held = 0;
     s->reported = 0;
     s->corner_newest = 0;
+    s->composed = 0;
     s->have_prev = s->have_next = s->staged = false;
     s->corner_done = false;
     s->pset_img[0] = s->pset_img[1] = -1;
@@ -1275,6 +1306,65 @@ extern "C" int ofx_session_flow_of(ofx_session *s, int pair, int level, float **
     if (d_ptr) *d_ptr = s->flowset[pair % B][level] + s->flow_own_offset(level);
     if (row0) *row0 = s->own0[level];
     if (rows) *rows = s->own1[level] - s->own0[level];
+    return OFX_OK;
+}
+
+extern "C" int ofx_session_stream_compose(ofx_session *s, int level, float *d_ring, size_t slot_stride_bytes, int n_slots)
+{
+    OFX_REQUIRE(s, "ofx_session_stream_compose: null session");
+    if (s->stream_n > 0 || s->n_held > 0) {
+        ofx_set_error("ofx_session_stream_compose: the stream has frames already; set the ring before the first frame of a stream");
+        return OFX_E_STATE;
+    }
+    if (!d_ring) {
+        s->ring = nullptr;
+        s->composed = 0;
+        return OFX_OK;
+    }
+    const int B = stream_batch_of(s);
+    OFX_REQUIRE(level >= 0 && level < s->p.levels, "ofx_session_stream_compose: level %d out of range (0 .. %d)", level, s->p.levels - 1);
+    OFX_REQUIRE(n_slots >= B, "ofx_session_stream_compose: %d slots, the ring needs at least stream_batch = %d (the pairs one call completes)",
+                n_slots, B);
+    const size_t slot_bytes = (size_t)(s->own1[level] - s->own0[level]) * (size_t)s->w[level] * 2 * sizeof(float);
+    OFX_REQUIRE(((uintptr_t)d_ring & 15) == 0, "ofx_session_stream_compose: the ring must be 16-byte aligned");
+    OFX_REQUIRE(slot_stride_bytes % 16 == 0 && slot_stride_bytes >= slot_bytes,
+                "ofx_session_stream_compose: slot stride %zu bytes must be a multiple of 16 and at least the slot's %zu bytes", slot_stride_bytes,
+                slot_bytes);
+    if (slot_bytes / 8 >= ((size_t)1 << 31)) {
+        ofx_set_error("ofx_session_stream_compose: a slot of %zu pixels is more than this build composes (2^31)", slot_bytes / 8);
+        return OFX_E_UNSUPPORTED;
+    }
+    // a rank composes its own rows: own row y at `level` reads row y >> (k - level) of level k, which must be one of the rows the
+    // rank computes there (ShardPlan's rows are the coarsest level's, doubled per level)
+    for (int k = level + 1; k < s->p.levels && s->own1[level] > s->own0[level]; ++k) {
+        const int sc = k - level;
+        if ((s->own0[level] >> sc) < s->own0[k] || ((s->own1[level] - 1) >> sc) >= s->own1[k]) {
+            ofx_set_error("ofx_session_stream_compose: own rows [%d,%d) of level %d read rows [%d,%d] of level %d, which owns [%d,%d)", s->own0[level],
+                          s->own1[level], level, s->own0[level] >> sc, (s->own1[level] - 1) >> sc, k, s->own0[k], s->own1[k]);
+            return OFX_E_UNSUPPORTED;
+        }
+    }
+    s->ring = d_ring;
+    s->ring_stride = slot_stride_bytes;
+    s->ring_slots = n_slots;
+    s->ring_level = level;
+    s->composed = 0;
+    return OFX_OK;
+}
+
+extern "C" int ofx_session_composed_of(ofx_session *s, int pair, float **d_ptr, int *row0, int *rows)
+{
+    OFX_REQUIRE(s, "ofx_session_composed_of: null session");
+    if (!s->ring) {
+        ofx_set_error("ofx_session_composed_of: no ring set (ofx_session_stream_compose)");
+        return OFX_E_STATE;
+    }
+    OFX_REQUIRE(pair >= 1 && pair <= s->composed && pair > s->composed - s->ring_slots,
+                "ofx_session_composed_of: pair %d is not among the newest %d composed pairs (newest: %ld)", pair, s->ring_slots, s->composed);
+    const int lv = s->ring_level;
+    if (d_ptr) *d_ptr = reinterpret_cast<float *>(reinterpret_cast<char *>(s->ring) + (size_t)((pair - 1) % s->ring_slots) * s->ring_stride);
+    if (row0) *row0 = s->own0[lv];
+    if (rows) *rows = s->own1[lv] - s->own0[lv];
     return OFX_OK;
 }
 

@@ -110,6 +110,7 @@ class Session:
         self._h = _vp()
         check(self.L.ofx_session_create(C.byref(p), C.byref(self._h)), "ofx_session_create")
         self._keep = []
+        self._ring, self._ring_level = None, 0
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -256,7 +257,8 @@ class Session:
         check(self.L.ofx_session_timing_read(self._h, C.byref(avg), C.byref(mn), C.byref(n)), "session_timing_read")
         return avg.value, mn.value, n.value
 
-    TIME_KINDS = {"lk": 0, "lk_acc": 1, "warp": 2, "stream": 3, "shift": 4, "corner": 5, "pyramid": 6, "lk_acc_warp": 7}   # OFX_TIME_*
+    TIME_KINDS = {"lk": 0, "lk_acc": 1, "warp": 2, "stream": 3, "shift": 4, "corner": 5, "pyramid": 6, "lk_acc_warp": 7,
+                  "compose": 8}   # OFX_TIME_*
 
     def timing_read_kind(self, kind: str):
         """(average us, minimum us, launches) of one kind of launch; call before timing_read, which re-arms."""
@@ -285,6 +287,37 @@ class Session:
         check(self.L.ofx_session_flow_of(self._h, pair, level, C.byref(ptr), C.byref(r0), C.byref(rows)), "session_flow_of")
         w = self.width >> level
         return DeviceView(ptr.value, (rows.value, w, 2), "<f4").tensor(), r0.value
+
+    def stream_compose(self, ring, level: int = 0):
+        """The stream pipeline's output stage (ofx_session_stream_compose): every pair it completes is composed at `level`
+        (main.cu:138-147, the reference's dense field, bit for bit) into slot (p - 1) mod n_slots of `ring`, by one more launch
+        per completing call on that call's stream.  ring: float32 CUDA tensor [n_slots, rows, width >> level, 2] (rows = the
+        level's own rows), rows tightly packed, the slot stride (stride(0)) free as long as it is 16-byte aligned; n_slots >=
+        stream_batch.  None turns it off.  Only before the first frame of a stream; stays in effect for later streams."""
+        if ring is None:
+            check(self.L.ofx_session_stream_compose(self._h, 0, None, 0, 0), "stream_compose")
+            self._ring = None
+            return
+        import torch
+
+        w = self.width >> level
+        rows = (self.height >> level) if self.shard is None else self.shard.own[level][1] - self.shard.own[level][0]
+        assert ring.is_cuda and ring.dtype == torch.float32 and ring.dim() == 4, "ring: float32 CUDA tensor [n_slots, rows, w, 2]"
+        assert tuple(ring.shape[1:]) == (rows, w, 2), f"ring slots must be [{rows}, {w}, 2], got {tuple(ring.shape[1:])}"
+        assert ring.stride()[1:] == (2 * w, 2, 1), "ring: the rows of a slot must be tightly packed"
+        check(self.L.ofx_session_stream_compose(self._h, level, ring.data_ptr(), 4 * int(ring.stride(0)), int(ring.shape[0])),
+              "stream_compose")
+        self._ring = ring
+        self._ring_level = level
+        self._keep.append(ring)
+
+    def composed_of(self, pair: int):
+        """torch float32 view [rows, width >> level, 2] of `pair`'s slot in the ring (ofx_session_composed_of), while it is one
+        of the newest n_slots composed pairs; valid once the launch of the call that reported the pair has run."""
+        ptr, r0, rows = _vp(), C.c_int(), C.c_int()
+        check(self.L.ofx_session_composed_of(self._h, pair, C.byref(ptr), C.byref(r0), C.byref(rows)), "session_composed_of")
+        w = self.width >> self._ring_level
+        return DeviceView(ptr.value, (rows.value, w, 2), "<f4").tensor()
 
     def uv(self, level: int):
         """Shift vector of `level` for the pair in progress (the slot alternates per pair: query after every swap)."""
@@ -434,3 +467,56 @@ def flow_pair(prev1: np.ndarray, next1: np.ndarray, levels: int, window: int, mo
         return [s.flow_host(k) for k in range(levels)]
     finally:
         s.close()
+
+
+def video_flow(frames, levels: int, window: int, mode: str = "lk_float", level: int = 0, iters: int = 1, min_det: float = 0.0,
+               batch: Optional[int] = None, out=None):
+    """Dense flow of every consecutive pair of a clip, in one call: the field of main.cu:138-147 -- sum over k >= level of
+    2^(k-level) * flow_k(y >> (k-level), x >> (k-level)), the reference's only definition of the final result -- composed
+    at `level` by the stream pipeline's output stage, bit for bit the reference's (ofx_compose_flow of the pair's flow pyramid).
+
+    frames: uint8 CUDA tensor [N, H, W], N >= 2, unit column stride (rows and frames may be strided).  Returns float32
+    [N-1, H >> level, W >> level, 2]: out[p-1] is the flow of frame p-1 -> frame p.  The result tensor itself is the ring the
+    pipeline writes (no copies); `out` may supply it (same shape, tightly packed rows, 16-byte aligned slots).  Frames are
+    read in place when their pitch and alignment allow it (with iters > 1: a pitch of the width rounded up to 64), otherwise
+    through copies.  stream_batch: `batch`, or suggest_stream_batch, at most N-1.  Work is enqueued on the current torch stream;
+    the call returns once the pipeline has drained, and raises when a pair is not the reference's result (strict)."""
+    import torch
+
+    assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 3, "frames: uint8 CUDA tensor [N, H, W]"
+    N, H, W = (int(v) for v in frames.shape)
+    assert N >= 2 and frames.stride(2) == 1, "frames: at least two, with unit column stride"
+    assert 0 <= level < levels
+    hl, wl = H >> level, W >> level
+    slot = hl * wl * 2
+    stride = (slot + 3) // 4 * 4        # floats from slot to slot: a multiple of 16 bytes
+    if out is None:
+        flat = torch.empty((N - 1) * stride, dtype=torch.float32, device=frames.device)
+        out = flat.as_strided((N - 1, hl, wl, 2), (stride, 2 * wl, 2, 1))
+    else:
+        assert out.dtype == torch.float32 and tuple(out.shape) == (N - 1, hl, wl, 2), f"out must be float32 [{N - 1}, {hl}, {wl}, 2]"
+    pitch, fstride, ptr = int(frames.stride(1)), int(frames.stride(0)), frames.data_ptr()
+    aligned = pitch % 4 == 0 and fstride % 4 == 0 and ptr % 4 == 0 and pitch >= W
+    # (the kernels read a borrowed frame's rows in 4-byte groups: the last row's pitch must lie inside the tensor's storage)
+    st = frames.untyped_storage()
+    inside = ptr + (N - 1) * fstride + H * pitch <= st.data_ptr() + st.nbytes()
+    if aligned and inside:
+        borrow = iters <= 1 or pitch == pitch_for(W)   # (else the session copies every frame into its own planes)
+    else:
+        padded = torch.empty((N, H, pitch_for(W)), dtype=torch.uint8, device=frames.device)
+        padded[:, :, :W] = frames
+        frames, borrow = padded[:, :, :W], True
+    B = batch if batch is not None else suggest_stream_batch(W, H, levels, borrow_frames=borrow, two_stage=borrow)
+    B = max(1, min(int(B), N - 1))
+    s = Session(W, H, levels, window, mode, iters=iters, min_det=min_det, stream_batch=B, borrow_frames=borrow, two_stage=borrow,
+                strict=True)
+    try:
+        s.stream_compose(out, level)
+        s.stream_begin()
+        for i in range(N):
+            s.stream_submit(frames[i])
+        while s.stream_drain() != -2:
+            pass
+    finally:
+        s.close()
+    return out

@@ -100,6 +100,8 @@ _SIGS = {
     "ofx_stage_threads": [],
     "ofx_debug_stream_trace": [_vp, _i, C.POINTER(_i)],
     "ofx_session_flow_of": [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i)],
+    "ofx_session_stream_compose": [_vp, _i, _vp, C.c_size_t, _i],
+    "ofx_session_composed_of": [_vp, _i, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i)],
     "ofx_session_stream_submit": [_vp, _vp, _i, _vp, C.POINTER(_i)],
     "ofx_session_stream_drain": [_vp, _vp, C.POINTER(_i)],
     "ofx_session_stream_submit_frames": [_vp, C.POINTER(_vp), C.POINTER(_i), _i, _i, _vp, C.POINTER(_i)],

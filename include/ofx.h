@@ -500,6 +500,24 @@ int ofx_session_stream_submit_frames(ofx_session *s, const uint8_t *const *d_gra
 /* Flow of `pair` at `level` while it is one of the newest stream_batch completed pairs of the stream pipeline (pair p
  * lives in flow set p mod stream_batch).  Same outputs as ofx_session_flow. */
 int ofx_session_flow_of(ofx_session *s, int pair, int level, float **d_ptr, int *row0, int *rows);
+/* Composed dense flow (main.cu:138-147, = ofx_compose_flow at `level`, bit for bit) of every pair the stream pipeline
+ * completes, written by the pipeline into a caller-owned ring: pair p (frames counted from 0, pair p = frame p-1 -> frame p)
+ * goes to slot (p - 1) mod n_slots at d_ring + slot * slot_stride_bytes, rows x (width >> level) x 2 floats, tightly packed
+ * (rows = the level's own rows, as ofx_session_flow_of reports them; a sharded session composes its own rows, and is refused
+ * with OFX_E_UNSUPPORTED when they would read coarse rows it does not own).  Every call of ofx_session_stream_submit /
+ * _submit_frames / _drain that completes pairs enqueues ONE more launch on its `stream`, after the call's last launch, that
+ * writes the slots of all those pairs (timing kind OFX_TIME_COMPOSE).
+ * Lifetime: the slot of pair p is written by the launch that the call reporting p complete enqueues on its `stream`, and
+ * overwritten by the launch of pair p + n_slots; reading it on another stream or from the host needs that launch to have
+ * completed.  The ring must stay allocated while the pipeline may write it.
+ * d_ring 16-byte aligned, slot_stride_bytes a multiple of 16 and at least the slot's size, 0 <= level < levels,
+ * n_slots >= stream_batch (the pairs one call completes); otherwise OFX_E_INVALID.  d_ring == NULL turns it off (the default:
+ * no launch, no allocation).  Only before the first frame of a stream (before or right after ofx_session_stream_begin);
+ * OFX_E_STATE once a stream has frames.  Stays in effect for later streams. */
+int ofx_session_stream_compose(ofx_session *s, int level, float *d_ring, size_t slot_stride_bytes, int n_slots);
+/* Slot of `pair` while it is one of the newest n_slots pairs composed into the ring; row0 / rows as ofx_session_flow_of.
+ * OFX_E_STATE without a ring, OFX_E_INVALID for a pair not (or no longer) in it. */
+int ofx_session_composed_of(ofx_session *s, int pair, float **d_ptr, int *row0, int *rows);
 /* prev <- next (main.cu:270-272). */
 int ofx_session_swap(ofx_session *s);
 /* Device pointers / geometry of the session's buffers. which: 0 = prev, 1 = next, 2 = shifted scratch. */
@@ -526,7 +544,8 @@ int ofx_session_timing_read(ofx_session *s, double *avg_us, double *min_us, int 
 #define OFX_TIME_CORNER 5  /* corner kernel */
 #define OFX_TIME_PYRAMID 6 /* fused pyramid launch */
 #define OFX_TIME_LK_ACC_WARP 7 /* the same launch when it also writes the next iteration's warped image (lk_body_warp.h) */
-#define OFX_TIME_KINDS 8
+#define OFX_TIME_COMPOSE 8 /* the stream pipeline's output stage (ofx_session_stream_compose): one per call that completes pairs */
+#define OFX_TIME_KINDS 9
 int ofx_session_timing_read_kind(ofx_session *s, int kind, double *avg_us, double *min_us, int *launches);
 
 /* ---- host-pointer convenience used by the gpu:: compat surface ------------ */
