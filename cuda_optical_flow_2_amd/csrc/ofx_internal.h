@@ -95,3 +95,12 @@ struct ofx_compose_batch {
     unsigned n_px; // w * rows
 };
 int ofx_compose_batch_launch(const ofx_compose_batch *a, void *stream);
+
+// the stream pipeline's colour front end (frontend.hip): the filter's tables for one (window, sigma_s, sigma_b), built once on the
+// host (window 0: grey frames only; an unsupported window is OFX_E_UNSUPPORTED), and one launch over n <= OFX_STREAM_MAX_BATCH
+// frames (modes[i]: OFX_FRONTEND_GREY / _BILATERAL / _BILATERAL_FAST; a call that mixes the two bilateral forms launches twice)
+struct ofx_frontend_tables;
+int ofx_frontend_tables_make(int window, double sigma_s, double sigma_b, ofx_frontend_tables **out);
+void ofx_frontend_tables_free(ofx_frontend_tables *t);
+int ofx_frontend_run(const ofx_frontend_tables *t, const uint8_t *const *src3, const int *src_pitch, uint8_t *const *dst, const int *dst_pitch,
+                     const int *modes, int n, int w, int h, hipStream_t st);

@@ -100,6 +100,15 @@ struct ofx_session {
     size_t ring_stride = 0; // bytes from slot to slot
     int ring_slots = 0, ring_level = 0;
     long composed = 0;
+    // ofx_session_stream_frontend: colour frames through the front end (frontend.hip).  fe_mode: what a frame gets
+    // (OFX_FRONTEND_GREY / _BILATERAL / _BILATERAL_FAST), 0 = off; frame 0 of a stream gets OFX_FRONTEND_GREY with
+    // OFX_FRONTEND_FLAG_FIRST_GREY.  borrow_frames: the filtered plane of image set i (fplane[i], at pitch[0]) stands in for the
+    // borrowed frame; otherwise the front end writes img[i][0] and the pyramid stage does not copy level 0.
+    int fe_mode = 0, fe_flags = 0;
+    ofx_frontend_tables *fe = nullptr;
+    void *fe_arena = nullptr;
+    uint8_t *fplane[kSets]{};
+    int stream_input = 0; // what the stream in progress has received: 0 = nothing yet, 1 = grey frames, 2 = colour frames
 };
 
 // Runs `launch` bracketed by a pair of timing events of kind `kind` when the session is armed (ofx_session_timing).
@@ -393,6 +402,8 @@ extern "C" int ofx_session_destroy(ofx_session *s)
         if (ev) (void)hipEventDestroy(ev);
     if (s->aux) (void)hipStreamDestroy(s->aux);
     if (s->arena) e = hipFree(s->arena);
+    if (s->fe_arena && e == hipSuccess) e = hipFree(s->fe_arena);
+    ofx_frontend_tables_free(s->fe);
     delete s;
     if (e != hipSuccess) {
         ofx_set_error("ofx_session_destroy: hipFree: %s", hipGetErrorString(e));
@@ -934,6 +945,8 @@ extern "C" int ofx_session_pair_status(ofx_session *s, int pair, int *h_status, 
 // after the corner stage wrote it and rewritten two ticks after.  The flows of pair p go to flow set p mod B.  After a
 // tick every pair <= f0-B-1 is done.
 static int stream_batch_of(const ofx_session *s) { return s->p.stream_batch >= 2 ? s->p.stream_batch : 1; }
+// image sets the stream pipeline cycles through: (D + 1) B + 2 (stream_tick)
+static int stream_sets(const ofx_session *s) { return (s->p.stream_two_stage ? 2 : 3) * stream_batch_of(s) + 2; }
 
 // One launch composing pairs first .. last (the pairs a call of the pipeline completes) into their ring slots.
 static int compose_ring(ofx_session *s, long first, long last, void *stream)
@@ -1025,6 +1038,8 @@ static int stream_tick(ofx_session *s, const uint8_t *const *frames, const int *
             s->bpitch[set] = pitches[i];
             P.d_levels[0] = nullptr;
             P.d_patch_levels[0] = nullptr;
+        } else if (s->stream_input == 2) { // the front end wrote level 0 of the set itself (frontend_tick): nothing to copy
+            P.d_levels[0] = nullptr;
         }
     }
     for (long pc = f0 - (D - 1) * B; pc <= f0 - (D - 1) * B + B - 1; ++pc) { // corner(pair pc)
@@ -1222,6 +1237,7 @@ extern "C" int ofx_session_stream_begin(ofx_session *s)
     s->reported = 0;
     s->corner_newest = 0;
     s->composed = 0;
+    s->stream_input = 0;
     s->have_prev = s->have_next = s->staged = false;
     s->corner_done = false;
     s->pset_img[0] = s->pset_img[1] = -1;
@@ -1229,21 +1245,59 @@ extern "C" int ofx_session_stream_begin(ofx_session *s)
     return OFX_OK;
 }
 
-// Submit the next frame of the stream.  *completed_pair (may be NULL) receives the highest pair (frame p-1 -> frame p,
-// frames counted from 0) whose flow is complete after this call in `stream` order, or -1 when the call completed none.
-extern "C" int ofx_session_stream_submit(ofx_session *s, const uint8_t *d_gray1, int pitch, void *stream, int *completed_pair)
+// A tick of colour frames: ONE front-end launch writes the filtered planes of the tick's frames (the sets they are assigned to,
+// frame f -> set f mod stream_sets), then the tick runs on those planes as its frames.
+static int frontend_tick(ofx_session *s, const uint8_t *const *img3, const int *pitch3, int n, void *stream, int *completed_pair)
 {
-    OFX_REQUIRE(s && d_gray1, "ofx_session_stream_submit: null argument");
+    const uint8_t *fr[kMaxBatch];
+    int pt[kMaxBatch];
+    if (n > 0) {
+        uint8_t *dst[kMaxBatch];
+        int dp[kMaxBatch], md[kMaxBatch];
+        const int sets = stream_sets(s);
+        for (int i = 0; i < n; ++i) {
+            const long f = s->stream_n + i;
+            dst[i] = s->p.borrow_frames ? s->fplane[f % sets] : s->img[f % sets][0];
+            dp[i] = s->pitch[0];
+            md[i] = f == 0 && (s->fe_flags & OFX_FRONTEND_FLAG_FIRST_GREY) ? OFX_FRONTEND_GREY : s->fe_mode;
+            fr[i] = dst[i];
+            pt[i] = s->pitch[0];
+        }
+        OfxRange range("ofx.frontend");
+        OFX_TRY(ofx_frontend_run(s->fe, img3, pitch3, dst, dp, md, n, s->w[0], s->h[0], ofx_stream(stream)));
+    }
+    return stream_tick(s, fr, pt, n, stream, completed_pair);
+}
+
+// Submit the next frame of the stream (input 1: a grey frame, 2: a colour frame for the front end).  *completed_pair (may be
+// NULL) receives the highest pair (frame p-1 -> frame p, frames counted from 0) whose flow is complete after this call in `stream`
+// order, or -1 when the call completed none.
+static int stream_submit(ofx_session *s, const uint8_t *frame, int pitch, void *stream, int *completed_pair, int input, const char *who)
+{
+    OFX_REQUIRE(s && frame, "%s: null argument", who);
     if (s->stream_n < 0) {
-        ofx_set_error("ofx_session_stream_submit: call ofx_session_stream_begin first");
+        ofx_set_error("%s: call ofx_session_stream_begin first", who);
         return OFX_E_STATE;
     }
-    OFX_REQUIRE(s->stream_frames < 0, "ofx_session_stream_submit: the stream is being drained");
+    OFX_REQUIRE(s->stream_frames < 0, "%s: the stream is being drained", who);
+    if (input == 2 && !s->fe_mode) {
+        ofx_set_error("%s: colour frames need the front end (ofx_session_stream_frontend)", who);
+        return OFX_E_STATE;
+    }
+    if (s->stream_input != 0 && s->stream_input != input) {
+        ofx_set_error("%s: this stream has received %s frames; a stream takes grey frames or colour frames, not both", who,
+                      s->stream_input == 1 ? "grey" : "colour");
+        return OFX_E_STATE;
+    }
+    if (input == 2)
+        OFX_REQUIRE(pitch >= 3 * s->w[0] && ((uintptr_t)frame & 3) == 0,
+                    "%s: a colour frame must be 4-byte aligned with a pitch of at least 3 * %d bytes (got %d)", who, s->w[0], pitch);
+    s->stream_input = input;
     int dummy = -1;
     if (!completed_pair) completed_pair = &dummy;
     const int B = stream_batch_of(s);
     if (s->n_held + 1 < B) { // the tick is not full yet: remember the frame
-        s->held_frame[s->n_held] = d_gray1;
+        s->held_frame[s->n_held] = frame;
         s->held_pitch[s->n_held] = pitch;
         ++s->n_held;
         *completed_pair = -1;
@@ -1252,11 +1306,81 @@ extern "C" int ofx_session_stream_submit(ofx_session *s, const uint8_t *d_gray1,
     const uint8_t *fr[kMaxBatch];
     int pt[kMaxBatch];
     for (int i = 0; i < s->n_held; ++i) fr[i] = s->held_frame[i], pt[i] = s->held_pitch[i];
-    fr[s->n_held] = d_gray1;
+    fr[s->n_held] = frame;
     pt[s->n_held] = pitch;
     const int n = s->n_held + 1;
     s->n_held = 0;
-    return stream_tick(s, fr, pt, n, stream, completed_pair);
+    return input == 2 ? frontend_tick(s, fr, pt, n, stream, completed_pair) : stream_tick(s, fr, pt, n, stream, completed_pair);
+}
+
+extern "C" int ofx_session_stream_submit(ofx_session *s, const uint8_t *d_gray1, int pitch, void *stream, int *completed_pair)
+{
+    return stream_submit(s, d_gray1, pitch, stream, completed_pair, 1, "ofx_session_stream_submit");
+}
+
+extern "C" int ofx_session_stream_submit_3ch(ofx_session *s, const uint8_t *d_img3, int pitch, void *stream, int *completed_pair)
+{
+    return stream_submit(s, d_img3, pitch, stream, completed_pair, 2, "ofx_session_stream_submit_3ch");
+}
+
+extern "C" int ofx_session_stream_submit_frames_3ch(ofx_session *s, const uint8_t *const *d_img3, const int *pitches, int pitch0, int n,
+                                                    void *stream, int *completed_pair)
+{
+    OFX_REQUIRE(s && d_img3 && n >= 1, "ofx_session_stream_submit_frames_3ch: bad arguments");
+    int newest = -1;
+    for (int i = 0; i < n; ++i) {
+        int done = -1;
+        OFX_TRY(ofx_session_stream_submit_3ch(s, d_img3[i], pitches ? pitches[i] : pitch0, stream, &done));
+        newest = done > newest ? done : newest;
+    }
+    if (completed_pair) *completed_pair = newest;
+    return OFX_OK;
+}
+
+extern "C" int ofx_session_stream_frontend(ofx_session *s, int mode, int window, double sigma_s, double sigma_b, int flags)
+{
+    OFX_REQUIRE(s, "ofx_session_stream_frontend: null session");
+    if (s->p.sharded) {
+        ofx_set_error("ofx_session_stream_frontend: not on a sharded session (each rank would filter the whole frame)");
+        return OFX_E_UNSUPPORTED;
+    }
+    if (s->stream_n > 0 || s->n_held > 0) {
+        ofx_set_error("ofx_session_stream_frontend: the stream has frames already; set the front end before the first frame of a stream");
+        return OFX_E_STATE;
+    }
+    OFX_REQUIRE(mode == OFX_FRONTEND_OFF || mode == OFX_FRONTEND_GREY || mode == OFX_FRONTEND_BILATERAL,
+                "ofx_session_stream_frontend: mode %d (OFX_FRONTEND_OFF / _GREY / _BILATERAL)", mode);
+    OFX_REQUIRE((flags & ~(OFX_FRONTEND_FLAG_FAST | OFX_FRONTEND_FLAG_FIRST_GREY)) == 0, "ofx_session_stream_frontend: unknown flags %#x", flags);
+    OFX_HIP(hipSetDevice(s->p.device));
+    if (mode == OFX_FRONTEND_OFF) {
+        ofx_frontend_tables_free(s->fe);
+        s->fe = nullptr;
+        s->fe_mode = s->fe_flags = 0;
+        for (uint8_t *&pl : s->fplane) pl = nullptr;
+        void *a = s->fe_arena;
+        s->fe_arena = nullptr;
+        if (a) OFX_HIP(hipFree(a));
+        return OFX_OK;
+    }
+    ofx_frontend_tables *t = nullptr;
+    OFX_TRY(ofx_frontend_tables_make(mode == OFX_FRONTEND_BILATERAL ? window : 0, sigma_s, sigma_b, &t));
+    if (s->p.borrow_frames && !s->fe_arena) {
+        // one plane per image set at the level-0 pitch, plus the three readable bytes the fused warp may fetch past level 0
+        const size_t plane = align_up((size_t)s->pitch[0] * (size_t)s->h[0] + 64, 256);
+        const hipError_t e = hipMalloc(&s->fe_arena, plane * (size_t)s->n_sets);
+        if (e != hipSuccess) {
+            ofx_frontend_tables_free(t);
+            s->fe_arena = nullptr;
+            ofx_set_error("ofx_session_stream_frontend: hipMalloc(%zu bytes): %s", plane * (size_t)s->n_sets, hipGetErrorString(e));
+            return OFX_E_HIP;
+        }
+        for (int i = 0; i < s->n_sets; ++i) s->fplane[i] = static_cast<uint8_t *>(s->fe_arena) + plane * (size_t)i;
+    }
+    ofx_frontend_tables_free(s->fe);
+    s->fe = t;
+    s->fe_mode = mode == OFX_FRONTEND_GREY ? OFX_FRONTEND_GREY : (flags & OFX_FRONTEND_FLAG_FAST) ? OFX_FRONTEND_BILATERAL_FAST : OFX_FRONTEND_BILATERAL;
+    s->fe_flags = flags;
+    return OFX_OK;
 }
 
 extern "C" int ofx_session_stream_submit_frames(ofx_session *s, const uint8_t *const *d_gray1, const int *pitches, int pitch0, int n,
@@ -1294,7 +1418,7 @@ extern "C" int ofx_session_stream_drain(ofx_session *s, void *stream, int *compl
         s->stream_frames = -1;
         return OFX_OK;
     }
-    return stream_tick(s, fr, pt, n, stream, completed_pair);
+    return s->stream_input == 2 ? frontend_tick(s, fr, pt, n, stream, completed_pair) : stream_tick(s, fr, pt, n, stream, completed_pair);
 }
 
 extern "C" int ofx_session_flow_of(ofx_session *s, int pair, int level, float **d_ptr, int *row0, int *rows)

@@ -226,6 +226,41 @@ class Session:
               "stream_submit_frames")
         return done.value
 
+    FRONTEND_MODES = {"off": 0, "grey": 1, "bilateral": 2}   # OFX_FRONTEND_OFF / _GREY / _BILATERAL
+
+    def stream_frontend(self, mode="bilateral", window: int = 9, sigma_s: float = 2.0, sigma_b: float = 10.0, fast: bool = False,
+                        first_grey: bool = False):
+        """The stream pipeline's colour front end (ofx_session_stream_frontend): every tick's colour frames (stream_submit_3ch)
+        are averaged to grey and, with mode "bilateral", filtered (square odd window 3 .. 13, main.cu:240: 9, 2.0, 10.0) by one
+        launch that writes the planes the tick reads.  fast: the +-1 LSB filter.  first_grey: frame 0 of every stream is averaged
+        only (main.cu:198-209).  mode "off" or None turns it off.  Only before the first frame of a stream."""
+        m = self.FRONTEND_MODES["off" if mode is None else mode]
+        flags = (1 if fast else 0) | (2 if first_grey else 0)   # OFX_FRONTEND_FLAG_FAST / _FIRST_GREY
+        check(self.L.ofx_session_stream_frontend(self._h, m, int(window), float(sigma_s), float(sigma_b), flags), "stream_frontend")
+
+    def _check_3ch(self, t):
+        assert t.is_cuda and t.dtype.itemsize == 1 and tuple(t.shape) == (self.height, self.width, 3), "colour frame: uint8 CUDA [H, W, 3]"
+        assert t.stride(2) == 1 and t.stride(1) == 3, "colour frame: interleaved channels (stride(2) == 1, stride(1) == 3)"
+
+    def stream_submit_3ch(self, t, stream=None) -> int:
+        """stream_submit for a colour frame [H, W, 3] (ofx_session_stream_submit_3ch): the front end must be set.  The tensor is
+        read by the front-end launch of the call that launches its tick and must stay unmodified until that launch has run."""
+        self._check_3ch(t)
+        done = C.c_int(-1)
+        check(self.L.ofx_session_stream_submit_3ch(self._h, t.data_ptr(), int(t.stride(0)), _stream_ptr(stream), C.byref(done)),
+              "stream_submit_3ch")
+        return done.value
+
+    def stream_submit_frames_3ch(self, frames, stream=None) -> int:
+        """stream_submit_frames for colour frames (ofx_session_stream_submit_frames_3ch); a FrameGroup of them may be reused."""
+        g = frames if isinstance(frames, FrameGroup) else FrameGroup(frames)
+        for t in g.tensors:
+            self._check_3ch(t)
+        done = C.c_int(-1)
+        check(self.L.ofx_session_stream_submit_frames_3ch(self._h, g.ptrs, None, g.pitch, g.n, _stream_ptr(stream), C.byref(done)),
+              "stream_submit_frames_3ch")
+        return done.value
+
     def stream_drain(self, stream=None) -> int:
         done = C.c_int(-1)
         check(self.L.ofx_session_stream_drain(self._h, _stream_ptr(stream), C.byref(done)), "stream_drain")
@@ -470,7 +505,7 @@ def flow_pair(prev1: np.ndarray, next1: np.ndarray, levels: int, window: int, mo
 
 
 def video_flow(frames, levels: int, window: int, mode: str = "lk_float", level: int = 0, iters: int = 1, min_det: float = 0.0,
-               batch: Optional[int] = None, out=None):
+               batch: Optional[int] = None, out=None, frontend: Optional[str] = None, bilateral=(9, 2.0, 10.0), fast: bool = False):
     """Dense flow of every consecutive pair of a clip, in one call: the field of main.cu:138-147 -- sum over k >= level of
     2^(k-level) * flow_k(y >> (k-level), x >> (k-level)), the reference's only definition of the final result -- composed
     at `level` by the stream pipeline's output stage, bit for bit the reference's (ofx_compose_flow of the pair's flow pyramid).
@@ -480,10 +515,17 @@ def video_flow(frames, levels: int, window: int, mode: str = "lk_float", level: 
     pipeline writes (no copies); `out` may supply it (same shape, tightly packed rows, 16-byte aligned slots).  Frames are
     read in place when their pitch and alignment allow it (with iters > 1: a pitch of the width rounded up to 64), otherwise
     through copies.  stream_batch: `batch`, or suggest_stream_batch, at most N-1.  Work is enqueued on the current torch stream;
-    the call returns once the pipeline has drained, and raises when a pair is not the reference's result (strict)."""
+    the call returns once the pipeline has drained, and raises when a pair is not the reference's result (strict).
+
+    A colour clip, uint8 [N, H, W, 3] with interleaved channels, goes through the pipeline's front end (Session.stream_frontend):
+    frontend="main_cu" (the default for colour) is main.cu:198-240 exactly -- frame 0 averaged to grey only, every later frame
+    averaged and then bilateral-filtered with `bilateral` = (window, sigma_s, sigma_b), 9x9 (2, 10) as there; "bilateral" filters
+    every frame, "grey" filters none.  fast: the +-1 LSB filter.  A grey clip ignores these three."""
     import torch
 
-    assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 3, "frames: uint8 CUDA tensor [N, H, W]"
+    assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() in (3, 4), "frames: uint8 CUDA tensor [N, H, W] or [N, H, W, 3]"
+    if frames.dim() == 4:
+        return _video_flow_3ch(frames, levels, window, mode, level, iters, min_det, batch, out, frontend or "main_cu", bilateral, fast)
     N, H, W = (int(v) for v in frames.shape)
     assert N >= 2 and frames.stride(2) == 1, "frames: at least two, with unit column stride"
     assert 0 <= level < levels
@@ -515,6 +557,52 @@ def video_flow(frames, levels: int, window: int, mode: str = "lk_float", level: 
         s.stream_begin()
         for i in range(N):
             s.stream_submit(frames[i])
+        while s.stream_drain() != -2:
+            pass
+    finally:
+        s.close()
+    return out
+
+
+def _ring_for(N, H, W, level, device, out):
+    import torch
+
+    hl, wl = H >> level, W >> level
+    stride = (hl * wl * 2 + 3) // 4 * 4   # floats from slot to slot: a multiple of 16 bytes
+    if out is None:
+        flat = torch.empty((N - 1) * stride, dtype=torch.float32, device=device)
+        return flat.as_strided((N - 1, hl, wl, 2), (stride, 2 * wl, 2, 1))
+    assert out.dtype == torch.float32 and tuple(out.shape) == (N - 1, hl, wl, 2), f"out must be float32 [{N - 1}, {hl}, {wl}, 2]"
+    return out
+
+
+def _video_flow_3ch(frames, levels, window, mode, level, iters, min_det, batch, out, frontend, bilateral, fast):
+    """video_flow of a colour clip [N, H, W, 3]: the front end writes the session's own planes, so the pipeline always runs in its
+    fast configuration (borrowed planes, two stages) whatever the clip's layout; only the colour frames' own alignment matters."""
+    import torch
+
+    assert frontend in ("main_cu", "bilateral", "grey"), f"frontend: 'main_cu', 'bilateral' or 'grey', not {frontend!r}"
+    N, H, W, ch = (int(v) for v in frames.shape)
+    assert ch == 3 and N >= 2, "frames: [N, H, W, 3], at least two"
+    assert 0 <= level < levels
+    ptr, fstride, pitch = frames.data_ptr(), int(frames.stride(0)), int(frames.stride(1))
+    if not (frames.stride(3) == 1 and frames.stride(2) == 3 and ptr % 4 == 0 and fstride % 4 == 0 and pitch >= 3 * W):
+        # (every frame's base 4-byte aligned: rows padded to a multiple of four bytes)
+        padded = torch.empty((N, H, 3 * W + (-3 * W) % 4), dtype=torch.uint8, device=frames.device)
+        padded[:, :, :3 * W] = frames.reshape(N, H, 3 * W)
+        frames = padded[:, :, :3 * W].unflatten(2, (W, 3))
+    out = _ring_for(N, H, W, level, frames.device, out)
+    B = batch if batch is not None else suggest_stream_batch(W, H, levels, borrow_frames=True, two_stage=True)
+    B = max(1, min(int(B), N - 1))
+    s = Session(W, H, levels, window, mode, iters=iters, min_det=min_det, stream_batch=B, borrow_frames=True, two_stage=True, strict=True)
+    try:
+        win, ss, sb = bilateral
+        s.stream_frontend("grey" if frontend == "grey" else "bilateral", int(win), float(ss), float(sb), fast=fast,
+                          first_grey=frontend == "main_cu")
+        s.stream_compose(out, level)
+        s.stream_begin()
+        for i in range(N):
+            s.stream_submit_3ch(frames[i])
         while s.stream_drain() != -2:
             pass
     finally:

@@ -76,6 +76,7 @@ _SIGS = {
     "ofx_bilateral_3ch": [_vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _vp],
     "ofx_bilateral_3ch_fast": [_vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _vp],
     "ofx_bilateral_wrappers_fast": [_i],
+    "ofx_frontend_1ch": [C.POINTER(_vp), C.POINTER(_i), _i, C.POINTER(_vp), C.POINTER(_i), _i, _i, _i, _i, C.POINTER(_i), _i, _i, _d, _d, _vp],
     "ofx_sub_u8": [_vp, _vp, C.c_size_t, _vp, _vp],
     "ofx_srm_3ch_u8": [_vp, _vp, _i, _i, _i, _i, _vp, _vp],
     "ofx_downscale_mask_3ch": [_vp, _vp, _i, _i, _vp, _i, _i, _vp],
@@ -102,6 +103,9 @@ _SIGS = {
     "ofx_session_flow_of": [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i)],
     "ofx_session_stream_compose": [_vp, _i, _vp, C.c_size_t, _i],
     "ofx_session_composed_of": [_vp, _i, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i)],
+    "ofx_session_stream_frontend": [_vp, _i, _i, _d, _d, _i],
+    "ofx_session_stream_submit_3ch": [_vp, _vp, _i, _vp, C.POINTER(_i)],
+    "ofx_session_stream_submit_frames_3ch": [_vp, C.POINTER(_vp), C.POINTER(_i), _i, _i, _vp, C.POINTER(_i)],
     "ofx_session_stream_submit": [_vp, _vp, _i, _vp, C.POINTER(_i)],
     "ofx_session_stream_drain": [_vp, _vp, C.POINTER(_i)],
     "ofx_session_stream_submit_frames": [_vp, C.POINTER(_vp), C.POINTER(_i), _i, _i, _vp, C.POINTER(_i)],

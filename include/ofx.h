@@ -335,6 +335,26 @@ int ofx_bilateral_3ch_fast(const uint8_t *d_src3, const uint8_t *d_gray3, uint8_
  * makes them run ofx_bilateral_3ch_fast (on != 0) or the bit-exact kernel (on == 0, the default; environment
  * OFX_BILATERAL_FAST=1 starts with it on).  on < 0 only queries.  Returns the previous setting. */
 int ofx_bilateral_wrappers_fast(int on);
+/* The stream pipeline's colour front end as a batched call: main.cu:222-240 -- grayscale_avg, then the bilateral pre-filter with
+ * the grey image as its own source (square odd window 3 .. 13: ofx_bilateral_3ch(g, g, ...) of the grey image) -- for n <=
+ * OFX_STREAM_MAX_BATCH colour frames in ONE launch, each written as a one-channel plane.  Frame i: d_src3[i] interleaved 3-channel
+ * u8 (channel order does not matter), 4-byte aligned, row pitch src_pitches[i] >= 3 * w bytes (tightly packed odd widths
+ * included); d_dst[i] one-channel u8, row pitch dst_pitches[i] >= w, of which columns [0, w) of every row are written (either
+ * pitch array may be NULL when every frame's pitch is src_pitch0 / dst_pitch0).  Per frame (modes[i], or mode0 for all when
+ * modes is NULL):
+ *   OFX_FRONTEND_GREY            (c0 + c1 + c2) / 3 in integers (ofx_grayscale_avg_3ch's value)
+ *   OFX_FRONTEND_BILATERAL       then the bit-exact filter (= ofx_bilateral_3ch of that grey image as its own source, channel 0)
+ *   OFX_FRONTEND_BILATERAL_FAST  then the +-1 LSB filter (ofx_bilateral_3ch_fast's float arithmetic; the exact one where that
+ *                                does not apply: sigma_b > 2e4)
+ * window / sigma_s / sigma_b are ignored when every frame is GREY; an unsupported window is OFX_E_UNSUPPORTED.  A call that mixes
+ * BILATERAL and BILATERAL_FAST frames launches twice.  The tables are built on the host when (window, sigma_s, sigma_b) changes. */
+#define OFX_FRONTEND_OFF 0
+#define OFX_FRONTEND_GREY 1
+#define OFX_FRONTEND_BILATERAL 2
+#define OFX_FRONTEND_BILATERAL_FAST 3
+int ofx_frontend_1ch(const uint8_t *const *d_src3, const int *src_pitches, int src_pitch0, uint8_t *const *d_dst, const int *dst_pitches,
+                     int dst_pitch0, int n, int w, int h, const int *modes, int mode0, int window, double sigma_s, double sigma_b,
+                     void *stream);
 
 /* the remaining functions of namespace cpu (OptFlowCpu.hpp:3-184), device-resident, so that the cpu:: call surface of
  * include/OptFlowCpu.hpp runs on the MI355X as well */
@@ -518,6 +538,30 @@ int ofx_session_stream_compose(ofx_session *s, int level, float *d_ring, size_t 
 /* Slot of `pair` while it is one of the newest n_slots pairs composed into the ring; row0 / rows as ofx_session_flow_of.
  * OFX_E_STATE without a ring, OFX_E_INVALID for a pair not (or no longer) in it. */
 int ofx_session_composed_of(ofx_session *s, int pair, float **d_ptr, int *row0, int *rows);
+/* Colour frames into the stream pipeline (main.cu:222-272 as one device-resident pipeline): with the front end set, every call
+ * that launches a tick first enqueues ONE launch of the front end (ofx_frontend_1ch) for that tick's colour frames on its `stream`,
+ * writing the filtered one-channel planes the tick then reads as its frames:
+ *   mode: OFX_FRONTEND_OFF (the default: nothing allocated or launched), OFX_FRONTEND_GREY (average only) or
+ *         OFX_FRONTEND_BILATERAL (average, then the bilateral filter with window / sigma_s / sigma_b; square odd windows 3 .. 13,
+ *         others OFX_E_UNSUPPORTED; main.cu:240 uses 9, 2.0, 10.0);
+ *   flags: OFX_FRONTEND_FLAG_FAST = the +-1 LSB arithmetic of the filter; OFX_FRONTEND_FLAG_FIRST_GREY = frame 0 of every stream is
+ *         averaged only (main.cu:198-209: the first frame primes the previous pyramid unfiltered).
+ * The planes: with borrow_frames = 0 the front end writes level 0 of the frame's image set and the pyramid stage does not copy
+ * it; with borrow_frames = 1 the session owns one plane per image set at its level-0 pitch (allocated here, only then), and
+ * those planes are what the later stages borrow.  Refinement iterations, the corner repair and the compose ring work unchanged.
+ * Only before the first frame of a stream (OFX_E_STATE once a stream has frames); stays in effect for later streams.  Sharded
+ * sessions: OFX_E_UNSUPPORTED. */
+#define OFX_FRONTEND_FLAG_FAST 1
+#define OFX_FRONTEND_FLAG_FIRST_GREY 2
+int ofx_session_stream_frontend(ofx_session *s, int mode, int window, double sigma_s, double sigma_b, int flags);
+/* ofx_session_stream_submit / _submit_frames for colour frames: interleaved 3-channel u8, 4-byte aligned, row pitch >= 3 * width
+ * (OFX_E_INVALID otherwise).  The same contracts as the grey calls, completed pairs included.  A stream takes grey frames or colour
+ * frames, not both (OFX_E_STATE), and colour frames need the front end set (OFX_E_STATE).  LIFETIME: a colour frame is read by
+ * the front-end launch of the call that launches its tick, and by nothing after it -- it must stay valid and unmodified until
+ * that launch has finished (the rule of a non-borrowed grey frame), whatever borrow_frames says. */
+int ofx_session_stream_submit_3ch(ofx_session *s, const uint8_t *d_img3, int pitch, void *stream, int *completed_pair);
+int ofx_session_stream_submit_frames_3ch(ofx_session *s, const uint8_t *const *d_img3, const int *pitches, int pitch0, int n, void *stream,
+                                         int *completed_pair);
 /* prev <- next (main.cu:270-272). */
 int ofx_session_swap(ofx_session *s);
 /* Device pointers / geometry of the session's buffers. which: 0 = prev, 1 = next, 2 = shifted scratch. */
