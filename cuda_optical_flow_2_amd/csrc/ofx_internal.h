@@ -96,6 +96,31 @@ struct ofx_compose_batch {
 };
 int ofx_compose_batch_launch(const ofx_compose_batch *a, void *stream);
 
+// the stream pipeline's sampled output stage (sample_ring.hip): the composed field (compose_px.h) of n <= OFX_STREAM_MAX_BATCH pairs
+// read at a few positions instead of composed everywhere, in ONE launch.  Pair i reads lv[i][k] as in ofx_compose_batch.
+//   arrows (arrows[0] != NULL): the arrow field of main.cu:123-169 of pair i at a_level (a_w x a_h, grid step a_offset = a_w / arrow_res,
+//     a_ny x a_nx arrows), a_ny * a_nx records of four int32 (x0, y0, x1, y1; an undrawn arrow has x1 = y1 = -1) at arrows[i] (16-byte aligned);
+//   tracks (points != NULL): n_points float2 (x, y) in pixels of t_level (t_w x t_h) and their int32 status (0 = alive), advected
+//     through the n pairs in order; a point that leaves the level or meets a non-finite flow at pair i is frozen with status
+//     pair0 + i.  hist[i] (NULL: none; 8-byte aligned) receives every point's position after pair i.
+struct ofx_sample_batch {
+    const float *lv[OFX_STREAM_MAX_BATCH][OFX_MAX_LEVELS];
+    int32_t *arrows[OFX_STREAM_MAX_BATCH];
+    float *hist[OFX_STREAM_MAX_BATCH];
+    float *points;
+    int32_t *status;
+    int own0[OFX_MAX_LEVELS];
+    int n, levels;
+    int a_level, a_w, a_h, a_offset, a_ny, a_nx;
+    int t_level, t_w, t_h, n_points, pair0;
+};
+int ofx_sample_batch_launch(const ofx_sample_batch *a, void *stream);
+// offset / ny / nx of the arrow grid of a w x h level (main.cu:125-131); OFX_E_INVALID when w / arrow_res would be 0
+int ofx_arrow_grid(int w, int h, int arrow_res, int *offset, int *ny, int *nx, const char *who);
+// every level of a w x h pyramid that a coarser one is read under must have even dimensions (the session's rule): then pixel
+// (y >> s, x >> s) of level k exists for every pixel of level `level`
+int ofx_check_sample_pyramid(int w, int h, int levels, int level, const char *who);
+
 // the stream pipeline's colour front end (frontend.hip): the filter's tables for one (window, sigma_s, sigma_b), built once on the
 // host (window 0: grey frames only; an unsupported window is OFX_E_UNSUPPORTED), and one launch over n <= OFX_STREAM_MAX_BATCH
 // frames (modes[i]: OFX_FRONTEND_GREY / _BILATERAL / _BILATERAL_FAST; a call that mixes the two bilateral forms launches twice)

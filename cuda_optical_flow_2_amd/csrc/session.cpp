@@ -100,6 +100,16 @@ struct ofx_session {
     size_t ring_stride = 0; // bytes from slot to slot
     int ring_slots = 0, ring_level = 0;
     long composed = 0;
+    // ofx_session_stream_arrows / _stream_tracks (sample_ring.hip): the caller's arrow ring, points, statuses and history ring
+    // (nullptr: off), and the newest pair sampled
+    int32_t *arrow_ring = nullptr;
+    size_t arrow_stride = 0;
+    int arrow_slots = 0, arrow_level = 0, arrow_offset = 0, arrow_ny = 0, arrow_nx = 0;
+    float *trk_points = nullptr, *trk_hist = nullptr;
+    int32_t *trk_status = nullptr;
+    size_t trk_stride = 0;
+    int trk_n = 0, trk_slots = 0, trk_level = 0;
+    long sampled = 0;
     // ofx_session_stream_frontend: colour frames through the front end (frontend.hip).  fe_mode: what a frame gets
     // (OFX_FRONTEND_GREY / _BILATERAL / _BILATERAL_FAST), 0 = off; frame 0 of a stream gets OFX_FRONTEND_GREY with
     // OFX_FRONTEND_FLAG_FIRST_GREY.  borrow_frames: the filtered plane of image set i (fplane[i], at pitch[0]) stands in for the
@@ -968,6 +978,35 @@ static int compose_ring(ofx_session *s, long first, long last, void *stream)
     return timed_launch(s, OFX_TIME_COMPOSE, stream, [&] { return ofx_compose_batch_launch(&cb, stream); });
 }
 
+// One launch sampling pairs first .. last: their arrow fields into the arrow ring, the tracked points through them in order.
+static int sample_ring(ofx_session *s, long first, long last, void *stream)
+{
+    const int B = stream_batch_of(s);
+    static thread_local ofx_sample_batch sb; // (2 KB)
+    memset(&sb, 0, sizeof sb);
+    sb.levels = s->p.levels;
+    for (int k = 0; k < s->p.levels; ++k) sb.own0[k] = s->own0[k];
+    if (s->arrow_ring) {
+        sb.a_level = s->arrow_level, sb.a_w = s->w[s->arrow_level], sb.a_h = s->h[s->arrow_level];
+        sb.a_offset = s->arrow_offset, sb.a_ny = s->arrow_ny, sb.a_nx = s->arrow_nx;
+    }
+    if (s->trk_points) {
+        sb.points = s->trk_points, sb.status = s->trk_status, sb.n_points = s->trk_n;
+        sb.t_level = s->trk_level, sb.t_w = s->w[s->trk_level], sb.t_h = s->h[s->trk_level];
+        sb.pair0 = (int)first;
+    }
+    for (long p = first; p <= last; ++p, ++sb.n) {
+        for (int k = 0; k < s->p.levels; ++k) sb.lv[sb.n][k] = s->flowset[p % B][k] + s->flow_own_offset(k);
+        if (s->arrow_ring)
+            sb.arrows[sb.n] = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(s->arrow_ring) + (size_t)((p - 1) % s->arrow_slots) * s->arrow_stride);
+        if (s->trk_points && s->trk_hist)
+            sb.hist[sb.n] = reinterpret_cast<float *>(reinterpret_cast<char *>(s->trk_hist) + (size_t)((p - 1) % s->trk_slots) * s->trk_stride);
+    }
+    s->sampled = last;
+    OfxRange range("ofx.sample_ring");
+    return ofx_sample_batch_launch(&sb, stream);
+}
+
 static int stream_tick(ofx_session *s, const uint8_t *const *frames, const int *pitches, int n_frames, void *stream, int *completed_pair)
 {
     const int B = stream_batch_of(s);
@@ -1216,6 +1255,8 @@ static int stream_tick(ofx_session *s, const uint8_t *const *frames, const int *
     // the output stage (ofx_session_stream_compose): behind the tick's last launch on the same stream, before the next tick
     // rewrites flow set p mod B
     if (s->ring && newest >= 1) OFX_TRY(compose_ring(s, oldest, newest, stream));
+    // the sampled output stage (ofx_session_stream_arrows / _stream_tracks): one launch, under the same rule
+    if ((s->arrow_ring || s->trk_points) && newest >= 1) OFX_TRY(sample_ring(s, oldest, newest, stream));
     s->stream_n = f0 + B;
     return OFX_OK;
 }
@@ -1237,6 +1278,7 @@ extern "C" int ofx_session_stream_begin(ofx_session *s)
     s->reported = 0;
     s->corner_newest = 0;
     s->composed = 0;
+    s->sampled = 0;
     s->stream_input = 0;
     s->have_prev = s->have_next = s->staged = false;
     s->corner_done = false;
@@ -1489,6 +1531,95 @@ extern "C" int ofx_session_composed_of(ofx_session *s, int pair, float **d_ptr, 
     if (d_ptr) *d_ptr = reinterpret_cast<float *>(reinterpret_cast<char *>(s->ring) + (size_t)((pair - 1) % s->ring_slots) * s->ring_stride);
     if (row0) *row0 = s->own0[lv];
     if (rows) *rows = s->own1[lv] - s->own0[lv];
+    return OFX_OK;
+}
+
+// what ofx_session_stream_arrows / _stream_tracks share: the session may take a new output setting, and the ring fits
+static int sampled_settable(ofx_session *s, const char *who)
+{
+    if (s->stream_n > 0 || s->n_held > 0) {
+        ofx_set_error("%s: the stream has frames already; set the output before the first frame of a stream", who);
+        return OFX_E_STATE;
+    }
+    if (s->p.sharded) {
+        ofx_set_error("%s: not on a sharded session (sampled positions cross shard boundaries)", who);
+        return OFX_E_UNSUPPORTED;
+    }
+    return OFX_OK;
+}
+
+static int sampled_ring_ok(const ofx_session *s, const void *ring, size_t stride, size_t slot_bytes, int n_slots, const char *who)
+{
+    const int B = stream_batch_of(s);
+    OFX_REQUIRE(n_slots >= B, "%s: %d slots, the ring needs at least stream_batch = %d (the pairs one call completes)", who, n_slots, B);
+    OFX_REQUIRE(((uintptr_t)ring & 15) == 0, "%s: the ring must be 16-byte aligned", who);
+    OFX_REQUIRE(stride % 16 == 0 && stride >= slot_bytes, "%s: slot stride %zu bytes must be a multiple of 16 and at least the slot's %zu bytes", who,
+                stride, slot_bytes);
+    return OFX_OK;
+}
+
+extern "C" int ofx_session_stream_arrows(ofx_session *s, int level, int arrow_res, int32_t *d_ring, size_t slot_stride_bytes, int n_slots)
+{
+    const char *who = "ofx_session_stream_arrows";
+    OFX_REQUIRE(s, "%s: null session", who);
+    OFX_TRY(sampled_settable(s, who));
+    if (!d_ring) {
+        s->arrow_ring = nullptr;
+        s->sampled = 0;
+        return OFX_OK;
+    }
+    OFX_REQUIRE(level >= 0 && level < s->p.levels, "%s: level %d out of range (0 .. %d)", who, level, s->p.levels - 1);
+    int offset, ny, nx;
+    OFX_TRY(ofx_arrow_grid(s->w[level], s->h[level], arrow_res, &offset, &ny, &nx, who));
+    OFX_TRY(ofx_check_sample_pyramid(s->w[level], s->h[level], s->p.levels, level, who));
+    OFX_TRY(sampled_ring_ok(s, d_ring, slot_stride_bytes, (size_t)ny * (size_t)nx * 16, n_slots, who));
+    s->arrow_ring = d_ring;
+    s->arrow_stride = slot_stride_bytes;
+    s->arrow_slots = n_slots;
+    s->arrow_level = level;
+    s->arrow_offset = offset, s->arrow_ny = ny, s->arrow_nx = nx;
+    s->sampled = 0;
+    return OFX_OK;
+}
+
+extern "C" int ofx_session_arrows_of(ofx_session *s, int pair, int32_t **d_ptr, int *ny, int *nx)
+{
+    OFX_REQUIRE(s, "ofx_session_arrows_of: null session");
+    if (!s->arrow_ring) {
+        ofx_set_error("ofx_session_arrows_of: no ring set (ofx_session_stream_arrows)");
+        return OFX_E_STATE;
+    }
+    OFX_REQUIRE(pair >= 1 && pair <= s->sampled && pair > s->sampled - s->arrow_slots,
+                "ofx_session_arrows_of: pair %d is not among the newest %d sampled pairs (newest: %ld)", pair, s->arrow_slots, s->sampled);
+    if (d_ptr) *d_ptr = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(s->arrow_ring) + (size_t)((pair - 1) % s->arrow_slots) * s->arrow_stride);
+    if (ny) *ny = s->arrow_ny;
+    if (nx) *nx = s->arrow_nx;
+    return OFX_OK;
+}
+
+extern "C" int ofx_session_stream_tracks(ofx_session *s, int level, float *d_points, int32_t *d_status, int n_points, float *d_history,
+                                         size_t slot_stride_bytes, int n_slots)
+{
+    const char *who = "ofx_session_stream_tracks";
+    OFX_REQUIRE(s, "%s: null session", who);
+    OFX_TRY(sampled_settable(s, who));
+    if (!d_points) {
+        s->trk_points = s->trk_hist = nullptr;
+        s->trk_status = nullptr;
+        return OFX_OK;
+    }
+    OFX_REQUIRE(level >= 0 && level < s->p.levels, "%s: level %d out of range (0 .. %d)", who, level, s->p.levels - 1);
+    OFX_REQUIRE(d_status && n_points >= 1, "%s: %d points need a status word each", who, n_points);
+    OFX_REQUIRE(((uintptr_t)d_points & 7) == 0 && ((uintptr_t)d_status & 3) == 0, "%s: points must be 8-byte, statuses 4-byte aligned", who);
+    OFX_TRY(ofx_check_sample_pyramid(s->w[level], s->h[level], s->p.levels, level, who));
+    if (d_history) OFX_TRY(sampled_ring_ok(s, d_history, slot_stride_bytes, (size_t)n_points * 8, n_slots, who));
+    s->trk_points = d_points;
+    s->trk_status = d_status;
+    s->trk_n = n_points;
+    s->trk_level = level;
+    s->trk_hist = d_history;
+    s->trk_stride = d_history ? slot_stride_bytes : 0;
+    s->trk_slots = d_history ? n_slots : 0;
     return OFX_OK;
 }
 

@@ -111,6 +111,7 @@ class Session:
         check(self.L.ofx_session_create(C.byref(p), C.byref(self._h)), "ofx_session_create")
         self._keep = []
         self._ring, self._ring_level = None, 0
+        self._arrows = self._tracks = None
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -354,6 +355,61 @@ class Session:
         w = self.width >> self._ring_level
         return DeviceView(ptr.value, (rows.value, w, 2), "<f4").tensor()
 
+    def stream_arrows(self, ring, level: int = 0, arrow_res: int = 30):
+        """The stream pipeline's sampled output stage, arrows (ofx_session_stream_arrows): the arrow field of main.cu:123-169 of
+        every pair it completes -- the composed field at `level` read at the grid points i, j = 0, offset, 2 offset, .. with
+        offset = (width >> level) // arrow_res, clamped to +-offset, added to the point and truncated -- into slot (p - 1) mod n_slots
+        of `ring`: int32 CUDA tensor [n_slots, ny, nx, 4] of (x0, y0, x1, y1) in the level's pixels, x1 = y1 = -1 for an arrow the
+        reference does not draw; (offset, ny, nx) = arrow_grid(width >> level, height >> level, arrow_res).  Slots tightly packed,
+        the slot stride free as long as it is a multiple of 16 bytes; n_slots >= stream_batch.  One launch per completing call,
+        shared with stream_tracks; no dense ring needed.  None turns it off.  Only before the first frame of a stream."""
+        if ring is None:
+            check(self.L.ofx_session_stream_arrows(self._h, 0, 1, None, 0, 0), "stream_arrows")
+            self._arrows = None
+            return
+        import torch
+
+        _, ny, nx = arrow_grid(self.width >> level, self.height >> level, arrow_res)
+        assert ring.is_cuda and ring.dtype == torch.int32 and ring.dim() == 4, "ring: int32 CUDA tensor [n_slots, ny, nx, 4]"
+        assert tuple(ring.shape[1:]) == (ny, nx, 4), f"ring slots must be [{ny}, {nx}, 4], got {tuple(ring.shape[1:])}"
+        assert ring.stride()[1:] == (4 * nx, 4, 1), "ring: the arrows of a slot must be tightly packed"
+        check(self.L.ofx_session_stream_arrows(self._h, level, arrow_res, ring.data_ptr(), 4 * int(ring.stride(0)), int(ring.shape[0])),
+              "stream_arrows")
+        self._arrows = ring
+
+    def arrows_of(self, pair: int):
+        """torch int32 view [ny, nx, 4] of `pair`'s slot in the arrow ring (ofx_session_arrows_of), while it is one of the newest
+        n_slots sampled pairs; valid once the launch of the call that reported the pair has run."""
+        ptr, ny, nx = _vp(), C.c_int(), C.c_int()
+        check(self.L.ofx_session_arrows_of(self._h, pair, C.byref(ptr), C.byref(ny), C.byref(nx)), "session_arrows_of")
+        return DeviceView(ptr.value, (ny.value, nx.value, 4), "<i4").tensor()
+
+    def stream_tracks(self, points, status, history=None, level: int = 0):
+        """The stream pipeline's sampled output stage, tracks (ofx_session_stream_tracks): `points` (float32 CUDA [n, 2] of (x, y)
+        in the pixels of `level`) are moved through every completed pair in order by the composed flow at the pixel they are in;
+        `status` (int32 CUDA [n], 0 = alive) receives the pair at which a point left the level or met a non-finite flow -- such a
+        point keeps its position from then on.  After the launch of the call that completes pair p, `points` holds the positions
+        in frame p.  history: float32 CUDA [n_slots, n, 2] (slot stride a multiple of 16 bytes, n_slots >= stream_batch), slot
+        (p - 1) mod n_slots receives the positions after pair p.  The caller initialises points and status; the result does not
+        depend on stream_batch.  points = None turns it off.  Only before the first frame of a stream."""
+        if points is None:
+            check(self.L.ofx_session_stream_tracks(self._h, 0, None, None, 0, None, 0, 0), "stream_tracks")
+            self._tracks = None
+            return
+        import torch
+
+        n = int(points.shape[0])
+        assert points.is_cuda and points.dtype == torch.float32 and tuple(points.shape) == (n, 2) and points.is_contiguous(), "points: float32 CUDA [n, 2]"
+        assert status.is_cuda and status.dtype == torch.int32 and tuple(status.shape) == (n,) and status.is_contiguous(), "status: int32 CUDA [n]"
+        hp, hs, hn = None, 0, 0
+        if history is not None:
+            assert history.is_cuda and history.dtype == torch.float32 and history.dim() == 3 and tuple(history.shape[1:]) == (n, 2), \
+                f"history: float32 CUDA [n_slots, {n}, 2]"
+            assert history.stride()[1:] == (2, 1), "history: the points of a slot must be tightly packed"
+            hp, hs, hn = history.data_ptr(), 4 * int(history.stride(0)), int(history.shape[0])
+        check(self.L.ofx_session_stream_tracks(self._h, level, points.data_ptr(), status.data_ptr(), n, hp, hs, hn), "stream_tracks")
+        self._tracks = (points, status, history)   # (kept alive while the pipeline may write them; replaces the previous ones)
+
     def uv(self, level: int):
         """Shift vector of `level` for the pair in progress (the slot alternates per pair: query after every swap)."""
         ptr = _vp()
@@ -521,47 +577,22 @@ def video_flow(frames, levels: int, window: int, mode: str = "lk_float", level: 
     frontend="main_cu" (the default for colour) is main.cu:198-240 exactly -- frame 0 averaged to grey only, every later frame
     averaged and then bilateral-filtered with `bilateral` = (window, sigma_s, sigma_b), 9x9 (2, 10) as there; "bilateral" filters
     every frame, "grey" filters none.  fast: the +-1 LSB filter.  A grey clip ignores these three."""
+    N, H, W = _clip_shape(frames)
+    assert 0 <= level < levels
+    out = _ring_for(N, H, W, level, frames.device, out)
+    _run_clip(frames, levels, window, mode, iters, min_det, batch, frontend, bilateral, fast, lambda s: s.stream_compose(out, level))
+    return out
+
+
+def _clip_shape(frames):
     import torch
 
     assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() in (3, 4), "frames: uint8 CUDA tensor [N, H, W] or [N, H, W, 3]"
     if frames.dim() == 4:
-        return _video_flow_3ch(frames, levels, window, mode, level, iters, min_det, batch, out, frontend or "main_cu", bilateral, fast)
-    N, H, W = (int(v) for v in frames.shape)
-    assert N >= 2 and frames.stride(2) == 1, "frames: at least two, with unit column stride"
-    assert 0 <= level < levels
-    hl, wl = H >> level, W >> level
-    slot = hl * wl * 2
-    stride = (slot + 3) // 4 * 4        # floats from slot to slot: a multiple of 16 bytes
-    if out is None:
-        flat = torch.empty((N - 1) * stride, dtype=torch.float32, device=frames.device)
-        out = flat.as_strided((N - 1, hl, wl, 2), (stride, 2 * wl, 2, 1))
-    else:
-        assert out.dtype == torch.float32 and tuple(out.shape) == (N - 1, hl, wl, 2), f"out must be float32 [{N - 1}, {hl}, {wl}, 2]"
-    pitch, fstride, ptr = int(frames.stride(1)), int(frames.stride(0)), frames.data_ptr()
-    aligned = pitch % 4 == 0 and fstride % 4 == 0 and ptr % 4 == 0 and pitch >= W
-    # (the kernels read a borrowed frame's rows in 4-byte groups: the last row's pitch must lie inside the tensor's storage)
-    st = frames.untyped_storage()
-    inside = ptr + (N - 1) * fstride + H * pitch <= st.data_ptr() + st.nbytes()
-    if aligned and inside:
-        borrow = iters <= 1 or pitch == pitch_for(W)   # (else the session copies every frame into its own planes)
-    else:
-        padded = torch.empty((N, H, pitch_for(W)), dtype=torch.uint8, device=frames.device)
-        padded[:, :, :W] = frames
-        frames, borrow = padded[:, :, :W], True
-    B = batch if batch is not None else suggest_stream_batch(W, H, levels, borrow_frames=borrow, two_stage=borrow)
-    B = max(1, min(int(B), N - 1))
-    s = Session(W, H, levels, window, mode, iters=iters, min_det=min_det, stream_batch=B, borrow_frames=borrow, two_stage=borrow,
-                strict=True)
-    try:
-        s.stream_compose(out, level)
-        s.stream_begin()
-        for i in range(N):
-            s.stream_submit(frames[i])
-        while s.stream_drain() != -2:
-            pass
-    finally:
-        s.close()
-    return out
+        assert int(frames.shape[3]) == 3, "frames: [N, H, W, 3]"
+    N, H, W = (int(v) for v in frames.shape[:3])
+    assert N >= 2, "frames: at least two"
+    return N, H, W
 
 
 def _ring_for(N, H, W, level, device, out):
@@ -576,35 +607,109 @@ def _ring_for(N, H, W, level, device, out):
     return out
 
 
-def _video_flow_3ch(frames, levels, window, mode, level, iters, min_det, batch, out, frontend, bilateral, fast):
-    """video_flow of a colour clip [N, H, W, 3]: the front end writes the session's own planes, so the pipeline always runs in its
-    fast configuration (borrowed planes, two stages) whatever the clip's layout; only the colour frames' own alignment matters."""
+def _run_clip(frames, levels, window, mode, iters, min_det, batch, frontend, bilateral, fast, attach):
+    """What video_flow, video_arrows and video_tracks share: the clip (grey [N, H, W] or colour [N, H, W, 3]) through the stream
+    pipeline, in the configuration video_flow documents; attach(session) sets the output stages before the stream begins.
+    Grey frames are read in place when their pitch and alignment allow it, otherwise through copies.  A colour clip's front end
+    writes the session's own planes, so the pipeline always runs in its fast configuration (borrowed planes, two stages)
+    whatever the clip's layout; only the colour frames' own alignment matters."""
     import torch
 
-    assert frontend in ("main_cu", "bilateral", "grey"), f"frontend: 'main_cu', 'bilateral' or 'grey', not {frontend!r}"
-    N, H, W, ch = (int(v) for v in frames.shape)
-    assert ch == 3 and N >= 2, "frames: [N, H, W, 3], at least two"
-    assert 0 <= level < levels
-    ptr, fstride, pitch = frames.data_ptr(), int(frames.stride(0)), int(frames.stride(1))
-    if not (frames.stride(3) == 1 and frames.stride(2) == 3 and ptr % 4 == 0 and fstride % 4 == 0 and pitch >= 3 * W):
-        # (every frame's base 4-byte aligned: rows padded to a multiple of four bytes)
-        padded = torch.empty((N, H, 3 * W + (-3 * W) % 4), dtype=torch.uint8, device=frames.device)
-        padded[:, :, :3 * W] = frames.reshape(N, H, 3 * W)
-        frames = padded[:, :, :3 * W].unflatten(2, (W, 3))
-    out = _ring_for(N, H, W, level, frames.device, out)
-    B = batch if batch is not None else suggest_stream_batch(W, H, levels, borrow_frames=True, two_stage=True)
+    N, H, W = _clip_shape(frames)
+    colour = frames.dim() == 4
+    if colour:
+        frontend = frontend or "main_cu"
+        assert frontend in ("main_cu", "bilateral", "grey"), f"frontend: 'main_cu', 'bilateral' or 'grey', not {frontend!r}"
+        ptr, fstride, pitch = frames.data_ptr(), int(frames.stride(0)), int(frames.stride(1))
+        if not (frames.stride(3) == 1 and frames.stride(2) == 3 and ptr % 4 == 0 and fstride % 4 == 0 and pitch >= 3 * W):
+            # (every frame's base 4-byte aligned: rows padded to a multiple of four bytes)
+            padded = torch.empty((N, H, 3 * W + (-3 * W) % 4), dtype=torch.uint8, device=frames.device)
+            padded[:, :, :3 * W] = frames.reshape(N, H, 3 * W)
+            frames = padded[:, :, :3 * W].unflatten(2, (W, 3))
+        borrow = True
+    else:
+        assert frames.stride(2) == 1, "frames: unit column stride"
+        pitch, fstride, ptr = int(frames.stride(1)), int(frames.stride(0)), frames.data_ptr()
+        aligned = pitch % 4 == 0 and fstride % 4 == 0 and ptr % 4 == 0 and pitch >= W
+        # (the kernels read a borrowed frame's rows in 4-byte groups: the last row's pitch must lie inside the tensor's storage)
+        st = frames.untyped_storage()
+        inside = ptr + (N - 1) * fstride + H * pitch <= st.data_ptr() + st.nbytes()
+        if aligned and inside:
+            borrow = iters <= 1 or pitch == pitch_for(W)   # (else the session copies every frame into its own planes)
+        else:
+            padded = torch.empty((N, H, pitch_for(W)), dtype=torch.uint8, device=frames.device)
+            padded[:, :, :W] = frames
+            frames, borrow = padded[:, :, :W], True
+    B = batch if batch is not None else suggest_stream_batch(W, H, levels, borrow_frames=borrow, two_stage=borrow)
     B = max(1, min(int(B), N - 1))
-    s = Session(W, H, levels, window, mode, iters=iters, min_det=min_det, stream_batch=B, borrow_frames=True, two_stage=True, strict=True)
+    s = Session(W, H, levels, window, mode, iters=iters, min_det=min_det, stream_batch=B, borrow_frames=borrow, two_stage=borrow,
+                strict=True)
     try:
-        win, ss, sb = bilateral
-        s.stream_frontend("grey" if frontend == "grey" else "bilateral", int(win), float(ss), float(sb), fast=fast,
-                          first_grey=frontend == "main_cu")
-        s.stream_compose(out, level)
+        if colour:
+            win, ss, sb = bilateral
+            s.stream_frontend("grey" if frontend == "grey" else "bilateral", int(win), float(ss), float(sb), fast=fast,
+                              first_grey=frontend == "main_cu")
+        attach(s)
         s.stream_begin()
+        submit = s.stream_submit_3ch if colour else s.stream_submit
         for i in range(N):
-            s.stream_submit_3ch(frames[i])
+            submit(frames[i])
         while s.stream_drain() != -2:
             pass
     finally:
         s.close()
+
+
+def arrow_grid(w: int, h: int, arrow_res: int):
+    """(offset, ny, nx) of the arrow field of a w x h level (main.cu:125-131): grid step offset = w // arrow_res, arrows at
+    i = 0, offset, .. < h and j = 0, offset, .. < w."""
+    assert w > 0 and h > 0 and arrow_res >= 1
+    offset = w // arrow_res
+    assert offset >= 1, f"arrow_res {arrow_res} is more than the level's width {w}"
+    return offset, -(-h // offset), -(-w // offset)
+
+
+def video_arrows(frames, levels: int, window: int, mode: str = "lk_float", level: int = 0, arrow_res: int = 30, iters: int = 1,
+                 min_det: float = 0.0, batch: Optional[int] = None, out=None, frontend: Optional[str] = None, bilateral=(9, 2.0, 10.0),
+                 fast: bool = False):
+    """The arrow field the reference program shows (main.cu:123-169) for every consecutive pair of a clip, sampled from the pairs'
+    flow pyramids by the pipeline's sampled output stage (Session.stream_arrows) -- no dense field is composed.  frames and the
+    other arguments as video_flow.  Returns int32 [N-1, ny, nx, 4]: out[p-1] holds (x0, y0, x1, y1) of pair p's arrows in the
+    pixels of `level`, x1 = y1 = -1 for an arrow the reference skips; (offset, ny, nx) = arrow_grid(W >> level, H >> level,
+    arrow_res).  `out` may supply the tensor (that shape, contiguous)."""
+    import torch
+
+    N, H, W = _clip_shape(frames)
+    assert 0 <= level < levels
+    _, ny, nx = arrow_grid(W >> level, H >> level, arrow_res)
+    if out is None:
+        out = torch.empty((N - 1, ny, nx, 4), dtype=torch.int32, device=frames.device)
+    else:
+        assert out.dtype == torch.int32 and tuple(out.shape) == (N - 1, ny, nx, 4) and out.is_contiguous(), f"out must be int32 [{N - 1}, {ny}, {nx}, 4]"
+    _run_clip(frames, levels, window, mode, iters, min_det, batch, frontend, bilateral, fast, lambda s: s.stream_arrows(out, level, arrow_res))
     return out
+
+
+def video_tracks(frames, points, levels: int, window: int, mode: str = "lk_float", level: int = 0, iters: int = 1, min_det: float = 0.0,
+                 batch: Optional[int] = None, frontend: Optional[str] = None, bilateral=(9, 2.0, 10.0), fast: bool = False):
+    """Points tracked through a clip by the pipeline's sampled output stage (Session.stream_tracks).  points: float32 [n, 2] of
+    (x, y) in the pixels of `level` in frame 0 (CUDA tensor or array; not modified).  Returns (positions float32 [N, n, 2],
+    status int32 [n]): positions[0] are the input points, positions[p] the positions in frame p; status is 0 for a point alive
+    at the end, else the pair at which it left the level or met a non-finite flow (it keeps its position from then on).  The
+    other arguments as video_flow."""
+    import torch
+
+    N, H, W = _clip_shape(frames)
+    assert 0 <= level < levels
+    pts = torch.as_tensor(points, dtype=torch.float32, device=frames.device)
+    assert pts.dim() == 2 and pts.shape[1] == 2 and pts.shape[0] >= 1, "points: [n, 2]"
+    n = int(pts.shape[0])
+    stride = (2 * n + 3) // 4 * 4     # floats from frame to frame: a multiple of 16 bytes
+    flat = torch.empty(N * stride, dtype=torch.float32, device=frames.device)
+    positions = flat.as_strided((N, n, 2), (stride, 2, 1))
+    positions[0] = pts
+    state = pts.clone().contiguous()
+    status = torch.zeros(n, dtype=torch.int32, device=frames.device)
+    _run_clip(frames, levels, window, mode, iters, min_det, batch, frontend, bilateral, fast,
+              lambda s: s.stream_tracks(state, status, positions[1:], level))
+    return positions, status

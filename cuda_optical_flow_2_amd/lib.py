@@ -103,6 +103,11 @@ _SIGS = {
     "ofx_session_flow_of": [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i)],
     "ofx_session_stream_compose": [_vp, _i, _vp, C.c_size_t, _i],
     "ofx_session_composed_of": [_vp, _i, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i)],
+    "ofx_sample_arrows": [C.POINTER(_vp), _i, _i, _i, _i, _i, _vp, _vp],
+    "ofx_advect_points": [C.POINTER(_vp), _i, _i, _i, _i, _i, _vp, _vp, _i, _vp],
+    "ofx_session_stream_arrows": [_vp, _i, _i, _vp, C.c_size_t, _i],
+    "ofx_session_arrows_of": [_vp, _i, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i)],
+    "ofx_session_stream_tracks": [_vp, _i, _vp, _vp, _i, _vp, C.c_size_t, _i],
     "ofx_session_stream_frontend": [_vp, _i, _i, _d, _d, _i],
     "ofx_session_stream_submit_3ch": [_vp, _vp, _i, _vp, C.POINTER(_i)],
     "ofx_session_stream_submit_frames_3ch": [_vp, C.POINTER(_vp), C.POINTER(_i), _i, _i, _vp, C.POINTER(_i)],

@@ -285,6 +285,25 @@ int ofx_warp_levels(const ofx_warp_desc *levels, int n, void *stream);
 int ofx_compose_flow(const float *const *d_flow_levels, int w, int h, int levels, int level, float *d_dst,
                      void *stream);
 
+/* The composed field sampled instead of composed everywhere.  C(y, x) below is ofx_compose_flow's value at pixel (y, x) of `level`
+ * (w x h), bit for bit; w and h must be multiples of 2^(levels - 1 - level) (every level but the coarsest even), otherwise
+ * OFX_E_INVALID.
+ *
+ * ofx_sample_arrows: the arrow field of main.cu:123-169.  offset = w / arrow_res (integer division; 0 is OFX_E_INVALID -- the
+ * reference would loop forever); grid points i = 0, offset, .. < h and j = 0, offset, .. < w, ny = ceil(h / offset) by
+ * nx = ceil(w / offset) of them.  At each: (u, v) = C(i, j), each clamped to [-offset, +offset] by float comparisons a NaN passes
+ * unclamped; x1 = (int)(u + (float)j), y1 = (int)(v + (float)i), one float add each, truncated toward zero.  The arrow is not
+ * drawn when x1 < 0 || y1 < 0 or a sum is NaN.  d_dst (16-byte aligned) receives [ny][nx] records of four int32
+ * (x0 = j, y0 = i, x1, y1), x1 = y1 = -1 for an undrawn arrow, in pixels of `level`.
+ *
+ * ofx_advect_points: n_points float32 (x, y) in pixels of `level` (d_points, 8-byte aligned) with an int32 status each (0 = alive)
+ * moved through one pair's flow.  A point with status != 0 is left alone; one outside [0, w) x [0, h) (NaN included) gets
+ * status = pair and keeps its position; otherwise (u, v) = C((int)y, (int)x) and (x + u, y + v), one float add each, is stored --
+ * unless a sum is not finite: status = pair, position kept.  pair >= 1. */
+int ofx_sample_arrows(const float *const *d_flow_levels, int w, int h, int levels, int level, int arrow_res, int32_t *d_dst, void *stream);
+int ofx_advect_points(const float *const *d_flow_levels, int w, int h, int levels, int level, int pair, float *d_points, int32_t *d_status,
+                      int n_points, void *stream);
+
 /* ---- layout helpers ------------------------------------------------------ */
 int ofx_extract_ch0(const uint8_t *d_src3, uint8_t *d_dst1, int w, int h, int dst_pitch, void *stream);
 int ofx_replicate_3ch(const uint8_t *d_src1, int src_pitch, uint8_t *d_dst3, int w, int h, void *stream);
@@ -538,6 +557,29 @@ int ofx_session_stream_compose(ofx_session *s, int level, float *d_ring, size_t 
 /* Slot of `pair` while it is one of the newest n_slots pairs composed into the ring; row0 / rows as ofx_session_flow_of.
  * OFX_E_STATE without a ring, OFX_E_INVALID for a pair not (or no longer) in it. */
 int ofx_session_composed_of(ofx_session *s, int pair, float **d_ptr, int *row0, int *rows);
+/* The stream pipeline's sampled output stage: what ofx_sample_arrows / ofx_advect_points compute, for every pair the pipeline
+ * completes, read straight from the pairs' flow pyramids -- no composed ring needed (the ring may be on as well).  Every call of
+ * ofx_session_stream_submit / _submit_frames / _drain that completes pairs enqueues ONE more launch on its `stream`, after the
+ * call's last launch, for arrows and tracks together (no timing kind records it); with neither set nothing is launched.
+ *   arrows: pair p's field (ofx_sample_arrows at `level` with `arrow_res`, main.cu:267 uses 30) goes to slot (p - 1) mod n_slots at
+ *     d_ring + slot * slot_stride_bytes, [ny][nx][4] int32 tightly packed.  d_ring 16-byte aligned, slot_stride_bytes a multiple
+ *     of 16 and at least ny * nx * 16, n_slots >= stream_batch, arrow_res between 1 and the level's width; otherwise OFX_E_INVALID.
+ *     Lifetime of a slot: as the compose ring's.
+ *   tracks: the caller's points (d_points, n_points x (x, y) float32 in pixels of `level`, 8-byte aligned) and statuses (d_status,
+ *     int32, 0 = alive) are advected through the completed pairs in increasing order (ofx_advect_points with pair = p: a lost point's
+ *     status is the pair that lost it); after the launch that completes pair p they hold the positions in frame p.  The result does
+ *     not depend on stream_batch.  The caller owns and initialises both buffers; ofx_session_stream_begin does not touch them.
+ *     d_history (may be NULL): slot (p - 1) mod n_slots at d_history + slot * slot_stride_bytes receives all n_points positions
+ *     after pair p, frozen ones included; 16-byte aligned, stride a multiple of 16 and at least n_points * 8, n_slots >= stream_batch.
+ * d_ring == NULL / d_points == NULL turns that output off (the default).  Only before the first frame of a stream (OFX_E_STATE once
+ * a stream has frames); stays in effect for later streams, whose pairs count from 1 again.  Sharded sessions: OFX_E_UNSUPPORTED
+ * (points cross shard boundaries). */
+int ofx_session_stream_arrows(ofx_session *s, int level, int arrow_res, int32_t *d_ring, size_t slot_stride_bytes, int n_slots);
+/* Slot of `pair` while it is one of the newest n_slots pairs sampled into the arrow ring, and the grid's size.  OFX_E_STATE
+ * without a ring, OFX_E_INVALID for a pair not (or no longer) in it. */
+int ofx_session_arrows_of(ofx_session *s, int pair, int32_t **d_ptr, int *ny, int *nx);
+int ofx_session_stream_tracks(ofx_session *s, int level, float *d_points, int32_t *d_status, int n_points, float *d_history,
+                              size_t slot_stride_bytes, int n_slots);
 /* Colour frames into the stream pipeline (main.cu:222-272 as one device-resident pipeline): with the front end set, every call
  * that launches a tick first enqueues ONE launch of the front end (ofx_frontend_1ch) for that tick's colour frames on its `stream`,
  * writing the filtered one-channel planes the tick then reads as its frames:
