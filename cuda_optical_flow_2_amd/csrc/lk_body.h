@@ -41,24 +41,6 @@ struct LkTable {
 // knows they came from the kernarg segment and would fall back to flat_* instructions with 64-bit VALU address
 // arithmetic; these casts put them back into the global address space (scalar base + 32-bit lane offset).
 #define OFX_GLOBAL __attribute__((address_space(1)))
-#ifndef OFX_LK_NT_STORES
-#define OFX_LK_NT_STORES 1
-#endif
-#ifndef OFX_LK_INTERIOR_VARIANT
-#define OFX_LK_INTERIOR_VARIANT 1
-#endif
-#ifndef OFX_LK_HBOX_SLIDE
-#define OFX_LK_HBOX_SLIDE 1
-#endif
-#ifndef OFX_LK_FOLD_PRIMING
-#define OFX_LK_FOLD_PRIMING 1 // the strip's first R - 1 rows enter through the high halves (lk_wave_impl, "Priming, folded")
-#endif
-#ifndef OFX_LK_HBOX_SLIDE_MAX_R
-#define OFX_LK_HBOX_SLIDE_MAX_R 12 // (4: the sliding box sums only where the neighbour columns are one lane away)
-#endif
-#ifndef OFX_LK_PROGRESS_PRIORITY
-#define OFX_LK_PROGRESS_PRIORITY 1
-#endif
 struct __attribute__((packed)) UnalignedU32 {
     uint32_t v;
 };
@@ -97,12 +79,7 @@ __device__ __forceinline__ uint32_t gload_u32_nt(const uint8_t *base, uint32_t o
 {
     return __builtin_nontemporal_load((const OFX_GLOBAL uint32_t *)((const OFX_GLOBAL uint8_t *)base + lane_off(off)));
 }
-__device__ __forceinline__ uint32_t gload_u32_unaligned(const uint8_t *base, uint32_t off)
-{
-    return ((const OFX_GLOBAL UnalignedU32 *)((const OFX_GLOBAL uint8_t *)base + lane_off(off)))->v;
-}
 typedef OFX_GLOBAL float *gfloat_ptr;
-__device__ __forceinline__ gfloat_ptr gptr_f32(float *base, uint32_t idx) { return (gfloat_ptr)base + lane_off(idx); }
 // base + a BYTE offset kept by the caller (see lane_off_var): selects as scalar base + 32-bit lane offset
 __device__ __forceinline__ gfloat_ptr gptr_f32_var(float *base, uint32_t &byte_off)
 {
@@ -112,20 +89,12 @@ __device__ __forceinline__ gfloat_ptr gptr_f32_var(float *base, uint32_t &byte_o
 // the trailing window re-reads from L2
 __device__ __forceinline__ void gstore_f32x2(gfloat_ptr p, float a, float b)
 {
-#if OFX_LK_NT_STORES
     __builtin_nontemporal_store(f32x2{a, b}, (OFX_GLOBAL f32x2 *)p);
-#else
-    *(OFX_GLOBAL f32x2 *)p = f32x2{a, b};
-#endif
 }
 __device__ __forceinline__ void gstore_f32x4(gfloat_ptr p, f32x4 v)
 {
     typedef float f32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));
-#if OFX_LK_NT_STORES
     __builtin_nontemporal_store((f32x4_a8)v, (OFX_GLOBAL f32x4_a8 *)p);
-#else
-    *(OFX_GLOBAL f32x4_a8 *)p = (f32x4_a8)v;
-#endif
 }
 __device__ __forceinline__ void gstore_i32(int32_t *p, int32_t v) { *(OFX_GLOBAL int32_t *)p = v; }
 // stores at (wave-uniform base) + (per-lane byte offset)
@@ -184,24 +153,17 @@ __device__ __forceinline__ int lane_from(int x)
 // is kept a two-operand add (the fence after it stops the compiler from merging two of them into a v_add3_u32, which
 // cannot carry a DPP operand), so that the combiner folds move and add into ONE v_add_u32_dpp -- 2 instructions per
 // neighbour term instead of 3 for two.  Addition is commutative, so the operand mix-up that broke the subtract form
-// (above) cannot change the result.  OFX_LK_FOLD_DPP_ADDS=0 restores the fenced moves + add3.
-#ifndef OFX_LK_FOLD_DPP_ADDS
-#define OFX_LK_FOLD_DPP_ADDS 1
-#endif
+// (above) cannot change the result.
 template <int D>
 __device__ __forceinline__ int add_from(int acc, int x)
 {
     if constexpr (D == 0) {
         return acc + x;
     } else {
-#if OFX_LK_FOLD_DPP_ADDS
         const int near = lane_from<(D > 0 ? D - 1 : D + 1)>(x); // all but the last lane step: fenced moves
         int r = acc + __builtin_amdgcn_update_dpp(0, near, D > 0 ? 0x130 /* wave_shl:1 */ : 0x138 /* wave_shr:1 */, 0xf, 0xf, true);
         asm volatile("" : "+v"(r));
         return r;
-#else
-        return acc + lane_from<D>(x);
-#endif
     }
 }
 
@@ -272,39 +234,23 @@ __device__ __forceinline__ int col_minus(const int (&a)[4], int y)
 template <int R>
 __device__ __forceinline__ void hbox4(const int (&a)[4], int (&out)[4])
 {
-    if constexpr (OFX_LK_HBOX_SLIDE && R <= OFX_LK_HBOX_SLIDE_MAX_R) {
-        // Windows of neighbouring columns differ by one column leaving and one entering (for R <= 4 both lie in this lane or the
-        // one next to it, for R <= 8 up to two lanes away, else three): out[0] and out[3] in full, then out[1] = out[0] - a(-R) + a(R + 1) and
-        // out[2] = out[3] - a(R + 3) + a(2 - R), each difference two instructions -- n = a(leaving) - out; out' = a(entering) - n
-        // -- two short dependent chains, 11-12 instructions per quantity instead of 13.
-        int q[4], s[4];
-        q[0] = a[0];
-        q[1] = q[0] + a[1];
-        q[2] = q[1] + a[2];
-        q[3] = q[2] + a[3];
-        s[3] = a[3];
-        s[2] = s[3] + a[2];
-        s[1] = s[2] + a[1];
-        s[0] = q[3];
-        out[0] = hbox_one<R, 0>(q, s);
-        out[3] = hbox_one<R, 3>(q, s);
-        out[1] = col_minus<1 + R>(a, col_minus<0 - R>(a, out[0]));
-        out[2] = col_minus<2 - R>(a, col_minus<3 + R>(a, out[3]));
-    } else {
-        int q[4], s[4];
-        q[0] = a[0];
-        q[1] = q[0] + a[1];
-        q[2] = q[1] + a[2];
-        q[3] = q[2] + a[3];
-        s[3] = a[3];
-        s[2] = s[3] + a[2];
-        s[1] = s[2] + a[1];
-        s[0] = q[3];
-        out[0] = hbox_one<R, 0>(q, s);
-        out[1] = hbox_one<R, 1>(q, s);
-        out[2] = hbox_one<R, 2>(q, s);
-        out[3] = hbox_one<R, 3>(q, s);
-    }
+    // Windows of neighbouring columns differ by one column leaving and one entering (for R <= 4 both lie in this lane or the
+    // one next to it, for R <= 8 up to two lanes away, else three): out[0] and out[3] in full, then out[1] = out[0] - a(-R) + a(R + 1) and
+    // out[2] = out[3] - a(R + 3) + a(2 - R), each difference two instructions -- n = a(leaving) - out; out' = a(entering) - n
+    // -- two short dependent chains, 11-12 instructions per quantity instead of 13.
+    int q[4], s[4];
+    q[0] = a[0];
+    q[1] = q[0] + a[1];
+    q[2] = q[1] + a[2];
+    q[3] = q[2] + a[3];
+    s[3] = a[3];
+    s[2] = s[3] + a[2];
+    s[1] = s[2] + a[1];
+    s[0] = q[3];
+    out[0] = hbox_one<R, 0>(q, s);
+    out[3] = hbox_one<R, 3>(q, s);
+    out[1] = col_minus<1 + R>(a, col_minus<0 - R>(a, out[0]));
+    out[2] = col_minus<2 - R>(a, col_minus<3 + R>(a, out[3]));
 }
 
 // ---- the five box sums of a step in lockstep -----------------------------------------------------------------------------------
@@ -445,16 +391,11 @@ __device__ __forceinline__ void hbox4x5(const int (&a)[5][4], int (&out)[5][4])
     int o0[5], o1[5], o2[5], o3[5];
     hbox_one5<R, 0>(q, s, o0);
     hbox_one5<R, 3>(q, s, o3);
-    if constexpr (OFX_LK_HBOX_SLIDE && R <= OFX_LK_HBOX_SLIDE_MAX_R) {
-        int t[5];
-        col_minus5<0 - R>(a, o0, t);
-        col_minus5<1 + R>(a, t, o1);
-        col_minus5<3 + R>(a, o3, t);
-        col_minus5<2 - R>(a, t, o2);
-    } else {
-        hbox_one5<R, 1>(q, s, o1);
-        hbox_one5<R, 2>(q, s, o2);
-    }
+    int t[5]; // the sliding differences of hbox4
+    col_minus5<0 - R>(a, o0, t);
+    col_minus5<1 + R>(a, t, o1);
+    col_minus5<3 + R>(a, o3, t);
+    col_minus5<2 - R>(a, t, o2);
 #pragma unroll
     for (int n = 0; n < 5; ++n) out[n][0] = o0[n], out[n][1] = o1[n], out[n][2] = o2[n], out[n][3] = o3[n];
 }
@@ -841,8 +782,8 @@ __device__ __forceinline__ void lk_wave_impl(const LkTable &T, int wave, int lan
     // the restart needs no code of its own -- its multiplier is 0 in steps H .. R + 1, and from step R + 2 on it is the row
     // leaving.  The first row comes out at step PR = R + 1 instead of 2R: R - 1 steps less per strip (3 of 8 for the 9x9
     // window, 8 of 18 for 19x19), which is 17 % -> 11 % of the steps of a 4K pair launched alone and what bounds the
-    // rows a rank of a sharded pair recomputes.  OFX_LK_FOLD_PRIMING=0 (H = 0) is the plain 2R-step priming.
-    constexpr int H = OFX_LK_FOLD_PRIMING ? R - 1 : 0;
+    // rows a rank of a sharded pair recomputes.
+    constexpr int H = R - 1;
     constexpr int PR = 2 * R - H;    // steps before the first output row
     const int y_first = ys - R;      // first derivative row this strip needs
     const int y_lo0 = y_first + H;   // derivative row of the low halves at step 0
@@ -864,9 +805,6 @@ __device__ __forceinline__ void lk_wave_impl(const LkTable &T, int wave, int lan
     }
 
     int vxx[4] = {0, 0, 0, 0}, vyy[4] = {0, 0, 0, 0}, vxy[4] = {0, 0, 0, 0}, vxt[4] = {0, 0, 0, 0}, vyt[4] = {0, 0, 0, 0};
-#ifdef OFX_X_SKELETON // timing experiment: row loads, the wait, the LDS exchange and the streaming stores -- nothing else
-    uint32_t skel = 0u;
-#endif
 
     auto body = [&](auto K, int s) {
         constexpr int k = decltype(K)::value; // s mod 3
@@ -875,20 +813,6 @@ __device__ __forceinline__ void lk_wave_impl(const LkTable &T, int wave, int lan
         const bool folded = H > 0 && s < H;   // high halves: the entering row y_first + s
         const int yh = folded ? y_first + s : yo;
 
-#if defined(OFX_X_EXTRA_SALU) || defined(OFX_X_EXTRA_VALU) // sensitivity experiments: N more scalar / vector instructions per row step
-        {
-#ifdef OFX_X_EXTRA_SALU
-            int sx = s;
-#pragma unroll
-            for (int e = 0; e < OFX_X_EXTRA_SALU; ++e) asm volatile("s_add_u32 %0, %0, 1" : "+s"(sx));
-#endif
-#ifdef OFX_X_EXTRA_VALU
-            int vx = lane;
-#pragma unroll
-            for (int e = 0; e < OFX_X_EXTRA_VALU; ++e) asm volatile("v_add_u32 %0, %0, %0" : "+v"(vx));
-#endif
-        }
-#endif
         // Issue the loads of the rows the next step adds (yy + 2 and the high stream's).  They are finished (mask / permute /
         // unpack) at the end of this step, before its flow stores: gfx9 counts loads and stores in one vmcnt and only orders
         // returns within a type, so a wait for a load that has younger stores outstanding is a wait for those stores too.
@@ -919,25 +843,16 @@ __device__ __forceinline__ void lk_wave_impl(const LkTable &T, int wave, int lan
         uint32_t rowm = ((yy >= 0 && yy < A.h) ? 0x00000001u : 0u) | ((yh >= 0 && yh < A.h) ? him : 0u);
         if constexpr (INTERIOR) rowm = (uint32_t)__builtin_amdgcn_readfirstlane((int)rowm); // one scalar multiplier pair for all columns
         const uint32_t mm[4] = {(uint32_t)cm[0] & rowm, (uint32_t)cm[1] & rowm, (uint32_t)cm[2] & rowm, (uint32_t)cm[3] & rowm};
-#ifndef OFX_X_SKELETON
         s2 ix[4], iy[4], it[4];
         derivs_pk(wp[k], wp[(k + 1) % 3], wp[(k + 2) % 3], two, ix, iy, it);
         accumulate_pk(ix, iy, it, mm, vxx, vyy, vxy, vxt, vyt);
-#else
-        (void)mm;
-#endif
         // row yy - 1 is done with: its slot takes row yy + 2 once the step's arithmetic is over
         // (the barrier keeps the scheduler from hoisting these few ALU ops -- and with them the wait -- up to the loads;
         // pin_row keeps the sink passes from moving them down into the next step, below its loads)
         auto take_rows = [&]() {
             __builtin_amdgcn_sched_barrier(0);
-#ifdef OFX_X_SKELETON
-            skel ^= finish_row(pf_ip) ^ finish_next(pf_in) ^ finish_row(pf_op) ^ finish_next(pf_on);
-            asm volatile("" : "+v"(skel));
-#else
             unpack_pk(finish_row(pf_ip), finish_next(pf_in), finish_row(pf_op), finish_next(pf_on), wp[k]);
             pin_row(wp[k]);
-#endif
         };
 
         // ---- emit output row y = yy - R ------------------------------------------------------------------------
@@ -947,30 +862,14 @@ __device__ __forceinline__ void lk_wave_impl(const LkTable &T, int wave, int lan
         f32x4 xlo, xhi; // this lane's two chunks of the exchanged row (only defined, and only used, in emitting steps: the
         asm("" : "=v"(xlo), "=v"(xhi)); // empty asm stands in for an initialisation that would cost 8 v_mov per step)
         if (emit) {
-#ifdef OFX_X_SKELETON
-#pragma unroll
-            for (int j = 0; j < 4; ++j) hxx[j] = hyy[j] = hxy[j] = hxt[j] = hyt[j] = (int)skel + j;
-#elif defined(OFX_X_NOHBOX) // timing experiments (OFX_BUILD_DEFS): what a stage costs is what the launch gains without it
-#pragma unroll
-            for (int j = 0; j < 4; ++j) hxx[j] = vxx[j], hyy[j] = vyy[j], hxy[j] = vxy[j], hxt[j] = vxt[j], hyt[j] = vyt[j];
-#else
             hbox4<R>(vxx, hxx);
             hbox4<R>(vyy, hyy);
             hbox4<R>(vxy, hxy);
             hbox4<R>(vxt, hxt);
             hbox4<R>(vyt, hyt);
-#endif
             if constexpr (!SUMS) {
                 // every lane solves (the halo lanes' results are dropped): no divergence before the rows are taken
-#if defined(OFX_X_NOSOLVE) || defined(OFX_X_SKELETON)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    uv[2 * j] = __int_as_float(hxx[j] ^ hxy[j] ^ hxt[j]);
-                    uv[2 * j + 1] = __int_as_float(hyy[j] ^ hyt[j]);
-                }
-#else
                 solve_lane<MODE, FAST>(hxx, hyy, hxy, hxt, hyt, sopt, uv);
-#endif
                 if constexpr (MAY_ACC) {
                     if (A.accumulate) { // (old_uv is zero in the lanes that do not store)
 #pragma unroll
@@ -1029,7 +928,8 @@ __device__ __forceinline__ void lk_wave_impl(const LkTable &T, int wave, int lan
     // other (70 / 95 / 125 / 165 us of a 186 us launch, tools/stream_timeline.py) and the last one runs its final quarter
     // alone, at the ~60 % issue rate of a lone wave.  Each wave therefore lowers its own priority as it advances through its
     // strip (3 -> 0 at the quarter marks): whoever is behind is served first, and the waves of a SIMD finish together.
-#if OFX_LK_PROGRESS_PRIORITY
+    // (a macro shared by the three forms of the march, not a function: as an inlined function the register allocation of the
+    // iteration kernels comes out differently, and they sit on the 128-VGPR line)
     const int q1 = nsteps / 4, q2 = nsteps / 2, q3 = nsteps - nsteps / 4;
     __builtin_amdgcn_s_setprio(3);
 #define OFX_LK_PRIO_STEP()                               \
@@ -1038,9 +938,6 @@ __device__ __forceinline__ void lk_wave_impl(const LkTable &T, int wave, int lan
         else if (s >= q2) __builtin_amdgcn_s_setprio(1); \
         else if (s >= q1) __builtin_amdgcn_s_setprio(2); \
     } while (0)
-#else
-#define OFX_LK_PRIO_STEP() ((void)0)
-#endif
     int s = 0;
     while (true) {
         body(std::integral_constant<int, 0>{}, s);
@@ -1051,7 +948,6 @@ __device__ __forceinline__ void lk_wave_impl(const LkTable &T, int wave, int lan
         if (++s >= nsteps) break;
         OFX_LK_PRIO_STEP();
     }
-#undef OFX_LK_PRIO_STEP
 }
 
 
@@ -1059,6 +955,7 @@ __device__ __forceinline__ void lk_wave_impl(const LkTable &T, int wave, int lan
 #include "lk_body_warp.h" // the warp of lk_iter in two stages (ITER == 2 below)
 #include "lk_body_buf.h" // lk_wave_buf: the same march on buffer resources (a fifth of the scalar instructions)
 #include "lk_body_wide.h" // lk_wave_wide: eight columns per lane (round 4)
+#undef OFX_LK_PRIO_STEP
 namespace ofx_dev {
 
 // One wave of the fused level kernel: picks the variant for its tile (wave-uniform: two complete copies of the march, nothing
@@ -1077,19 +974,13 @@ __device__ __forceinline__ void lk_wave(const LkTable &T, int wave, int lane, ui
     }
     const int tile = (wave - T.first_block[level]) % T.lv[level].tiles_x;
     const int cb0 = tile * TileGeom<R>::OUT_W - TileGeom<R>::LO_LANE * 4;
-    if constexpr (OFX_LK_BUFFER_PATH && !SUMS && !MAY_ACC) { // (the host keeps levels of 2 GB and more out of such launches)
-#if OFX_LK_INTERIOR_VARIANT
+    if constexpr (!SUMS && !MAY_ACC) { // (the host keeps levels of 2 GB and more out of such launches)
         if (cb0 >= 0 && cb0 + 256 <= T.lv[level].w) lk_wave_buf<R, MODE, FAST, true, LDS_ROWS, ITER>(T, wave, lane, xlds);
-        else
-#endif
-            lk_wave_buf<R, MODE, FAST, false, LDS_ROWS, ITER>(T, wave, lane, xlds);
+        else lk_wave_buf<R, MODE, FAST, false, LDS_ROWS, ITER>(T, wave, lane, xlds);
         return;
     }
-#if OFX_LK_INTERIOR_VARIANT
     if (cb0 >= 0 && cb0 + 256 <= T.lv[level].w) lk_wave_impl<R, MODE, SUMS, MAY_ACC, FAST, true>(T, wave, lane, xlds);
-    else
-#endif
-        lk_wave_impl<R, MODE, SUMS, MAY_ACC, FAST, false>(T, wave, lane, xlds);
+    else lk_wave_impl<R, MODE, SUMS, MAY_ACC, FAST, false>(T, wave, lane, xlds);
 }
 
 } // namespace ofx_dev

@@ -1,5 +1,5 @@
-// The LK march on buffer resources: the scalar diet of round 3.  Included by lk_body.h (which holds the shared pieces: packed
-// rows, derivatives, accumulation, box sums, the LDS exchange) -- not a stand-alone header.
+// The LK march on buffer resources.  Included by lk_body.h (which holds the shared pieces: packed rows, derivatives, accumulation,
+// box sums, the LDS exchange) -- not a stand-alone header.
 //
 // profiles/r03_ablation.txt: adding 40 scalar instructions to a row step lengthens the stream launch by 8.5 us -- a SIMD pays
 // ~1.35 cycles for every scalar instruction of its waves, and lk_wave_impl spends ~220 of them per step (a fifth of the launch),
@@ -14,26 +14,14 @@
 //   * a lane that must not store gets the lane offset kOob: the store is dropped by the same check -- no exec mask.
 // tools/ubench/buffer_ops.hip checks these behaviours on the device (unaligned dword, marker row, dropped stores).
 // The arithmetic, the LDS exchange, the packed registers and the order of loads and stores are those of lk_wave_impl; results
-// are bit-identical (the same tests run on both; OFX_LK_BUFFER_PATH=0 builds the old form everywhere).  The old form stays
-// for the inspection variant (SUMS) and for accumulating launches (MAY_ACC); the host keeps levels of 2 GB and more out of
-// launches that use this one (lk_launch.h).
+// are bit-identical (the same tests run on both).  lk_wave_impl stays for the inspection variant (SUMS) and for launches that may
+// accumulate in place (MAY_ACC); the host keeps levels of 2 GB and more out of launches that use this one (lk_launch.h).
 #pragma once
 
 namespace ofx_dev {
 
-#ifndef OFX_LK_BUFFER_PATH
-#define OFX_LK_BUFFER_PATH 1
-#endif
-#ifndef OFX_LK_HBOX_LOCKSTEP
-#define OFX_LK_HBOX_LOCKSTEP 1
-#endif
 constexpr int kOob = (int)0x80000000;
-#if defined(OFX_LK_STORE_AUX) // (experiments: other cache-policy bits of the flow stores -- bit 0 sc0, bit 1 nt, bit 4 sc1)
-#elif defined(OFX_X_TINYSTORE)
-#define OFX_LK_STORE_AUX 0 // (cached)
-#else
-#define OFX_LK_STORE_AUX (OFX_LK_NT_STORES ? 2 : 0) // nt: streaming stores (see "the flow stores" in lk_body.h)
-#endif
+constexpr int kLkStoreAux = 2; // cache policy of the flow stores: nt, streaming (see "the flow stores" in lk_body.h)
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base, int bytes)
@@ -41,7 +29,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base, in
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, bytes, 0x00027000);
 }
 
-// DMA (OFX_LK_DMA_ROWS): the rows of a step are fetched TWO steps ahead, straight into LDS (buffer_load ... lds: no VGPR holds
+// DMA: the rows of a step are fetched TWO steps ahead, straight into LDS (buffer_load ... lds: no VGPR holds
 // them while they are in flight), six per step -- prev / shifted next / own next, for the entering and the leaving window -- into
 // one of two sets of six 256-byte rows behind the wave's exchange row.  The point is the wait: gfx9 counts loads and stores in
 // ONE counter, so the march's "wait for the rows fetched a step ahead" was also a wait for the two flow stores of the step
@@ -49,54 +37,17 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base, in
 // themselves, so with the next step's six loads already issued behind them, s_waitcnt vmcnt(6) means "this step's rows have
 // arrived" whatever the stores are doing: if one of this step's rows were still out, all six younger loads would be too, and
 // the count could not be six.  Stores may now take up to two steps to complete before a wave waits for them.
-#ifndef OFX_LK_DMA_ROWS
-#define OFX_LK_DMA_ROWS 1
-#endif
-// Deferred flow store (experiment; -DOFX_LK_DEFER_STORE=1): a step's output row stays in a SECOND exchange row
-// of LDS and is stored one step later, in the middle of the next step -- after that step's row loads have been issued, so that no
-// load queues behind the two 1 KB stores of the row before it.  Measured: profiles/r04_ablation.txt.
-// 0: never; 1: every launch of the buffer march; 2 (shipped): the accumulating launches of lk_iter only (ITER 1, 2, 4), whose step
-// holds the most memory operations (row loads, the old flow, eight warp taps, three stores): between +2.3 % and 0 at 4K / 5
-// iterations (two batches, different boxes); the reference-defined tick measured 0 % (ring in the Infinity Cache) to -3 % (frames
-// from HBM) with it and keeps the plain order.
-#ifndef OFX_LK_DEFER_STORE
-#define OFX_LK_DEFER_STORE 2
-#endif
-// The leaving window's rows out of an LDS ring (round 4).  In the accumulating launches 16 B/px of flow stream through the XCD's 4 MB
-// L2 between a row's first read (entering the vertical window) and its second (leaving it, 2R + 1 steps later): the second read
-// misses and goes to the fabric -- 391 MB of the launch's 1 600 MB of fabric reads (profiles/r04_ablation.txt batch 6).  A lane
-// keeps the finished dwords (prev, next) of the last 2R + 1 entering rows in 8 bytes per row of LDS of its own and takes the leaving
-// row from there: no load, no fabric traffic, no finish.  (R + 1) KB per wave; accumulating launches without deep fetch,
-// R <= 8.  OFX_LK_OUT_RING=0: both rows from memory, as the tick does (whose L2 holds them: it fetches 1.10 x its algorithmic reads).
-// MEASURED (profiles/r04_ablation.txt batch 6): fabric reads of the launch 1 601 -> 1 386 MB (traffic 1.35 x -> 1.23 x algorithmic), launch
-// 462 vs 459 us, 1080p and the pair-at-a-time path 1.6 % slower (the packed selectors it needs to stay within 128 VGPRs cost ~18 vector
-// instructions per row step): the launch is not bound by its fabric traffic either.  Bit-exact; OFF by default.
-#ifndef OFX_LK_OUT_RING
-#define OFX_LK_OUT_RING 0
-#endif
-template <int R, int ITER, bool DMA>
-constexpr bool lk_out_ring()
-{
-    return OFX_LK_OUT_RING && (ITER == 1 || ITER == 2 || ITER == 4) && !DMA && R <= 8;
-}
-template <int R, int ITER, bool DMA>
-constexpr int lk_ring_bytes()
-{
-    return lk_out_ring<R, ITER, DMA>() ? (R + 1) * 1024 : 0; // (two rows per 16-byte lane slot: the address is 16 * lane + a scalar)
-}
-#ifndef OFX_LK_ACC_LOAD_AUX
-#define OFX_LK_ACC_LOAD_AUX 0
-#endif
-// 1: the accumulating launches read the old flow in the exchanged (gap-free) layout and put it back in place through LDS.  Built to
-// test whether the launch's fabric reads (FETCH_SIZE: 1.65 x its algorithmic reads) come from the two half-used 16-byte loads per
-// lane: they do not (FETCH_SIZE 811 vs 781 GiB-units, launch 452-455 vs 439-457 us: profiles/r04_ablation.txt batch 5).  Off.
-#ifndef OFX_LK_ACC_XLOAD
-#define OFX_LK_ACC_XLOAD 0
-#endif
-constexpr int kLkXRows = OFX_LK_DEFER_STORE ? 2 : 1;            // exchange rows per wave
+// Deferred flow store (DEFER): a step's output row stays in a SECOND exchange row of LDS and is stored one step later, in the middle
+// of the next step -- after that step's row loads have been issued, so that no load queues behind the two 1 KB stores of the row
+// before it.  Only the accumulating launches of lk_iter (ITER 1, 2, 4) do it, whose step holds the most memory operations (row
+// loads, the old flow, eight warp taps, three stores); the tick measured 0 % to -3 % with it and keeps the plain order
+// (profiles/r04_ablation.txt).
+constexpr int kLkXRows = 2;                                     // exchange rows per wave (the second one: DEFER)
 constexpr int kLkWaveLdsX = kLkXRows * kLkWaveLds;              // what a wave of the buffer march owns without the deep fetch
 constexpr int kLkDmaRowBytes = 256, kLkDmaRows = 6, kLkDmaSetBytes = kLkDmaRows * kLkDmaRowBytes;
-constexpr int kLkWaveLdsDma = kLkWaveLdsX + 2 * kLkDmaSetBytes; // the exchange row(s), then two sets of fetched rows
+constexpr int kLkWaveLdsDma = kLkWaveLdsX + 2 * kLkDmaSetBytes; // the exchange rows, then two sets of fetched rows
+// (the host sizes the dynamic LDS and asks for the occupancy with these)
+static_assert(kLkWaveLdsX == 2 * 2176 && kLkWaveLdsDma == 2 * 2176 + 2 * 1536, "LDS per wave of the buffer march");
 
 // ITER (refinement iterations of lk_iter): 0 = flow = result (the reference's level); 1 = flow += result,
 // the row's old flow fetched through the flow's own resource with the step's rows; 2 = the same, and the march also writes the
@@ -110,8 +61,7 @@ __device__ __forceinline__ void lk_wave_buf(const LkTable &T, int wave, int lane
     using G = TileGeom<R>;
     constexpr int NS = 2 * R + 1;
     constexpr bool ACC = ITER == 1 || ITER == 2 || ITER == 4, WOUT = ITER >= 2, ROWWIN = ITER >= 4;
-    constexpr bool DEFER = OFX_LK_DEFER_STORE == 1 || (OFX_LK_DEFER_STORE == 2 && ACC);
-    constexpr bool RING = lk_out_ring<R, ITER, DMA>(); // the leaving rows come out of the wave's LDS ring (xlds + kLkWaveLdsX)
+    constexpr bool DEFER = ACC; // the deferred flow store (above)
 
     if (wave >= T.first_block[T.n]) return;
     int level = 0, hi = T.n;
@@ -174,7 +124,7 @@ __device__ __forceinline__ void lk_wave_buf(const LkTable &T, int wave, int lane
     [[maybe_unused]] WarpRowState WM;
     if constexpr (WOUT) {
         pin_scalar(A.warp_scale);
-        rs_wsrc = make_rsrc(A.warp_src, plane_bytes + (OFX_WARP_LEAN ? 3 : 0)); // (lk_body_warp.h: a tap dword may start in the plane's last three bytes)
+        rs_wsrc = make_rsrc(A.warp_src, plane_bytes + 3); // (lk_body_warp.h: a tap dword may start in the plane's last three bytes)
         rs_wout = make_rsrc(A.warp_out, plane_bytes);
         const bool out_lane = lane >= G::LO_LANE && lane <= G::HI_LANE && cb < A.w;
         wvo = out_lane ? (uint32_t)cb : (uint32_t)kOob; // (a level whose width is no multiple of 4 ends inside the dword: the rest is row padding)
@@ -322,17 +272,13 @@ __device__ __forceinline__ void lk_wave_buf(const LkTable &T, int wave, int lane
     };
 
     // (the folded priming and the slot rotation are those of lk_wave_impl)
-    constexpr int H = OFX_LK_FOLD_PRIMING ? R - 1 : 0;
+    constexpr int H = R - 1;
     constexpr int PR = 2 * R - H;
     const int y_lo0 = y_first + H;
     const int nsteps = (ye - ys) + PR;
     RowPk<MODE> wp[3];
     const s2 two = pk_two();
     refresh_map(y_first - 1);
-    // RING: slot ((r - (y_lo0 - 1)) mod NS) holds image row r; this lane's 8 bytes of it are (prev, next), finished
-    // (rows 2j and 2j + 1 share a lane's 16 bytes of KB j, so that the address is the lane's 16 * lane -- a register the exchange keeps
-    // anyway -- plus a scalar: a pointer of its own would be the 129th VGPR of a kernel that must fit 128)
-    auto ring_at = [&](int slot) -> lds_ptr { return (lds_ptr)xlds + (kLkWaveLdsX + (slot >> 1) * 1024 + (slot & 1) * 8) + lane_off_var(l16); };
     {
         uint32_t pi, ni, po = 0u, no = 0u;
 #pragma unroll
@@ -340,10 +286,8 @@ __device__ __forceinline__ void lk_wave_buf(const LkTable &T, int wave, int lane
             load_pair(y_lo0 - 1 + t, false, pi, ni);
             if constexpr (H > 0) load_pair(y_first - 1 + t, true, po, no);
             unpack_pk(pi, ni, po, no, wp[t]);
-            if constexpr (RING) *(__attribute__((address_space(3))) u32x2 *)(ring_at(t % NS)) = u32x2{pi, ni};
         }
     }
-    [[maybe_unused]] int rslot = 3 % NS; // the slot of the row the next step adds (and of the one it takes out of the ring)
     if constexpr (DMA) { // the rows step 0 takes at its end (the b rows of step 1): y_lo0 + 2 and the high stream's
         const int ro0 = (H > 1 && 1 < H) ? y_first + 2 : y_lo0 - NS + 2;
         issue_rows(0, y_lo0 + 2, ro0);
@@ -359,25 +303,17 @@ __device__ __forceinline__ void lk_wave_buf(const LkTable &T, int wave, int lane
 
     // the two streaming stores of output row (step s_row) from its chunks xlo / xhi of the exchanged layout
     auto store_row = [&](int s_row, const f32x4 xlo, const f32x4 xhi) {
-#if defined(OFX_X_TINYSTORE) // timing experiment: every row lands in the first MB of the flow (L2 hits, no HBM write stream)
-        const int fso = __builtin_amdgcn_readfirstlane((fso0 + (s_row - PR) * fstep) & 0xff000);
-#else
         const int fso = __builtin_amdgcn_readfirstlane(fso0 + (s_row - PR) * fstep); // this row's offset in the flow
-#endif
         // two gap-free streaming stores of 1 KB; the lanes past the tile's end are dropped by the resource's range check
-#if defined(OFX_X_NOSTORE) // timing experiment: the row is exchanged but never stored
-        asm volatile("" : : "v"(xlo), "v"(xhi), "s"(fso));
-#else
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, xlo), rs_flow, INTERIOR ? lane_off_var(l16) : vo_lo, fso, OFX_LK_STORE_AUX);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, xhi), rs_flow, vo_hi, fso, OFX_LK_STORE_AUX);
-#endif
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, xlo), rs_flow, INTERIOR ? lane_off_var(l16) : vo_lo, fso, kLkStoreAux);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, xhi), rs_flow, vo_hi, fso, kLkStoreAux);
         if (__builtin_expect(ragged, 0)) { // the one lane whose chunk holds a single pixel
             const u32x4 ql = __builtin_bit_cast(u32x4, xlo), qh = __builtin_bit_cast(u32x4, xhi);
-            __builtin_amdgcn_raw_buffer_store_b64(u32x2{ql.x, ql.y}, rs_flow, st_lo2 ? l16 : (uint32_t)kOob, fso, OFX_LK_STORE_AUX);
-            __builtin_amdgcn_raw_buffer_store_b64(u32x2{qh.x, qh.y}, rs_flow, st_hi2 ? l16 + 1024u : (uint32_t)kOob, fso, OFX_LK_STORE_AUX);
+            __builtin_amdgcn_raw_buffer_store_b64(u32x2{ql.x, ql.y}, rs_flow, st_lo2 ? l16 : (uint32_t)kOob, fso, kLkStoreAux);
+            __builtin_amdgcn_raw_buffer_store_b64(u32x2{qh.x, qh.y}, rs_flow, st_hi2 ? l16 + 1024u : (uint32_t)kOob, fso, kLkStoreAux);
         }
     };
-    // OFX_LK_DEFER_STORE: the row of step s_row out of its exchange row (s_row & 1), and its stores
+    // DEFER: the row of step s_row out of its exchange row (s_row & 1), and its stores
     [[maybe_unused]] auto deferred_store = [&](int s_row) {
         const lds_ptr xl_r = xl_base + (s_row & 1) * kLkWaveLds + lane_off_var(l16);
         const f32x4 dlo = *(__attribute__((address_space(3))) f32x4 *)(xl_r);
@@ -407,18 +343,9 @@ __device__ __forceinline__ void lk_wave_buf(const LkTable &T, int wave, int lane
             const int po_in = row_off(yy + 2), po_out = row_off_out(ro);
             pf_ip = fetch_prev(po_in);
             pf_in = fetch_next(yy + 2, po_in);
-#ifndef OFX_X_NO_OUTROWS // (diagnostic builds, profiles/r04_ablation.txt batch 6: which loads the launch's fabric reads belong to)
-            if (RING && s >= NS - 3) {
-                // the leaving row entered NS steps ago (or with the priming rows): its finished dwords wait in the ring
-                const u32x2 q = *(const __attribute__((address_space(3))) u32x2 *)(ring_at(rslot));
-                pf_op = q.x;
-                pf_on.sh = q.y;
-            } else {
-                pf_op = fetch_prev(po_out);
-                // (a row of the leaving window before y_first - 1 is never used and may lie below the table: its pixels are zeros)
-                if (ro >= y_first - 1) pf_on = fetch_next(ro, po_out);
-            }
-#endif
+            pf_op = fetch_prev(po_out);
+            // (a row of the leaving window before y_first - 1 is never used and may lie below the table: its pixels are zeros)
+            if (ro >= y_first - 1) pf_on = fetch_next(ro, po_out);
         }
         const bool emit = s >= PR;
         // ACC: the flow this row adds to, as it lies (this lane's 4 pixels), fetched with the step's rows
@@ -427,26 +354,13 @@ __device__ __forceinline__ void lk_wave_buf(const LkTable &T, int wave, int lane
             asm("" : "=v"(old_a), "=v"(old_b));
             if (emit) {
                 const int fnat = __builtin_amdgcn_readfirstlane(fso0 + (s - PR) * fstep - x0 * 8); // offset of the row's pixel 0
-                // (OFX_LK_ACC_LOAD_AUX: cache-policy bits of the old flow's loads.  2 = nt -- "read once, do not displace the image rows the
-                // trailing window re-reads" -- measured 20 % SLOWER at 4K / 5 iterations: 554 vs 457 us, profiles/r04_ablation.txt batch 4)
-#ifdef OFX_X_NO_OLDFLOW
-                old_a = old_b = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-                if (false)
-#endif
-                if constexpr (INTERIOR && OFX_LK_ACC_XLOAD) {
-                    // the old flow in the EXCHANGED layout, as the stores write it: each of the two loads covers 1 KB without gaps
-                    // (in place, a lane's two 16-byte halves make every instruction touch all sixteen lines of the row and use half of
-                    // each).  Put back in place through the exchange row right before the add.
-                    const int fx = __builtin_amdgcn_readfirstlane(fso0 + (s - PR) * fstep);
-                    old_a = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_flow, lane_off_var(l16), fx, OFX_LK_ACC_LOAD_AUX));
-                    old_b = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_flow, vo_hi, fx, OFX_LK_ACC_LOAD_AUX));
-                } else if constexpr (INTERIOR) {
-                    old_a = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_flow, nat_off, fnat, OFX_LK_ACC_LOAD_AUX));
-                    old_b = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_flow, nat_off + 16u, fnat, OFX_LK_ACC_LOAD_AUX));
+                if constexpr (INTERIOR) {
+                    old_a = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_flow, nat_off, fnat, 0));
+                    old_b = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_flow, nat_off + 16u, fnat, 0));
                 } else { // (per pixel: a level of odd width ends inside a 16-byte piece)
                     auto off = [&](int j) { return ((bmask >> (8 * j)) & 1u) ? nat_off + 8u * (uint32_t)j : (uint32_t)kOob; };
-                    const u32x2 p0 = __builtin_amdgcn_raw_buffer_load_b64(rs_flow, off(0), fnat, OFX_LK_ACC_LOAD_AUX), p1 = __builtin_amdgcn_raw_buffer_load_b64(rs_flow, off(1), fnat, OFX_LK_ACC_LOAD_AUX);
-                    const u32x2 p2 = __builtin_amdgcn_raw_buffer_load_b64(rs_flow, off(2), fnat, OFX_LK_ACC_LOAD_AUX), p3 = __builtin_amdgcn_raw_buffer_load_b64(rs_flow, off(3), fnat, OFX_LK_ACC_LOAD_AUX);
+                    const u32x2 p0 = __builtin_amdgcn_raw_buffer_load_b64(rs_flow, off(0), fnat, 0), p1 = __builtin_amdgcn_raw_buffer_load_b64(rs_flow, off(1), fnat, 0);
+                    const u32x2 p2 = __builtin_amdgcn_raw_buffer_load_b64(rs_flow, off(2), fnat, 0), p3 = __builtin_amdgcn_raw_buffer_load_b64(rs_flow, off(3), fnat, 0);
                     old_a = __builtin_bit_cast(f32x4, u32x4{p0.x, p0.y, p1.x, p1.y});
                     old_b = __builtin_bit_cast(f32x4, u32x4{p2.x, p2.y, p3.x, p3.y});
                 }
@@ -489,17 +403,7 @@ __device__ __forceinline__ void lk_wave_buf(const LkTable &T, int wave, int lane
                 if (__builtin_expect(!all_in, 0)) o_n = row(4), o_no = row(5);
                 unpack_pk(finish_row(a_p), take_one(yy + 2, false, a_n, o_n), finish_row(a_po), take_one(ro, true, a_no, o_no), wp[k]);
             } else {
-                if constexpr (RING) {
-                    const uint32_t p_in = finish_row(pf_ip), n_in = finish_next(pf_in);
-                    uint32_t p_out, n_out;
-                    if (s >= NS - 3) p_out = pf_op, n_out = pf_on.sh;
-                    else p_out = finish_row(pf_op), n_out = finish_next(pf_on);
-                    unpack_pk(p_in, n_in, p_out, n_out, wp[k]);
-                    *(__attribute__((address_space(3))) u32x2 *)(ring_at(rslot)) = u32x2{p_in, n_in};
-                    rslot = rslot + 1 == NS ? 0 : rslot + 1;
-                } else {
-                    unpack_pk(finish_row(pf_ip), finish_next(pf_in), finish_row(pf_op), finish_next(pf_on), wp[k]);
-                }
+                unpack_pk(finish_row(pf_ip), finish_next(pf_in), finish_row(pf_op), finish_next(pf_on), wp[k]);
             }
             pin_row(wp[k]);
         };
@@ -508,7 +412,6 @@ __device__ __forceinline__ void lk_wave_buf(const LkTable &T, int wave, int lane
         asm("" : "=v"(xlo), "=v"(xhi));
         if (emit) {
             float uv[8];
-#if OFX_LK_HBOX_LOCKSTEP
             // the five box sums stage by stage (hbox4x5): no wait states between the dependent DPP operations of one quantity
             int hb[5][4];
             {
@@ -518,37 +421,7 @@ __device__ __forceinline__ void lk_wave_buf(const LkTable &T, int wave, int lane
                 hbox4x5<R>(va, hb);
             }
             const int(&hxx)[4] = hb[0], (&hyy)[4] = hb[1], (&hxy)[4] = hb[2], (&hxt)[4] = hb[3], (&hyt)[4] = hb[4];
-#else
-            int hxx[4], hyy[4], hxy[4], hxt[4], hyt[4];
-            hbox4<R>(vxx, hxx);
-            hbox4<R>(vyy, hyy);
-            hbox4<R>(vxy, hxy);
-            hbox4<R>(vxt, hxt);
-            hbox4<R>(vyt, hyt);
-#endif
-#ifdef OFX_X_NOSOLVE // timing experiment (results wrong by construction)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                uv[2 * j] = __int_as_float(hxx[j] ^ hxy[j] ^ hxt[j]);
-                uv[2 * j + 1] = __int_as_float(hyy[j] ^ hyt[j]);
-            }
-#else
             solve_lane<MODE, FAST>(hxx, hyy, hxy, hxt, hyt, sopt, uv);
-#endif
-            if constexpr (ACC && INTERIOR && OFX_LK_ACC_XLOAD) {
-                // chunks l and l + 64 of the row -> this lane's own 32 bytes (the inverse of the exchange in front of the stores; the
-                // halo lanes, whose pixels are never stored, get whatever the row held).  A wave's LDS operations execute in order.
-                const lds_ptr xr = DEFER ? (lds_ptr)xlds + (s & 1) * kLkWaveLds : (lds_ptr)xlds;
-                const lds_ptr xq = xr + 32 * G::LO_LANE + lane_off_var(l16);
-                *(__attribute__((address_space(3))) f32x4 *)(xq) = old_a;
-                *(__attribute__((address_space(3))) f32x4 *)(xq + 1024) = old_b;
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                old_a = *(__attribute__((address_space(3))) f32x4 *)(xr + 32 * lane);
-                old_b = *(__attribute__((address_space(3))) f32x4 *)(xr + 32 * lane + 16);
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-            }
             if constexpr (ACC) { // (the old flow is zero in the columns outside the image, which are never stored)
                 uv[0] = old_a.x + uv[0], uv[1] = old_a.y + uv[1], uv[2] = old_a.z + uv[2], uv[3] = old_a.w + uv[3];
                 uv[4] = old_b.x + uv[4], uv[5] = old_b.y + uv[5], uv[6] = old_b.z + uv[6], uv[7] = old_b.w + uv[7];
@@ -559,11 +432,7 @@ __device__ __forceinline__ void lk_wave_buf(const LkTable &T, int wave, int lane
                 const int yw = yy - R; // this step's output row
                 const uint32_t wn = warp_row_finish(WM);
                 const int wso = __builtin_amdgcn_readfirstlane(s > PR ? (yw - 1 - A.row0) * A.pitch : kOob);
-#ifdef OFX_X_NO_WSTORE
-                asm volatile("" : : "v"(wn), "s"(wso));
-#else
                 __builtin_amdgcn_raw_buffer_store_b32(wn, rs_wout, wvo, wso, 0);
-#endif
                 const float fu[4] = {uv[0], uv[2], uv[4], uv[6]}, fv[4] = {uv[1], uv[3], uv[5], uv[7]};
                 warp_row_prepare<ROWWIN>(rs_wsrc, A.warp_scale, A.w, A.h, A.pitch, A.row0, A.row_end, cb, yw, wnpx, fu, fv, WM, wmiss);
             }
@@ -584,18 +453,8 @@ __device__ __forceinline__ void lk_wave_buf(const LkTable &T, int wave, int lane
         }
     };
 
-#if OFX_LK_PROGRESS_PRIORITY
     const int q1 = nsteps / 4, q2 = nsteps / 2, q3 = nsteps - nsteps / 4;
     __builtin_amdgcn_s_setprio(3);
-#define OFX_LK_PRIO_STEP()                               \
-    do {                                                 \
-        if (s >= q3) __builtin_amdgcn_s_setprio(0);      \
-        else if (s >= q2) __builtin_amdgcn_s_setprio(1); \
-        else if (s >= q1) __builtin_amdgcn_s_setprio(2); \
-    } while (0)
-#else
-#define OFX_LK_PRIO_STEP() ((void)0)
-#endif
     int s = 0;
     while (true) {
         body(std::integral_constant<int, 0>{}, s);
@@ -606,7 +465,6 @@ __device__ __forceinline__ void lk_wave_buf(const LkTable &T, int wave, int lane
         if (++s >= nsteps) break;
         OFX_LK_PRIO_STEP();
     }
-#undef OFX_LK_PRIO_STEP
     if constexpr (DEFER) {
         if (nsteps > PR) deferred_store(nsteps - 1); // the last row
     }

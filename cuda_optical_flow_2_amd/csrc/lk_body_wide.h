@@ -34,6 +34,7 @@ static_assert(TileGeomW<4, 4>::LO_LANE == TileGeom<4>::LO_LANE && TileGeomW<4, 4
 static_assert(TileGeomW<11, 4>::OUT_W == TileGeom<11>::OUT_W, "TileGeomW<R, 4> is TileGeom<R>");
 
 constexpr int kLkWaveLdsW = 64 * 64 + 256; // one row of a wide wave (64 lanes x 8 pixels x 8 bytes) + the reads past its valid end
+static_assert(kLkWaveLdsW == 4352, "LDS per wave of the wide march (the host sizes the dynamic LDS with it)");
 
 // one image row of a lane's NC columns for both marching windows (lo halves: entering, hi: leaving): p = prev, q = next - prev
 // (lk_float) or next (compat_cpu)
@@ -522,7 +523,7 @@ __device__ __forceinline__ void lk_wave_wide(const LkTable &T, int wave, int lan
         finish_next(fetch_next(y, po), n);
     };
 
-    constexpr int H = OFX_LK_FOLD_PRIMING ? R - 1 : 0;
+    constexpr int H = R - 1;
     constexpr int PR = 2 * R - H;
     const int y_lo0 = y_first + H;
     const int nsteps = (ye - ys) + PR;
@@ -656,29 +657,19 @@ __device__ __forceinline__ void lk_wave_wide(const LkTable &T, int wave, int lan
             const int fso = __builtin_amdgcn_readfirstlane(fso0 + (s - PR) * fstep); // this row's offset in the flow
             // four gap-free streaming stores of 1 KB; the lanes past the tile's end are dropped by the resource's range check
 #pragma unroll
-            for (int i = 0; i < 4; ++i) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, xo[i]), rs_flow, vo[i], fso, OFX_LK_STORE_AUX);
+            for (int i = 0; i < 4; ++i) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, xo[i]), rs_flow, vo[i], fso, kLkStoreAux);
             if (__builtin_expect(ragged, 0)) { // the one lane whose chunk holds a single pixel
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const u32x4 qv = __builtin_bit_cast(u32x4, xo[i]);
-                    __builtin_amdgcn_raw_buffer_store_b64(u32x2{qv.x, qv.y}, rs_flow, st2[i] ? l16 + 1024u * (uint32_t)i : (uint32_t)kOob, fso, OFX_LK_STORE_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b64(u32x2{qv.x, qv.y}, rs_flow, st2[i] ? l16 + 1024u * (uint32_t)i : (uint32_t)kOob, fso, kLkStoreAux);
                 }
             }
         }
     };
 
-#if OFX_LK_PROGRESS_PRIORITY
     const int q1 = nsteps / 4, q2 = nsteps / 2, q3 = nsteps - nsteps / 4;
     __builtin_amdgcn_s_setprio(3);
-#define OFX_LK_PRIO_STEP()                               \
-    do {                                                 \
-        if (s >= q3) __builtin_amdgcn_s_setprio(0);      \
-        else if (s >= q2) __builtin_amdgcn_s_setprio(1); \
-        else if (s >= q1) __builtin_amdgcn_s_setprio(2); \
-    } while (0)
-#else
-#define OFX_LK_PRIO_STEP() ((void)0)
-#endif
     int s = 0;
     while (true) {
         body(std::integral_constant<int, 0>{}, s);
@@ -689,7 +680,6 @@ __device__ __forceinline__ void lk_wave_wide(const LkTable &T, int wave, int lan
         if (++s >= nsteps) break;
         OFX_LK_PRIO_STEP();
     }
-#undef OFX_LK_PRIO_STEP
     if constexpr (WOUT) { // the warped row of the last step
 #pragma unroll
         for (int g = 0; g < NG; ++g) {

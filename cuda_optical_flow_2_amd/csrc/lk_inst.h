@@ -1,0 +1,56 @@
+// The launch families declared in lk_launch.h, defined: included by the lk_inst_*.hip translation units only, each of which
+// instantiates one of them explicitly (and with it the family's kernels, radii 1..11 or 12).
+#pragma once
+
+#include "lk_launch.h"
+
+namespace ofx_launch {
+
+template <int MODE, bool FAST>
+int levels(int radius, const LkLevelIn *lv, int n, bool sums, hipStream_t st)
+{
+    int rc = OFX_E_UNSUPPORTED;
+    const bool known = dispatch_radius<lk_max_radius(MODE)>(radius, [&](auto R) {
+        if constexpr (!FAST) {
+            if (sums) {
+                rc = launch_r<decltype(R)::value, MODE, true, false>(lv, n, st);
+                return;
+            }
+        }
+        rc = launch_r<decltype(R)::value, MODE, false, FAST>(lv, n, st);
+    });
+    if (!known) ofx_set_error("ofx_lk_level: window %d not supported in mode %d", 2 * radius + 1, MODE);
+    return rc;
+}
+
+template <int MODE, bool FAST, int ITER, int NC>
+int iter(int radius, const LkLevelIn *lv, int n, hipStream_t st)
+{
+    int rc = OFX_E_UNSUPPORTED;
+    const bool known = dispatch_radius<lk_max_radius(MODE, NC)>(radius, [&](auto R) {
+        if constexpr (NC == 8) rc = launch_iter_rd<decltype(R)::value, MODE, FAST, ITER, false, 8>(lv, n, st);
+        else rc = launch_iter_r<decltype(R)::value, MODE, FAST, ITER>(lv, n, st);
+    });
+    if (!known) {
+        if constexpr (NC == 8) ofx_set_error("ofx_lk_levels: window %d not supported with eight columns per lane", 2 * radius + 1);
+        else ofx_set_error("ofx_lk_level: window %d not supported in mode %d", 2 * radius + 1, MODE);
+    }
+    return rc;
+}
+
+template <int MODE, bool FAST, int WOUT, int NC>
+int stream(int radius, const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st)
+{
+    int rc = OFX_E_UNSUPPORTED;
+    const bool known = dispatch_radius<lk_max_radius(MODE, NC)>(radius, [&](auto R) {
+        if constexpr (NC == 8) rc = launch_stream_rd<decltype(R)::value, MODE, FAST, false, WOUT, 8>(lv, n, S, stage_blocks, lds, st);
+        else rc = launch_stream_r<decltype(R)::value, MODE, FAST, WOUT>(lv, n, S, stage_blocks, lds, st);
+    });
+    if (!known) {
+        if constexpr (NC == 8) ofx_set_error("ofx_stream_launch: window %d not supported with eight columns per lane", 2 * radius + 1);
+        else ofx_set_error("ofx_stream_launch: window %d not supported in mode %d", 2 * radius + 1, MODE);
+    }
+    return rc;
+}
+
+} // namespace ofx_launch

@@ -1,8 +1,4 @@
 // One family of instantiations of the templates in lk_launch.h (see there): refinement iterations on the buffer march, ITER = 1.
-#include "lk_launch.h"
+#include "lk_inst.h"
 
-namespace ofx_launch {
-
-int iter1_lk_float_fast(int radius, const LkLevelIn *lv, int n, hipStream_t st) { return launch_iter_mode<OFX_MODE_LK_FLOAT, true, 1>(radius, lv, n, st); }
-
-} // namespace ofx_launch
+template int ofx_launch::iter<OFX_MODE_LK_FLOAT, true, 1>(int, const LkLevelIn *, int, hipStream_t);

@@ -1,11 +1,4 @@
 // One family of instantiations of the templates in lk_launch.h (see there).
-#include "lk_launch.h"
+#include "lk_inst.h"
 
-namespace ofx_launch {
-
-int stream_lk_float(int radius, const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st)
-{
-    return launch_stream_mode<OFX_MODE_LK_FLOAT, false>(radius, lv, n, S, stage_blocks, lds, st);
-}
-
-} // namespace ofx_launch
+template int ofx_launch::stream<OFX_MODE_LK_FLOAT, false>(int, const LkLevelIn *, int, StreamArgs &, const int *, size_t, hipStream_t);

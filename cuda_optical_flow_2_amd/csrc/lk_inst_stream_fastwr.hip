@@ -1,12 +1,5 @@
 // One family of instantiations of the templates in lk_launch.h (see there): the stream tick whose LK stage also writes the
 // warped images of its pairs' second refinement iteration (lk_wave_buf's ITER = 5: on the row windows of a shard).
-#include "lk_launch.h"
+#include "lk_inst.h"
 
-namespace ofx_launch {
-
-int stream_lk_float_fast_wout_rw(int radius, const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st)
-{
-    return launch_stream_mode<OFX_MODE_LK_FLOAT, true, 5>(radius, lv, n, S, stage_blocks, lds, st);
-}
-
-} // namespace ofx_launch
+template int ofx_launch::stream<OFX_MODE_LK_FLOAT, true, 5>(int, const LkLevelIn *, int, StreamArgs &, const int *, size_t, hipStream_t);

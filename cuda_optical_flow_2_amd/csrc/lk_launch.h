@@ -1,6 +1,7 @@
 // Kernels, planner and launchers of the fused level kernel and of the stream kernel, as templates: included by lk_level.hip
-// (entry points, argument checks) and by the lk_inst_*.hip translation units, each of which instantiates one (mode, solve)
-// family -- the radii 1..12 of a family are ~90 s of hipcc on one core, six families in parallel are ~40 s.
+// (entry points, argument checks) and, through lk_inst.h, by the lk_inst_*.hip translation units, each of which instantiates one
+// family (declared at the end of this file) -- the radii 1..12 of a family are ~90 s of hipcc on one core, six families in
+// parallel are ~40 s.
 #pragma once
 
 #include <stdio.h>
@@ -42,12 +43,9 @@ struct LkLevelIn {
 
 namespace {
 
-
-#ifndef OFX_LK_MIN_WAVES
-#define OFX_LK_MIN_WAVES(R) 3 // A/B on MI355X: capping at 128 VGPRs (4 waves) spills in the marching loop and is slower
-#endif
+constexpr int kLkMinWaves = 3; // A/B on MI355X: capping at 128 VGPRs (4 waves) spills in the marching loop and is slower
 template <int R, int MODE, bool SUMS, bool FAST>
-__global__ __launch_bounds__(64, OFX_LK_MIN_WAVES(R)) void lk_level_kernel(const LkTable T)
+__global__ __launch_bounds__(64, kLkMinWaves) void lk_level_kernel(const LkTable T)
 {
     __shared__ __attribute__((aligned(16))) uint8_t xlds[kLkWaveLds];
     lk_wave<R, MODE, SUMS, true, FAST>(T, (int)blockIdx.x, (int)threadIdx.x, xlds);
@@ -58,19 +56,12 @@ __global__ __launch_bounds__(64, OFX_LK_MIN_WAVES(R)) void lk_level_kernel(const
 // ITER = 2 needs 126 VGPRs in interior tiles and 130 in the tiles at the image's left and right edge (128 for 9x9: four waves per
 // SIMD, three for the other windows).  Capping it at 128 everywhere spills 2-8 registers and measured 1-3 % slower at 1080p, 4K
 // and 8K (profiles/r03_ablation.txt), so the cap stays at three waves.
-#ifndef OFX_ITER_MIN_WAVES
-#define OFX_ITER_MIN_WAVES(ITER) 3
-#endif
 // DMA: the rows are fetched two steps ahead through LDS (lk_body_buf.h; chosen per launch as for the stream kernel)
-// NC = 8: the march with eight columns per lane (lk_body_wide.h; no deep fetch)
-#ifndef OFX_WIDE_ITER_MIN_WAVES
-#define OFX_WIDE_ITER_MIN_WAVES 2
-#endif
+// NC = 8: the march with eight columns per lane (lk_body_wide.h; no deep fetch): two waves per SIMD
 template <int R, int MODE, bool FAST, int ITER, bool DMA = false, int NC = 4>
-// (with the LDS ring of the leaving rows the accumulating launches fit 128 VGPRs without scratch for R <= 7: four waves per SIMD)
-__global__ __launch_bounds__(64, NC == 8 ? OFX_WIDE_ITER_MIN_WAVES : (lk_out_ring<R, ITER, DMA>() && R <= 7 ? 4 : OFX_ITER_MIN_WAVES(ITER))) void lk_iter_kernel(const LkTable T)
+__global__ __launch_bounds__(64, NC == 8 ? 2 : 3) void lk_iter_kernel(const LkTable T)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t xlds[NC == 8 ? kLkWaveLdsW : (DMA ? kLkWaveLdsDma : kLkWaveLdsX + lk_ring_bytes<R, ITER, DMA>())];
+    __shared__ __attribute__((aligned(16))) uint8_t xlds[NC == 8 ? kLkWaveLdsW : (DMA ? kLkWaveLdsDma : kLkWaveLdsX)];
     const int wave = (int)blockIdx.x, lane = (int)threadIdx.x;
     if constexpr (NC == 8) {
         static_assert(!DMA, "the wide march has no deep fetch");
@@ -113,22 +104,18 @@ using ofx_launch::g_stream_trace_blocks;
 using ofx_launch::g_trace_header;
 using ofx_launch::g_stream_deep_fetch;
 
-// lk_float fits 5 blocks per CU (<= 96 VGPRs) without scratch for every radius; compat_cpu needs ~120: 4 blocks (<= 128)
-#ifndef OFX_PYR_PRIO
-#define OFX_PYR_PRIO 3 // priority of the marching-pyramid waves next to the LK waves (which go 3 -> 0 along their strips)
-#endif
-#ifndef OFX_STREAM_MIN_BLOCKS
-#define OFX_STREAM_MIN_BLOCKS(R, MODE) ((MODE) == OFX_MODE_LK_FLOAT ? 5 : 4)
-#endif
+constexpr int kPyrPrio = 3; // priority of the marching-pyramid waves next to the LK waves (which go 3 -> 0 along their strips)
 // DMA: the LK stage fetches its rows two steps ahead through LDS (lk_body_buf.h); chosen per launch by launch_stream_r
 // WOUT: the LK stage is iteration 1 of pairs that have more (lk_iter): it also writes the warped images of their second iteration
 // (lk_body_buf.h, ITER = WOUT = 3, or 5 on the row windows of a shard; ~128 VGPRs: three blocks per CU at least); 0: it does not
-// NC = 8: the LK stage marches with eight columns per lane (lk_body_wide.h): ~170 VGPRs, OFX_WIDE_MIN_BLOCKS blocks per CU
-#ifndef OFX_WIDE_MIN_BLOCKS
-#define OFX_WIDE_MIN_BLOCKS 3
-#endif
+// NC = 8: the LK stage marches with eight columns per lane (lk_body_wide.h): ~170 VGPRs, three blocks per CU (two with WOUT)
+// blocks per CU: lk_float fits 5 (<= 96 VGPRs) without scratch for every radius; compat_cpu needs ~120: 4 blocks (<= 128)
+constexpr int stream_min_blocks(int mode, int wout, int nc)
+{
+    return nc == 8 ? (wout ? 2 : 3) : (wout ? 3 : (mode == OFX_MODE_LK_FLOAT ? 5 : 4));
+}
 template <int R, int MODE, bool FAST, bool DMA, int WOUT = 0, int NC = 4>
-__global__ __launch_bounds__(256, NC == 8 ? (WOUT ? 2 : OFX_WIDE_MIN_BLOCKS) : (WOUT ? 3 : OFX_STREAM_MIN_BLOCKS(R, MODE))) void stream_kernel(const StreamArgs S)
+__global__ __launch_bounds__(256, stream_min_blocks(MODE, WOUT, NC)) void stream_kernel(const StreamArgs S)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
@@ -155,7 +142,7 @@ __global__ __launch_bounds__(256, NC == 8 ? (WOUT ? 2 : OFX_WIDE_MIN_BLOCKS) : (
     } else {
         int i = 0;
         while (i + 1 < kPyrStages && b >= S.first[i + 1]) ++i;
-        __builtin_amdgcn_s_setprio(OFX_PYR_PRIO);
+        __builtin_amdgcn_s_setprio(kPyrPrio);
         pyr_march_wave(S.pyr[i], 4 * (b - S.first[i]) + wv, tid & 63);
     }
     if (S.trace && b < S.trace_blocks && (tid & 63) == 0) { // one record per wave: 4 per block
@@ -181,64 +168,23 @@ int env_int(const char *name, int dflt)
 // `capacity` (lk_wave_target), but at least `min_h` so the 2R priming rows of a strip stay a minor cost.
 // The grid is sized to fit in ONE residency round: every wave runs for the whole kernel, so a second, partly filled
 // round would nearly double the run time.
-// Age skew (OFX_LK_SKEW="p0,p1,p2,p3", per cent): a SIMD serves its waves oldest first, and a wave's age rank on its SIMD is the
-// quartile of its block index (every CU receives one block of each quartile in turn).  The strips of the items in quartile q are
-// cut skew[q] per cent of the common height, so that the waves served first carry more rows.  Exact integer sums: the result
-// does not depend on where the strips are cut.
-inline const double *lk_skew()
-{
-    static double sk[4] = {1.0, 1.0, 1.0, 1.0};
-    static const bool init = [] {
-        const char *e = getenv("OFX_LK_SKEW");
-        int v[4];
-        if (e && sscanf(e, "%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3]) == 4)
-            for (int i = 0; i < 4; ++i) sk[i] = v[i] > 10 ? v[i] / 100.0 : 1.0;
-        return true;
-    }();
-    (void)init;
-    return sk;
-}
-
 template <int R, int NC = 4>
 int plan_table(const LkLevelIn *lv, int n, int capacity, LkTable *out)
 {
     using G = TileGeomW<R, NC>; // (NC = 4: TileGeom<R>)
     const int min_h = env_int("OFX_LK_MIN_STRIP", 8);
-    const double *skew = lk_skew();
-    const bool skewed = skew[0] != 1.0 || skew[1] != 1.0 || skew[2] != 1.0 || skew[3] != 1.0;
     int max_rows = 1;
     for (int i = 0; i < n; ++i) max_rows = lv[i].rows_out > max_rows ? lv[i].rows_out : max_rows;
-    int quart[OFX_MAX_LK_ITEMS] = {0};
     auto height = [&](int i, int H) {
-        int hi = skewed ? (int)(H * skew[quart[i]] + 0.5) : H;
-        hi = hi < min_h ? min_h : hi;
+        const int hi = H < min_h ? min_h : H;
         return hi < lv[i].rows_out ? hi : lv[i].rows_out;
     };
     auto item_waves = [&](int i, int H) { return (long)ofx_div_up(lv[i].a.w, G::OUT_W) * ofx_div_up(lv[i].rows_out, height(i, H)); };
-    auto solve_h = [&]() {
-        int H = min_h;
-        for (; H < max_rows; ++H) {
-            long waves = 0;
-            for (int i = 0; i < n; ++i) waves += item_waves(i, H);
-            if (waves <= (long)capacity) break;
-        }
-        return H;
-    };
-    int strip_h = solve_h();
-    if (skewed) { // the quartile of an item = where the middle of its block range falls; two rounds settle it
-        for (int round = 0; round < 2; ++round) {
-            long total = 0, pos = 0;
-            for (int i = 0; i < n; ++i) total += item_waves(i, strip_h);
-            int q_new[OFX_MAX_LK_ITEMS];
-            for (int i = 0; i < n; ++i) {
-                const long wv = item_waves(i, strip_h);
-                const int q = (int)((4 * (2 * pos + wv)) / (2 * (total > 0 ? total : 1)));
-                q_new[i] = q < 0 ? 0 : (q > 3 ? 3 : q);
-                pos += wv;
-            }
-            for (int i = 0; i < n; ++i) quart[i] = q_new[i];
-            strip_h = solve_h();
-        }
+    int strip_h = min_h;
+    for (; strip_h < max_rows; ++strip_h) {
+        long waves = 0;
+        for (int i = 0; i < n; ++i) waves += item_waves(i, strip_h);
+        if (waves <= (long)capacity) break;
     }
     LkTable t{};
     t.n = n;
@@ -304,14 +250,12 @@ int launch_iter_rd(const LkLevelIn *lv, int n, hipStream_t st)
 template <int R, int MODE, bool FAST, int ITER>
 int launch_iter_r(const LkLevelIn *lv, int n, hipStream_t st)
 {
-#if OFX_LK_DMA_ROWS
     // the deep fetch, chosen as for the stream kernel (8K, 10 iterations: 15 380 vs 15 110 Mpix/s; 4K: no difference beyond the
     // +-1.5 % between runs -- profiles/r03_ablation.txt).  OFX_ITER_DMA=0 / 1 overrides.
     static const int forced = [] { const char *e = getenv("OFX_ITER_DMA"); return e ? atoi(e) : -1; }();
     long max_px = 0;
     for (int i = 0; i < n; ++i) max_px = (long)lv[i].a.w * lv[i].a.h > max_px ? (long)lv[i].a.w * lv[i].a.h : max_px;
     if (forced > 0 || (forced < 0 && max_px >= 16l * 1000 * 1000)) return launch_iter_rd<R, MODE, FAST, ITER, true>(lv, n, st);
-#endif
     return launch_iter_rd<R, MODE, FAST, ITER, false>(lv, n, st);
 }
 
@@ -352,53 +296,9 @@ int launch_stream_rd(const LkLevelIn *lv, int n, StreamArgs &S, const int *stage
     return OFX_OK;
 }
 
-// the same launches with eight columns per lane (one translation unit per family: lk_inst_*8.hip)
-template <int MODE, bool FAST, int WOUT = 0>
-int launch_stream_mode_w8(int radius, const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st)
-{
-    switch (radius) {
-    case 1: return launch_stream_rd<1, MODE, FAST, false, WOUT, 8>(lv, n, S, stage_blocks, lds, st);
-    case 2: return launch_stream_rd<2, MODE, FAST, false, WOUT, 8>(lv, n, S, stage_blocks, lds, st);
-    case 3: return launch_stream_rd<3, MODE, FAST, false, WOUT, 8>(lv, n, S, stage_blocks, lds, st);
-    case 4: return launch_stream_rd<4, MODE, FAST, false, WOUT, 8>(lv, n, S, stage_blocks, lds, st);
-    case 5: return launch_stream_rd<5, MODE, FAST, false, WOUT, 8>(lv, n, S, stage_blocks, lds, st);
-    case 6: return launch_stream_rd<6, MODE, FAST, false, WOUT, 8>(lv, n, S, stage_blocks, lds, st);
-    case 7: return launch_stream_rd<7, MODE, FAST, false, WOUT, 8>(lv, n, S, stage_blocks, lds, st);
-    case 8: return launch_stream_rd<8, MODE, FAST, false, WOUT, 8>(lv, n, S, stage_blocks, lds, st);
-    case 9: return launch_stream_rd<9, MODE, FAST, false, WOUT, 8>(lv, n, S, stage_blocks, lds, st);
-    case 10: return launch_stream_rd<10, MODE, FAST, false, WOUT, 8>(lv, n, S, stage_blocks, lds, st);
-    case 11: return launch_stream_rd<11, MODE, FAST, false, WOUT, 8>(lv, n, S, stage_blocks, lds, st);
-    default: break;
-    }
-    ofx_set_error("ofx_stream_launch: window %d not supported with eight columns per lane", 2 * radius + 1);
-    return OFX_E_UNSUPPORTED;
-}
-
-template <int MODE, bool FAST, int ITER>
-int launch_iter_mode_w8(int radius, const LkLevelIn *lv, int n, hipStream_t st)
-{
-    switch (radius) {
-    case 1: return launch_iter_rd<1, MODE, FAST, ITER, false, 8>(lv, n, st);
-    case 2: return launch_iter_rd<2, MODE, FAST, ITER, false, 8>(lv, n, st);
-    case 3: return launch_iter_rd<3, MODE, FAST, ITER, false, 8>(lv, n, st);
-    case 4: return launch_iter_rd<4, MODE, FAST, ITER, false, 8>(lv, n, st);
-    case 5: return launch_iter_rd<5, MODE, FAST, ITER, false, 8>(lv, n, st);
-    case 6: return launch_iter_rd<6, MODE, FAST, ITER, false, 8>(lv, n, st);
-    case 7: return launch_iter_rd<7, MODE, FAST, ITER, false, 8>(lv, n, st);
-    case 8: return launch_iter_rd<8, MODE, FAST, ITER, false, 8>(lv, n, st);
-    case 9: return launch_iter_rd<9, MODE, FAST, ITER, false, 8>(lv, n, st);
-    case 10: return launch_iter_rd<10, MODE, FAST, ITER, false, 8>(lv, n, st);
-    case 11: return launch_iter_rd<11, MODE, FAST, ITER, false, 8>(lv, n, st);
-    default: break;
-    }
-    ofx_set_error("ofx_lk_levels: window %d not supported with eight columns per lane", 2 * radius + 1);
-    return OFX_E_UNSUPPORTED;
-}
-
 template <int R, int MODE, bool FAST, int WOUT>
 int launch_stream_r(const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st)
 {
-#if OFX_LK_BUFFER_PATH && OFX_LK_DMA_ROWS
     if constexpr (!WOUT) { // (a tick that also writes warped images measured slower with it: 8K 440 vs 416 us)
         static const int forced = [] { const char *e = getenv("OFX_LK_DMA"); return e ? atoi(e) : -1; }();
         long max_px = 0;
@@ -409,110 +309,41 @@ int launch_stream_r(const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_
         const int want = forced >= 0 ? (forced > 0 ? 1 : -1) : g_stream_deep_fetch;
         if (want > 0 || (want == 0 && max_px >= 16l * 1000 * 1000)) return launch_stream_rd<R, MODE, FAST, true, WOUT>(lv, n, S, stage_blocks, lds, st);
     }
-#endif
     return launch_stream_rd<R, MODE, FAST, false, WOUT>(lv, n, S, stage_blocks, lds, st);
 }
 
-template <int MODE, bool FAST, int WOUT = 0>
-int launch_stream_mode(int radius, const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st)
+// Calls f(std::integral_constant<int, R>{}) for R = radius when 1 <= radius <= MAX_R (which instantiates f for every such R);
+// false: the radius is outside that range and f was not called.
+template <int MAX_R, int R = 1, typename F>
+bool dispatch_radius(int radius, F &&f)
 {
-    switch (radius) {
-    case 1: return launch_stream_r<1, MODE, FAST, WOUT>(lv, n, S, stage_blocks, lds, st);
-    case 2: return launch_stream_r<2, MODE, FAST, WOUT>(lv, n, S, stage_blocks, lds, st);
-    case 3: return launch_stream_r<3, MODE, FAST, WOUT>(lv, n, S, stage_blocks, lds, st);
-    case 4: return launch_stream_r<4, MODE, FAST, WOUT>(lv, n, S, stage_blocks, lds, st);
-    case 5: return launch_stream_r<5, MODE, FAST, WOUT>(lv, n, S, stage_blocks, lds, st);
-    case 6: return launch_stream_r<6, MODE, FAST, WOUT>(lv, n, S, stage_blocks, lds, st);
-    case 7: return launch_stream_r<7, MODE, FAST, WOUT>(lv, n, S, stage_blocks, lds, st);
-    case 8: return launch_stream_r<8, MODE, FAST, WOUT>(lv, n, S, stage_blocks, lds, st);
-    case 9: return launch_stream_r<9, MODE, FAST, WOUT>(lv, n, S, stage_blocks, lds, st);
-    case 10: return launch_stream_r<10, MODE, FAST, WOUT>(lv, n, S, stage_blocks, lds, st);
-    case 11: return launch_stream_r<11, MODE, FAST, WOUT>(lv, n, S, stage_blocks, lds, st);
-    default: break;
+    if constexpr (R <= MAX_R) {
+        if (radius == R) {
+            f(std::integral_constant<int, R>{});
+            return true;
+        }
+        return dispatch_radius<MAX_R, R + 1>(radius, f);
+    } else {
+        return false;
     }
-    if constexpr (MODE == OFX_MODE_COMPAT_CPU) {
-        if (radius == 12) return launch_stream_r<12, MODE, FAST, WOUT>(lv, n, S, stage_blocks, lds, st);
-    }
-    ofx_set_error("ofx_stream_launch: window %d not supported in mode %d", 2 * radius + 1, MODE);
-    return OFX_E_UNSUPPORTED;
 }
-
-template <int MODE, bool FAST, int ITER>
-int launch_iter_mode(int radius, const LkLevelIn *lv, int n, hipStream_t st)
-{
-    switch (radius) {
-    case 1: return launch_iter_r<1, MODE, FAST, ITER>(lv, n, st);
-    case 2: return launch_iter_r<2, MODE, FAST, ITER>(lv, n, st);
-    case 3: return launch_iter_r<3, MODE, FAST, ITER>(lv, n, st);
-    case 4: return launch_iter_r<4, MODE, FAST, ITER>(lv, n, st);
-    case 5: return launch_iter_r<5, MODE, FAST, ITER>(lv, n, st);
-    case 6: return launch_iter_r<6, MODE, FAST, ITER>(lv, n, st);
-    case 7: return launch_iter_r<7, MODE, FAST, ITER>(lv, n, st);
-    case 8: return launch_iter_r<8, MODE, FAST, ITER>(lv, n, st);
-    case 9: return launch_iter_r<9, MODE, FAST, ITER>(lv, n, st);
-    case 10: return launch_iter_r<10, MODE, FAST, ITER>(lv, n, st);
-    case 11: return launch_iter_r<11, MODE, FAST, ITER>(lv, n, st);
-    default: break;
-    }
-    if constexpr (MODE == OFX_MODE_COMPAT_CPU) {
-        if (radius == 12) return launch_iter_r<12, MODE, FAST, ITER>(lv, n, st);
-    }
-    ofx_set_error("ofx_lk_level: window %d not supported in mode %d", 2 * radius + 1, MODE);
-    return OFX_E_UNSUPPORTED;
-}
-
-template <int MODE, bool SUMS, bool FAST>
-int launch_mode(int radius, const LkLevelIn *lv, int n, hipStream_t st)
-{
-    switch (radius) {
-    case 1: return launch_r<1, MODE, SUMS, FAST>(lv, n, st);
-    case 2: return launch_r<2, MODE, SUMS, FAST>(lv, n, st);
-    case 3: return launch_r<3, MODE, SUMS, FAST>(lv, n, st);
-    case 4: return launch_r<4, MODE, SUMS, FAST>(lv, n, st);
-    case 5: return launch_r<5, MODE, SUMS, FAST>(lv, n, st);
-    case 6: return launch_r<6, MODE, SUMS, FAST>(lv, n, st);
-    case 7: return launch_r<7, MODE, SUMS, FAST>(lv, n, st);
-    case 8: return launch_r<8, MODE, SUMS, FAST>(lv, n, st);
-    case 9: return launch_r<9, MODE, SUMS, FAST>(lv, n, st);
-    case 10: return launch_r<10, MODE, SUMS, FAST>(lv, n, st);
-    case 11: return launch_r<11, MODE, SUMS, FAST>(lv, n, st);
-    default: break;
-    }
-    if constexpr (MODE == OFX_MODE_COMPAT_CPU) {
-        if (radius == 12) return launch_r<12, MODE, SUMS, FAST>(lv, n, st);
-    }
-    ofx_set_error("ofx_lk_level: window %d not supported in mode %d", 2 * radius + 1, MODE);
-    return OFX_E_UNSUPPORTED;
-}
+constexpr int lk_max_radius(int mode, int nc = 4) { return mode == OFX_MODE_COMPAT_CPU && nc == 4 ? 12 : 11; } // windows up to 23x23 / 25x25
 
 } // namespace
 
-// One external function per family (defined in lk_inst_*.hip): all levels of a fused launch / one stream tick.
+// The families: lk_level.hip calls them, and each lk_inst_*.hip instantiates one explicitly (lk_inst.h holds the definitions), so
+// that the families compile in parallel.  The kernels stay internal to the unit that instantiates them.
 namespace ofx_launch {
-int levels_lk_float(int radius, const LkLevelIn *lv, int n, bool sums, hipStream_t st);
-int levels_lk_float_fast(int radius, const LkLevelIn *lv, int n, hipStream_t st);
-int levels_compat_cpu(int radius, const LkLevelIn *lv, int n, bool sums, hipStream_t st);
+// all levels of a fused launch (sums: the inspection variant, which does not depend on the solve: FAST = false only)
+template <int MODE, bool FAST>
+int levels(int radius, const LkLevelIn *lv, int n, bool sums, hipStream_t st);
 // refinement iterations on the buffer march (lk_wave_buf's ITER): 1 flow += result; 2 the launch also writes the next iteration's
-// warped images; 3 iteration 1 of pairs that have more: flow = result and the warped images of iteration 2
-// (one translation unit per ITER: lk_inst_iter_*.hip)
-int iter1_lk_float(int radius, const LkLevelIn *lv, int n, hipStream_t st);
-int iter2_lk_float(int radius, const LkLevelIn *lv, int n, hipStream_t st);
-int iter3_lk_float(int radius, const LkLevelIn *lv, int n, hipStream_t st);
-int iter1_lk_float_fast(int radius, const LkLevelIn *lv, int n, hipStream_t st);
-int iter2_lk_float_fast(int radius, const LkLevelIn *lv, int n, hipStream_t st);
-int iter3_lk_float_fast(int radius, const LkLevelIn *lv, int n, hipStream_t st);
-int iter4_lk_float(int radius, const LkLevelIn *lv, int n, hipStream_t st);      // (2 on the row windows of a shard)
-int iter4_lk_float_fast(int radius, const LkLevelIn *lv, int n, hipStream_t st);
-// a tick whose LK stage also writes the warped images of its pairs' second iteration
-int stream_lk_float_wout(int radius, const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st);
-int stream_lk_float_fast_wout(int radius, const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st);
-int stream_lk_float_wout_rw(int radius, const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st);      // (row windows)
-int stream_lk_float_fast_wout_rw(int radius, const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st);
-int stream_lk_float(int radius, const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st);
-int stream_lk_float_fast(int radius, const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st);
-int stream_compat_cpu(int radius, const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st);
-// eight columns per lane (lk_body_wide.h)
-int stream_lk_float_w8(int radius, const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st);
-int stream_lk_float_fast_w8(int radius, const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st);
-int levels_lk_float_w8(int radius, const LkLevelIn *lv, int n, hipStream_t st); // all levels of one pair (the pair-at-a-time path)
+// warped images; 3 iteration 1 of pairs that have more: flow = result and the warped images of iteration 2; 4: 2 on the row
+// windows of a shard.  NC = 8, ITER = 0: all levels of one pair with eight columns per lane (the pair-at-a-time path)
+template <int MODE, bool FAST, int ITER, int NC = 4>
+int iter(int radius, const LkLevelIn *lv, int n, hipStream_t st);
+// one stream tick.  WOUT = 3: its LK stage also writes the warped images of its pairs' second iteration (5: on row windows);
+// NC = 8: eight columns per lane (lk_body_wide.h)
+template <int MODE, bool FAST, int WOUT = 0, int NC = 4>
+int stream(int radius, const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st);
 } // namespace ofx_launch

@@ -91,6 +91,18 @@ int lk_build_levels(const ofx_lk_desc *d, int n, int window, int mode, int32_t *
     return OFX_OK;
 }
 
+// The buffer march addresses a level's planes and its flow rows through buffer resources with 32-bit offsets (lk_body_buf.h)
+bool fits_buffer_offsets(const LkArgs &a)
+{
+    return (long long)(a.row_end - a.row0) * a.pitch < (1ll << 31) && (long long)(a.out_y1 - a.flow_row0) * a.w * 8 < (1ll << 31);
+}
+bool fit_buffer_offsets(const LkLevelIn *lv, int m)
+{
+    for (int i = 0; i < m; ++i)
+        if (!fits_buffer_offsets(lv[i].a)) return false;
+    return true;
+}
+
 // Columns per lane of the LK march of a launch: 8 (lk_body_wide.h) or 4.  The wide march has no deep fetch, so launches that would
 // choose that (levels of 16 Mpx and more, launch_stream_r) keep four columns.  OFX_LK_COLS=4 / 8 overrides.
 #ifndef OFX_LK_COLS_DEFAULT
@@ -120,39 +132,35 @@ int lk_dispatch(const ofx_lk_desc *d, int n, int window, int mode, int32_t *d_su
     if ((lv[0].a.accumulate || lv[0].a.warp_out) && !d_sums) {
         // refinement iterations run on the buffer march (32-bit offsets: levels below 2 GB; larger ones keep the old form, which
         // cannot write the warped image)
-        bool small = true;
-        for (int i = 0; i < m; ++i)
-            small = small && (size_t)(lv[i].a.row_end - lv[i].a.row0) * (size_t)lv[i].a.pitch < ((size_t)1 << 31) &&
-                    (size_t)(lv[i].a.out_y1 - lv[i].a.flow_row0) * (size_t)lv[i].a.w * 8 < ((size_t)1 << 31);
+        const bool small = fit_buffer_offsets(lv, m);
         const bool wout = lv[0].a.warp_out != nullptr;
-        static const bool old_form = [] { const char *e = getenv("OFX_ITER_OLD_MARCH"); return e && atoi(e) != 0; }();
         OFX_REQUIRE(!wout || (small && mode != OFX_MODE_COMPAT_CPU), "ofx_lk_levels: d_warp_out needs mode lk_float and levels below 2 GB");
         bool rowwin = false; // a shard's row window: the warp reports taps it cannot reach (ITER 4 / 5)
         for (int i = 0; i < m; ++i) rowwin = rowwin || lv[i].a.row0 != 0 || lv[i].a.row_end != lv[i].a.h;
         OFX_REQUIRE(!(wout && rowwin && !lv[0].a.accumulate), "ofx_lk_levels: iteration 1 with d_warp_out on a row window runs in the stream tick only");
         const int iter = wout ? (lv[0].a.accumulate ? (rowwin ? 4 : 2) : 3) : 1; // (lk_wave_buf's ITER)
-        if (small && (wout || !old_form) && mode != OFX_MODE_COMPAT_CPU) // (compat_cpu accumulates in the old form below)
-        {
-            using F = int (*)(int, const LkLevelIn *, int, hipStream_t);
-            static const F tab[2][4] = {{ofx_launch::iter1_lk_float, ofx_launch::iter2_lk_float, ofx_launch::iter3_lk_float, ofx_launch::iter4_lk_float},
-                                        {ofx_launch::iter1_lk_float_fast, ofx_launch::iter2_lk_float_fast, ofx_launch::iter3_lk_float_fast,
-                                         ofx_launch::iter4_lk_float_fast}};
-            return tab[mode == OFX_MODE_LK_FLOAT_FAST][iter - 1](radius, lv, m, st);
+        if (small && mode != OFX_MODE_COMPAT_CPU) { // (compat_cpu accumulates in the old form below)
+            auto run = [&](auto FAST) {
+                constexpr bool F = decltype(FAST)::value;
+                switch (iter) {
+                case 1: return ofx_launch::iter<OFX_MODE_LK_FLOAT, F, 1>(radius, lv, m, st);
+                case 2: return ofx_launch::iter<OFX_MODE_LK_FLOAT, F, 2>(radius, lv, m, st);
+                case 3: return ofx_launch::iter<OFX_MODE_LK_FLOAT, F, 3>(radius, lv, m, st);
+                default: return ofx_launch::iter<OFX_MODE_LK_FLOAT, F, 4>(radius, lv, m, st);
+                }
+            };
+            return mode == OFX_MODE_LK_FLOAT_FAST ? run(std::true_type{}) : run(std::false_type{});
         }
     }
     // (experiment, OFX_LK_PLAIN_COLS=8: the pair-at-a-time launch on the march with eight columns per lane)
     static const bool plain_wide = [] { const char *e = getenv("OFX_LK_PLAIN_COLS"); return e && atoi(e) == 8; }();
-    if (plain_wide && !d_sums && mode == OFX_MODE_LK_FLOAT && !lv[0].a.accumulate && !lv[0].a.warp_out && radius >= 1 && radius <= 11) {
-        bool small = true;
-        for (int i = 0; i < m; ++i)
-            small = small && (size_t)(lv[i].a.row_end - lv[i].a.row0) * (size_t)lv[i].a.pitch < ((size_t)1 << 31) &&
-                    (size_t)(lv[i].a.out_y1 - lv[i].a.flow_row0) * (size_t)lv[i].a.w * 8 < ((size_t)1 << 31);
-        if (small) return ofx_launch::levels_lk_float_w8(radius, lv, m, st);
-    }
-    if (d_sums) // the sums do not depend on the solve
-        return mode != OFX_MODE_COMPAT_CPU ? ofx_launch::levels_lk_float(radius, lv, m, true, st) : ofx_launch::levels_compat_cpu(radius, lv, m, true, st);
-    if (mode == OFX_MODE_LK_FLOAT_FAST) return ofx_launch::levels_lk_float_fast(radius, lv, m, st);
-    return mode == OFX_MODE_LK_FLOAT ? ofx_launch::levels_lk_float(radius, lv, m, false, st) : ofx_launch::levels_compat_cpu(radius, lv, m, false, st);
+    if (plain_wide && !d_sums && mode == OFX_MODE_LK_FLOAT && !lv[0].a.accumulate && !lv[0].a.warp_out && radius >= 1 && radius <= 11 &&
+        fit_buffer_offsets(lv, m))
+        return ofx_launch::iter<OFX_MODE_LK_FLOAT, false, 0, 8>(radius, lv, m, st);
+    const bool sums = d_sums != nullptr; // (the sums do not depend on the solve)
+    if (mode == OFX_MODE_COMPAT_CPU) return ofx_launch::levels<OFX_MODE_COMPAT_CPU, false>(radius, lv, m, sums, st);
+    if (mode == OFX_MODE_LK_FLOAT_FAST && !sums) return ofx_launch::levels<OFX_MODE_LK_FLOAT, true>(radius, lv, m, false, st);
+    return ofx_launch::levels<OFX_MODE_LK_FLOAT, false>(radius, lv, m, sums, st);
 }
 
 } // namespace
@@ -267,7 +275,7 @@ extern "C" int ofx_stream_launch(const ofx_stream_stages *g, int window, int mod
     // the stream kernel's LK stage addresses planes and flow through buffer resources with 32-bit offsets (lk_body_buf.h)
     for (int i = 0; i < m; ++i) {
         const LkArgs &a = lv[i].a;
-        OFX_REQUIRE((long long)(a.row_end - a.row0) * a.pitch < (1ll << 31) && (long long)(a.out_y1 - a.flow_row0) * a.w * 8 < (1ll << 31),
+        OFX_REQUIRE(fits_buffer_offsets(a),
                     "ofx_stream_launch: level %dx%d is too large for one launch item (planes and flow rows must stay below 2 GB: "
                     "shard the level by rows)", a.w, a.h);
     }
@@ -275,21 +283,20 @@ extern "C" int ofx_stream_launch(const ofx_stream_stages *g, int window, int mod
     hipStream_t st = ofx_stream(stream);
     OFX_REQUIRE(g->deep_fetch >= -1 && g->deep_fetch <= 1, "ofx_stream_launch: deep_fetch must be -1, 0 or +1 (got %d)", g->deep_fetch);
     ofx_launch::g_stream_deep_fetch = g->deep_fetch;
-    if (m > 0 && lv[0].a.warp_out) { // the LK stage also writes the warped images of its pairs' second iteration (levels below 2 GB: checked above)
-        bool rw = false; // a shard's row windows
-        for (int i = 0; i < m; ++i) rw = rw || lv[i].a.row0 != 0 || lv[i].a.row_end != lv[i].a.h;
-        if (rw)
-            return mode == OFX_MODE_LK_FLOAT_FAST ? ofx_launch::stream_lk_float_fast_wout_rw(window >> 1, lv, m, S, stage_blocks, lds, st)
-                                                  : ofx_launch::stream_lk_float_wout_rw(window >> 1, lv, m, S, stage_blocks, lds, st);
-        return mode == OFX_MODE_LK_FLOAT_FAST ? ofx_launch::stream_lk_float_fast_wout(window >> 1, lv, m, S, stage_blocks, lds, st)
-                                              : ofx_launch::stream_lk_float_wout(window >> 1, lv, m, S, stage_blocks, lds, st);
-    }
-    if (mode != OFX_MODE_COMPAT_CPU && lk_cols(lv, m, window >> 1) == 8)
-        return mode == OFX_MODE_LK_FLOAT_FAST ? ofx_launch::stream_lk_float_fast_w8(window >> 1, lv, m, S, stage_blocks, lds, st)
-                                              : ofx_launch::stream_lk_float_w8(window >> 1, lv, m, S, stage_blocks, lds, st);
-    if (mode == OFX_MODE_LK_FLOAT_FAST) return ofx_launch::stream_lk_float_fast(window >> 1, lv, m, S, stage_blocks, lds, st);
-    return mode == OFX_MODE_LK_FLOAT ? ofx_launch::stream_lk_float(window >> 1, lv, m, S, stage_blocks, lds, st)
-                                     : ofx_launch::stream_compat_cpu(window >> 1, lv, m, S, stage_blocks, lds, st);
+    const int radius = window >> 1;
+    if (mode == OFX_MODE_COMPAT_CPU) return ofx_launch::stream<OFX_MODE_COMPAT_CPU, false>(radius, lv, m, S, stage_blocks, lds, st);
+    auto tick = [&](auto FAST) {
+        constexpr bool F = decltype(FAST)::value;
+        if (m > 0 && lv[0].a.warp_out) { // the LK stage also writes the warped images of its pairs' second iteration (levels below 2 GB: checked above)
+            bool rw = false; // a shard's row windows
+            for (int i = 0; i < m; ++i) rw = rw || lv[i].a.row0 != 0 || lv[i].a.row_end != lv[i].a.h;
+            return rw ? ofx_launch::stream<OFX_MODE_LK_FLOAT, F, 5>(radius, lv, m, S, stage_blocks, lds, st)
+                      : ofx_launch::stream<OFX_MODE_LK_FLOAT, F, 3>(radius, lv, m, S, stage_blocks, lds, st);
+        }
+        if (lk_cols(lv, m, radius) == 8) return ofx_launch::stream<OFX_MODE_LK_FLOAT, F, 0, 8>(radius, lv, m, S, stage_blocks, lds, st);
+        return ofx_launch::stream<OFX_MODE_LK_FLOAT, F>(radius, lv, m, S, stage_blocks, lds, st);
+    };
+    return mode == OFX_MODE_LK_FLOAT_FAST ? tick(std::true_type{}) : tick(std::false_type{});
 }
 
 // Debug / measurement hook (tools/stream_timeline.py): with a device buffer of 8 * capacity_blocks uint64 set, every

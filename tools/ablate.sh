@@ -3,7 +3,7 @@
 #   gpurun -- 'bash tools/ablate.sh gpurun_out/r4x tools/plans/<plan>.txt'        results: <outdir>/summary.txt, <outdir>/<name>.json
 # Plan lines:   name | ENV=VALUE ENV=VALUE ... | bench.py arguments       ('#' starts a comment; empty fields allowed)
 # Library variants built beforehand with OFX_BUILD_OUT / OFX_BUILD_DEFS are selected with OFX_LIB=<file> in the env field;
-# ablated kernels (-DOFX_X_*) are wrong by construction: add OFX_BENCH_SKIP_CHECK=1.
+# the ablated kernels of the plans (-DOFX_X_*, wrong by construction: OFX_BENCH_SKIP_CHECK=1) were last buildable at commit 61bdf36.
 O=${1:?outdir}; PLAN=${2:?plan file}
 cd ${GRAFT_REPO_ROOT:-.}
 mkdir -p $O
