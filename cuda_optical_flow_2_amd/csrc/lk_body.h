@@ -14,7 +14,10 @@ struct LkArgs {
     const uint8_t *next;
     const float *uv; // non-null: `next` is read through the reference's global shift by (uv[0], uv[1]) (fused shift)
     float *flow;   // interleaved (u,v), 2*w floats per row, row (y - flow_row0)
-    int32_t *sums; // optional: 5 planes of w ints per row (test/inspection variant)
+    union {
+        int32_t *sums;        // optional: 5 planes of w ints per row (test/inspection variant)
+        const float *flow_in; // two iterations per launch (lk_body_pair.h): the flow set the launch reads; `flow` is the one it writes
+    };
     size_t sums_plane;
     int w, h, pitch, row0, row_end; // buffer holds global rows [row0,row_end)
     int out_y0, out_y1, flow_row0;
@@ -955,6 +958,7 @@ __device__ __forceinline__ void lk_wave_impl(const LkTable &T, int wave, int lan
 #include "lk_body_warp.h" // the warp of lk_iter in two stages (ITER == 2 below)
 #include "lk_body_buf.h" // lk_wave_buf: the same march on buffer resources (a fifth of the scalar instructions)
 #include "lk_body_wide.h" // lk_wave_wide: eight columns per lane (round 4)
+#include "lk_body_pair.h" // lk_wave_pair: two refinement iterations in one march, the flow between them kept in LDS
 #undef OFX_LK_PRIO_STEP
 namespace ofx_dev {
 

@@ -38,6 +38,15 @@ int iter(int radius, const LkLevelIn *lv, int n, hipStream_t st)
     return rc;
 }
 
+template <bool FAST, bool WOUT>
+int iter_pair(int radius, const LkLevelIn *lv, int n, hipStream_t st)
+{
+    int rc = OFX_E_UNSUPPORTED;
+    const bool known = dispatch_radius<kLkPairMaxR>(radius, [&](auto R) { rc = launch_pair_r<decltype(R)::value, FAST, WOUT>(lv, n, st); });
+    if (!known) ofx_set_error("ofx_lk_levels_pair: window %d not supported", 2 * radius + 1);
+    return rc;
+}
+
 template <int MODE, bool FAST, int WOUT, int NC>
 int stream(int radius, const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st)
 {

@@ -81,6 +81,27 @@ __global__ __launch_bounds__(64, NC == 8 ? 2 : 3) void lk_iter_kernel(const LkTa
     else lk_wave_buf<R, MODE, FAST, false, DMA, ITER>(T, wave, lane, xlds);
 }
 
+// Two refinement iterations per launch (lk_body_pair.h): the second trails the first by R + 2 rows in the same wave; flow and warped
+// image between them stay in per-wave LDS rings (19.1 KB at 9x9).  Two waves per SIMD, planned for: a wave holds the registers of
+// two marches.  WOUT: the second iteration also writes the warped image of the one after it.
+template <int R, bool FAST, bool WOUT>
+__global__ __launch_bounds__(64, 2) void lk_pair_kernel(const LkTable T)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t xlds[pair_wave_lds(R)];
+    const int wave = (int)blockIdx.x, lane = (int)threadIdx.x;
+    if (wave >= T.first_block[T.n]) return;
+    int level = 0, hi = T.n;
+    while (hi - level > 1) {
+        const int mid = (level + hi) >> 1;
+        if (wave >= T.first_block[mid]) level = mid;
+        else hi = mid;
+    }
+    const int tile = (wave - T.first_block[level]) % T.lv[level].tiles_x;
+    const int cb0 = tile * TileGeomP<R>::OUT_W - TileGeomP<R>::LO_LANE * 4;
+    if (cb0 >= 0 && cb0 + 256 <= T.lv[level].w) lk_wave_pair<R, FAST, true, WOUT>(T, wave, lane, xlds);
+    else lk_wave_pair<R, FAST, false, WOUT>(T, wave, lane, xlds);
+}
+
 // ---- the stream kernel: one launch = one pipeline tick ---------------------------------------------------------------
 // A tick of a frame stream runs, as disjoint block ranges of ONE grid,
 //     pyramid(newest frame(s))  |  corner flows(earlier pair(s))  |  fused LK(still earlier pair(s))
@@ -168,10 +189,10 @@ int env_int(const char *name, int dflt)
 // `capacity` (lk_wave_target), but at least `min_h` so the 2R priming rows of a strip stay a minor cost.
 // The grid is sized to fit in ONE residency round: every wave runs for the whole kernel, so a second, partly filled
 // round would nearly double the run time.
-template <int R, int NC = 4>
-int plan_table(const LkLevelIn *lv, int n, int capacity, LkTable *out)
+// G: the tile's geometry (its OUT_W; TileGeomW<R, NC> -- NC = 4: TileGeom<R> -- or TileGeomP<R>)
+template <typename G>
+int plan_table_g(const LkLevelIn *lv, int n, int capacity, LkTable *out)
 {
-    using G = TileGeomW<R, NC>; // (NC = 4: TileGeom<R>)
     const int min_h = env_int("OFX_LK_MIN_STRIP", 8);
     int max_rows = 1;
     for (int i = 0; i < n; ++i) max_rows = lv[i].rows_out > max_rows ? lv[i].rows_out : max_rows;
@@ -201,14 +222,21 @@ int plan_table(const LkLevelIn *lv, int n, int capacity, LkTable *out)
     return blocks;
 }
 
+template <int R, int NC = 4>
+int plan_table(const LkLevelIn *lv, int n, int capacity, LkTable *out)
+{
+    return plan_table_g<TileGeomW<R, NC>>(lv, n, capacity, out);
+}
+
 // Number of LK waves a launch is planned for.  Every LK wave runs for the whole launch, so what matters is how many of
 // them share a SIMD: fewer leave issue slots empty, more shorten the strips (each strip pays its priming rows), and a count
 // that is not a whole number per SIMD makes the fuller SIMDs set the time.  Measured on MI355X (one 4K pair, 9x9): with 2R
 // priming steps per strip 3 per SIMD was the optimum; with the folded priming (R + 1 steps, lk_body.h) it is 4 -- 48.9 /
 // 42.0 / 40.4 / 41.6 us at 2 / 3 / 4 / 5.  `reserve` slots per SIMD are left to the other
 // stages of the stream kernel.
+// `full_fill`: per cent of the slots a plan that needs every slot may use.
 template <typename K>
-int lk_wave_target(K kernel, int threads, size_t lds, int reserve, int dflt_per_simd)
+int lk_wave_target(K kernel, int threads, size_t lds, int reserve, int dflt_per_simd, int full_fill = 95)
 {
     int dev = 0, cus = 256, per_cu = 0;
     hipDeviceProp_t prop;
@@ -221,7 +249,7 @@ int lk_wave_target(K kernel, int threads, size_t lds, int reserve, int dflt_per_
     if (per_simd < 1) per_simd = 1;
     // with wave slots to spare the plan may use the whole target (an uneven placement still fits in one round); a plan
     // that needs every slot keeps 5 % back, because a second, mostly empty round would double the run time
-    const int fill = env_int("OFX_LK_FILL", per_simd < occ ? 100 : 95);
+    const int fill = env_int("OFX_LK_FILL", per_simd < occ ? 100 : full_fill);
     return env_int("OFX_LK_TARGET_WAVES", (int)((long)cus * 4 * per_simd * fill / 100));
 }
 
@@ -257,6 +285,21 @@ int launch_iter_r(const LkLevelIn *lv, int n, hipStream_t st)
     for (int i = 0; i < n; ++i) max_px = (long)lv[i].a.w * lv[i].a.h > max_px ? (long)lv[i].a.w * lv[i].a.h : max_px;
     if (forced > 0 || (forced < 0 && max_px >= 16l * 1000 * 1000)) return launch_iter_rd<R, MODE, FAST, ITER, true>(lv, n, st);
     return launch_iter_rd<R, MODE, FAST, ITER, false>(lv, n, st);
+}
+
+// two iterations per launch: two waves per SIMD (a launch carries the work of two, so its strips are about twice as tall)
+template <int R, bool FAST, bool WOUT>
+int launch_pair_r(const LkLevelIn *lv, int n, hipStream_t st)
+{
+    // Every slot is planned for: at two waves per SIMD a SIMD that gets one wave idles half the launch while the full ones set its
+    // time -- measured at 4K, 9x9: 1 945 waves (95 %) 2.137 ms per tick, 2 048 waves 1.992, 1 800 waves 2.463 (the block is one
+    // wave of 19.1 KB: eight fit every CU, so a plan of cus x 8 waves still runs in one round)
+    static const int capacity = lk_wave_target(lk_pair_kernel<R, FAST, WOUT>, 64, 0, 0, 2, 100);
+    LkTable t{};
+    const int blocks = plan_table_g<TileGeomP<R>>(lv, n, capacity, &t);
+    hipLaunchKernelGGL((lk_pair_kernel<R, FAST, WOUT>), dim3((unsigned)blocks), dim3(64), 0, st, t);
+    OFX_HIP(hipGetLastError());
+    return OFX_OK;
 }
 
 // Deep fetch (DMA = true) pays where a step's row loads come from HBM -- measured on MI355X (profiles/r03_ablation.txt): 8K,
@@ -342,6 +385,10 @@ int levels(int radius, const LkLevelIn *lv, int n, bool sums, hipStream_t st);
 // windows of a shard.  NC = 8, ITER = 0: all levels of one pair with eight columns per lane (the pair-at-a-time path)
 template <int MODE, bool FAST, int ITER, int NC = 4>
 int iter(int radius, const LkLevelIn *lv, int n, hipStream_t st);
+// two refinement iterations per launch (lk_body_pair.h; radii 1..kLkPairMaxR, lk_float solves, whole levels): lv[i].a.flow_in is
+// the flow set read, .flow the one written; WOUT: the launch also writes the warped images of the iteration after its second
+template <bool FAST, bool WOUT>
+int iter_pair(int radius, const LkLevelIn *lv, int n, hipStream_t st);
 // one stream tick.  WOUT = 3: its LK stage also writes the warped images of its pairs' second iteration (5: on row windows);
 // NC = 8: eight columns per lane (lk_body_wide.h)
 template <int MODE, bool FAST, int WOUT = 0, int NC = 4>

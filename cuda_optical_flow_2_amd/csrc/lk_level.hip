@@ -316,6 +316,37 @@ extern "C" int ofx_lk_levels(const ofx_lk_desc *levels, int n, int window, int m
     return lk_dispatch(levels, n, window, mode, nullptr, stream);
 }
 
+// Two refinement iterations in one launch (lk_body_pair.h): descriptor i is what ofx_lk_levels takes for the FIRST of them
+// (accumulate set, d_next = the warped image of the iteration before), d_flow_in[i] holds the flow so far and d_flow receives the
+// flow after the second -- a different buffer: waves read d_flow_in at pixels whose owner may already have stored.  With
+// d_warp_out the launch also writes the warped image of the iteration after the second (d_warp_src is needed either way: the
+// first iteration's warp runs inside the launch).
+int ofx_lk_levels_pair(const ofx_lk_desc *d, const float *const *d_flow_in, int n, int window, int mode, void *stream)
+{
+    LkLevelIn lv[OFX_MAX_LK_ITEMS];
+    int m = 0;
+    OFX_REQUIRE(d != nullptr && d_flow_in != nullptr && n >= 1 && n <= OFX_MAX_LK_ITEMS, "ofx_lk_levels_pair: bad arguments");
+    OFX_REQUIRE(mode == OFX_MODE_LK_FLOAT || mode == OFX_MODE_LK_FLOAT_FAST, "ofx_lk_levels_pair: mode %d not supported", mode);
+    OFX_REQUIRE(window >= 3 && (window & 1) && (window >> 1) <= kLkPairMaxR, "ofx_lk_levels_pair: window %d not supported", window);
+    OFX_TRY(lk_build_levels(d, n, window, mode, nullptr, lv, &m));
+    OFX_REQUIRE(m == n, "ofx_lk_levels_pair: empty level");
+    const bool wout = d[0].d_warp_out != nullptr;
+    for (int i = 0; i < n; ++i) {
+        LkArgs &a = lv[i].a;
+        OFX_REQUIRE(a.accumulate && a.uv == nullptr && a.flow != nullptr && d_flow_in[i] != nullptr && d_flow_in[i] != a.flow && d[i].d_warp_src != nullptr,
+                    "ofx_lk_levels_pair: needs accumulate, no d_uv, d_warp_src and two distinct flow buffers");
+        OFX_REQUIRE(a.row0 == 0 && a.row_end == a.h && a.out_y0 == 0 && a.out_y1 == a.h && a.flow_row0 == 0, "ofx_lk_levels_pair: whole levels only");
+        OFX_REQUIRE(fits_buffer_offsets(a), "ofx_lk_levels_pair: levels must stay below 2 GB");
+        a.flow_in = d_flow_in[i];
+        a.warp_src = d[i].d_warp_src;
+        a.warp_scale = d[i].warp_scale;
+    }
+    hipStream_t st = ofx_stream(stream);
+    const int radius = window >> 1;
+    if (mode == OFX_MODE_LK_FLOAT_FAST) return wout ? ofx_launch::iter_pair<true, true>(radius, lv, n, st) : ofx_launch::iter_pair<true, false>(radius, lv, n, st);
+    return wout ? ofx_launch::iter_pair<false, true>(radius, lv, n, st) : ofx_launch::iter_pair<false, false>(radius, lv, n, st);
+}
+
 extern "C" int ofx_lk_level(const uint8_t *d_prev, const uint8_t *d_next, const ofx_geom *g, int window, int mode,
                             float *d_flow, int flow_row0, void *stream)
 {

@@ -82,6 +82,10 @@ int ofx_pyramid_corner_1ch(const uint8_t *d_level0, int pitch0, int w, int h, ui
 // shard's reads (rows [need0, need1) before the shift) to image rows outside [valid0, valid1); shard_rows = 4 ints per level
 int ofx_shard_margin_check(const float *d_uv, int levels, const int *heights, const int *shard_rows, int *d_status, void *stream);
 
+// two refinement iterations in one launch (lk_level.hip, lk_body_pair.h): windows up to 9x9, lk_float solves, whole levels;
+// d_flow_in[i]: the flow so far (read), levels[i].d_flow: the flow after both (written; another buffer)
+int ofx_lk_levels_pair(const ofx_lk_desc *levels, const float *const *d_flow_in, int n, int window, int mode, void *stream);
+
 // the stream pipeline's output stage (compose_ring.hip): the dense field (main.cu:138-147, = ofx_compose_flow at `level`) of
 // n <= OFX_STREAM_MAX_BATCH pairs in one launch.  Pair i reads lv[i][k] (k = level .. levels-1; each points at global row own0[k]
 // of its level, rows tightly packed, w >> (k - level) wide) and writes its rows x w x 2 floats tightly packed at dst[i]

@@ -12,6 +12,9 @@
 #include "compat_scratch.h"
 #include "ofx_internal.h"
 
+#ifndef OFX_ITER_PAIRS_DEFAULT
+#define OFX_ITER_PAIRS_DEFAULT 1 // the stream pipeline's iterations two per launch (lk_body_pair.h); OFX_ITER_PAIRS=0 / 1 overrides
+#endif
 namespace {
 constexpr size_t kAlign = 256;
 // The stream pipeline with B frames per tick uses 3B + 2 image sets and 2B shift-vector slots (see stream_tick); the
@@ -40,6 +43,10 @@ struct ofx_session {
     // refinement iterations in the stream pipeline: per flow set (pair p -> set p mod B) the shifted and the warped next image
     uint8_t *itsh[kMaxBatch][3][OFX_MAX_LEVELS]{};
     bool fused_iters = false; // the accumulating launches also write the next iteration's warped image (lk_body_warp.h)
+    // the stream pipeline runs the iterations after the tick's two per launch (lk_body_pair.h): such a launch reads one flow set and
+    // writes another, so every pair slot has a second set (flowset2); the last launch of a tick always writes flowset
+    bool iter_pairs = false;
+    float *flowset2[kMaxBatch][OFX_MAX_LEVELS]{};
     int cur = 0, sht = 0;                               // img[cur] = previous frame, img[(cur+1)%3] = next frame
     uint8_t *plane[3][OFX_MAX_LEVELS]{};                // role view: 0 prev, 1 next, 2 shifted scratch
     hipStream_t aux = nullptr;                          // pipelined path: staging stream owned by the session
@@ -213,7 +220,14 @@ extern "C" int ofx_session_create(const ofx_params *p_in, ofx_session **out)
     size_t total = 0;
     // (streamed refinement iterations: two more scratch planes per pair of a tick)
     const int n_iter_sets = p->iters > 1 ? 3 * (p->stream_batch >= 2 ? p->stream_batch : 1) : 0; // per flow set: shifted, warped, warped'
-    std::vector<size_t> off_plane[kSets + 2 + 3 * kMaxBatch], off_flow, off_flow2, flow_stride;
+    std::vector<size_t> off_plane[kSets + 2 + 3 * kMaxBatch], off_flow, off_flow2, off_flow_alt, flow_stride;
+    // Two iterations per launch in the stream pipeline (lk_body_pair.h): unsharded lk_float sessions with three iterations or more,
+    // windows up to 9x9, levels that do not take the deep fetch (below 16 Mpx).  OFX_ITER_PAIRS=0 / 1 overrides the default.
+    const bool want_pairs = p->iters >= 3 && !p->sharded && (p->mode == OFX_MODE_LK_FLOAT || p->mode == OFX_MODE_LK_FLOAT_FAST) &&
+                            (p->window >> 1) >= 1 && (p->window >> 1) <= 4 && (long)p->width * p->height < 16l * 1000 * 1000 &&
+                            [] { const char *e = getenv("OFX_ITER_DMA"); return !e || atoi(e) <= 0; }() &&
+                            [] { const char *e = getenv("OFX_ITER_PAIRS"); return e ? atoi(e) != 0 : OFX_ITER_PAIRS_DEFAULT != 0; }();
+    const int n_flow_slots = p->stream_batch >= 2 ? p->stream_batch : 1;
     for (int k = 0; k < p->levels; ++k) {
         s->w[k] = p->width >> k;
         s->h[k] = p->height >> k;
@@ -347,6 +361,11 @@ extern "C" int ofx_session_create(const ofx_params *p_in, ofx_session **out)
     total += align_up((size_t)OFX_MAX_LEVELS * 2 * sizeof(float) * kUvSlots, kAlign);
     const size_t off_staging = total; // one 3-channel frame for ofx_session_set_frame_host_3ch (unsharded sessions only)
     if (!p->sharded) total += align_up((size_t)p->width * (size_t)p->height * 3, kAlign);
+    // the second flow set of every pair slot, behind everything else: the first sets lie where they do without it
+    for (int k = 0; k < p->levels; ++k) {
+        off_flow_alt.push_back(total);
+        if (want_pairs) total += flow_stride[k] * (size_t)n_flow_slots;
+    }
 
     hipError_t e = hipMalloc(&s->arena, total);
     if (e != hipSuccess) {
@@ -371,6 +390,7 @@ extern "C" int ofx_session_create(const ofx_params *p_in, ofx_session **out)
         for (int t = 1; t < kMaxBatch; ++t)
             s->flowset[t][k] = reinterpret_cast<float *>(base + (t < p->stream_batch ? off_flow2[k] + (size_t)(t - 1) * flow_stride[k] : off_flow[k]));
         s->flow[k] = s->flowset[0][k];
+        for (int t = 0; t < n_flow_slots && want_pairs; ++t) s->flowset2[t][k] = reinterpret_cast<float *>(base + off_flow_alt[k] + (size_t)t * flow_stride[k]);
     }
     if (p->local_corner && !p->stream_two_stage)
         for (int k = 0; k < p->levels; ++k)
@@ -395,6 +415,7 @@ extern "C" int ofx_session_create(const ofx_params *p_in, ofx_session **out)
     if ((size_t)(s->buf1[0] - s->buf0[0]) * (size_t)s->pitch[0] >= ((size_t)1 << 31) ||
         (size_t)(s->buf1[0] - s->buf0[0]) * (size_t)s->w[0] * 8 >= ((size_t)1 << 31))
         s->fused_iters = false;
+    s->iter_pairs = want_pairs && s->fused_iters;
     repoint(s);
     *out = s;
     return OFX_OK;
@@ -1151,7 +1172,9 @@ static int stream_tick(ofx_session *s, const uint8_t *const *frames, const int *
     for (long pl = f0 - D * B; pl <= f0 - D * B + B - 1; ++pl) { // LK(pair pl), reading next through the shift vectors the previous tick wrote
         if (pl < 1 || pl > last_frame) continue;
         const int b = (int)(pl % B);
-        float *const *fl = s->flowset[b];
+        // (iterations two per launch: each such launch moves the flow to the slot's other set, and the last one must leave it in
+        // flowset -- with an odd number of them the tick starts in flowset2)
+        float *const *fl = s->iter_pairs && (((s->p.iters - 1) / 2) & 1) ? s->flowset2[b] : s->flowset[b];
         if (s->fused_iters)
             OFX_REQUIRE(!s->p.borrow_frames || (pitch_of(pl, 0, false) == s->pitch[0] && pitch_of(pl - 1, 0, false) == s->pitch[0]),
                         "ofx_session_stream_submit: with refinement iterations borrowed frames need a row pitch of %d bytes (the "
@@ -1208,13 +1231,19 @@ static int stream_tick(ofx_session *s, const uint8_t *const *frames, const int *
         static thread_local ofx_shift_desc sd[OFX_MAX_LK_ITEMS];
         static thread_local ofx_warp_desc wd[OFX_MAX_LK_ITEMS];
         static thread_local ofx_lk_desc ld[OFX_MAX_LK_ITEMS];
+        static thread_local const float *fin[OFX_MAX_LK_ITEMS];
+        // iterations two per launch (lk_body_pair.h), paired from the front; a left-over one runs alone, in place.  alt: the pairs'
+        // flow is in flowset2 (the tick's LK stage chose where it started, above)
+        bool alt = s->iter_pairs && (((s->p.iters - 1) / 2) & 1);
+        int wcur = 1; // the warped plane the next launch reads (itsh[b][1] / [2] alternate; the tick wrote [1])
         const int reach = s->p.window / 2 + 1;
         auto clip = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
-        for (int it = 1; it < s->p.iters; ++it) { // it = iterations done so far; this pass computes iteration it + 1
+        for (int it = 1; it < s->p.iters;) { // it = iterations done so far; this pass computes iteration it + 1 (two: and it + 2)
+            const bool two = s->iter_pairs && it + 2 <= s->p.iters;
             // fused (lk_body_warp.h): every launch but the last also writes the warped images of the pass after it, into the other of
             // the flow set's two warped planes (the tick's LK stage wrote those of this loop's first pass): no warp launch
-            const bool fused = s->fused_iters, need_warp = !fused, wout = fused && it + 1 < s->p.iters;
-            const int wi = fused ? 1 + ((it - 1) & 1) : 1, wo = 1 + (it & 1);
+            const bool fused = s->fused_iters, need_warp = !fused, wout = fused && it + (two ? 2 : 1) < s->p.iters;
+            const int wi = fused ? wcur : 1, wo = 3 - wi;
             int ns = 0, nw = 0;
             for (long pl = f0 - D * B; pl <= f0 - D * B + B - 1; ++pl) {
                 if (pl < 1 || pl > last_frame) continue;
@@ -1237,9 +1266,15 @@ static int stream_tick(ofx_session *s, const uint8_t *const *frames, const int *
                         if (it == 1 && !fused) sd[ns++] = ofx_shift_desc{next_k, s->itsh[b][0][k], level_geom(s, k, s->buf0[k], s->buf1[k]), uvslot(pl) + 2 * k};
                         src = s->itsh[b][0][k];
                     }
-                    wd[nw] = ofx_warp_desc{src, s->itsh[b][wi][k], level_geom(s, k, wa, we), s->flowset[b][k], s->fl0[k], OFX_ITER_SCALE,
+                    float *const fcur = alt ? s->flowset2[b][k] : s->flowset[b][k];
+                    wd[nw] = ofx_warp_desc{src, s->itsh[b][wi][k], level_geom(s, k, wa, we), fcur, s->fl0[k], OFX_ITER_SCALE,
                                            s->p.sharded ? s->corner_status : nullptr, 16 + k};
-                    ld[nw] = ofx_lk_desc{plane_of(pl - 1, k), s->itsh[b][wi][k], level_geom(s, k, a, e), s->flowset[b][k], s->fl0[k], nullptr, 1, s->p.min_det};
+                    ld[nw] = ofx_lk_desc{plane_of(pl - 1, k), s->itsh[b][wi][k], level_geom(s, k, a, e), fcur, s->fl0[k], nullptr, 1, s->p.min_det};
+                    if (two) { // reads fcur, writes the slot's other set; its first iteration's warp needs the source either way
+                        fin[nw] = fcur;
+                        ld[nw].d_flow = alt ? s->flowset[b][k] : s->flowset2[b][k];
+                        ld[nw].d_warp_src = src, ld[nw].warp_scale = OFX_ITER_SCALE;
+                    }
                     if (wout) {
                         ld[nw].d_warp_src = src, ld[nw].d_warp_out = s->itsh[b][wo][k], ld[nw].warp_scale = OFX_ITER_SCALE;
                         if (s->p.sharded) ld[nw].d_warp_status = s->corner_status, ld[nw].warp_status_bit = 16 + k;
@@ -1249,7 +1284,12 @@ static int stream_tick(ofx_session *s, const uint8_t *const *frames, const int *
             }
             if (ns) OFX_TRY(timed_launch(s, OFX_TIME_SHIFT, stream, [&] { return ofx_shift_levels(sd, ns, stream); }));
             if (need_warp) OFX_TRY(timed_launch(s, OFX_TIME_WARP, stream, [&] { return ofx_warp_levels(wd, nw, stream); }));
-            OFX_TRY(timed_launch(s, wout ? OFX_TIME_LK_ACC_WARP : OFX_TIME_LK_ACC, stream, [&] { return ofx_lk_levels(ld, nw, s->p.window, s->p.mode, stream); }));
+            OFX_TRY(timed_launch(s, wout ? OFX_TIME_LK_ACC_WARP : OFX_TIME_LK_ACC, stream, [&] {
+                return two ? ofx_lk_levels_pair(ld, fin, nw, s->p.window, s->p.mode, stream) : ofx_lk_levels(ld, nw, s->p.window, s->p.mode, stream);
+            }));
+            if (two) alt = !alt;
+            wcur = wo;
+            it += two ? 2 : 1;
         }
     }
     // the output stage (ofx_session_stream_compose): behind the tick's last launch on the same stream, before the next tick
