@@ -29,12 +29,19 @@ namespace ofx_dev {
 
 template <int R>
 struct TileGeomP { // a wave tile of the fused pair: B's output lanes
-    static constexpr int INSET = (R + 1 + 3) / 4; // lanes that R + 1 columns take
-    static constexpr int LO_LANE = TileGeom<R>::LO_LANE + INSET;
-    static constexpr int HI_LANE = TileGeom<R>::HI_LANE - INSET;
+    // A's results are exact from wave column R + 1 on (derivatives from column 1; hbox4x5's sliding differences are integer, so a
+    // lane's columns are each exact or not on their own, also in lanes below TileGeom<R>::LO_LANE), and B's outputs need them R + 1
+    // columns either side: B's first exact column is 2R + 2, its last 253 - 2R.  The inset is rounded to whole lanes ONCE.
+    static constexpr int FIRST_COL = 2 * R + 2;
+    static constexpr int LO_LANE = (FIRST_COL + 3) / 4;
+    static constexpr int HI_LANE = 63 - LO_LANE;
     static constexpr int OUT_W = (HI_LANE - LO_LANE + 1) * 4;
+    static_assert(4 * LO_LANE >= FIRST_COL && 4 * HI_LANE + 3 <= 253 - 2 * R, "B's output columns have all of A's results they need");
 };
-static_assert(TileGeomP<4>::LO_LANE == 4 && TileGeomP<4>::HI_LANE == 59 && TileGeomP<4>::OUT_W == 224, "9x9: lanes 4..59");
+static_assert(TileGeomP<4>::LO_LANE == 3 && TileGeomP<4>::HI_LANE == 60 && TileGeomP<4>::OUT_W == 232, "9x9: lanes 3..60");
+static_assert(TileGeomP<3>::LO_LANE == 2 && TileGeomP<3>::HI_LANE == 61 && TileGeomP<3>::OUT_W == 240, "7x7: lanes 2..61");
+static_assert(TileGeomP<2>::LO_LANE == 2 && TileGeomP<2>::HI_LANE == 61 && TileGeomP<2>::OUT_W == 240, "5x5: lanes 2..61");
+static_assert(TileGeomP<1>::LO_LANE == 1 && TileGeomP<1>::HI_LANE == 62 && TileGeomP<1>::OUT_W == 248, "3x3: lanes 1..62");
 
 constexpr int kLkPairMaxR = 4;
 constexpr int pair_warp_rows(int r) { return 2 * r + 4; } // rows [yyB - 2R, yyB + 1] are live in a step: 2R + 2, and slack
@@ -42,22 +49,21 @@ constexpr int pair_flow_rows(int r) { return r + 3; }     // LAG + 1
 constexpr int pair_wave_lds(int r) { return kLkWaveLds + 256 * pair_warp_rows(r) + 2048 * pair_flow_rows(r); }
 static_assert(pair_wave_lds(4) == 19584 && 8 * pair_wave_lds(4) <= 160 * 1024, "two waves per SIMD at 9x9");
 
+constexpr int pair_seg_steps(int r) { return 3 * r + 4; } // what a segment of a wave costs beyond its rows: priming and lag
+
+// One segment of a wave: rows [ysB, yeB) of tile column `tile` of item `level`.  Everything a segment needs is set up here, so a wave
+// may march several, one after the other (lk_pair_kernel).  q1..q3: the steps of THIS march at which the wave's priority drops, i.e.
+// the quarter points of the wave's whole work less the steps of its earlier segments.
 template <int R, bool FAST, bool INTERIOR, bool WOUT>
-__device__ __forceinline__ void lk_wave_pair(const LkTable &T, int wave, int lane, uint8_t *xlds)
+__device__ __forceinline__ void lk_wave_pair(const LkTable &T, int level, int tile, int ysB, int yeB, int lane, uint8_t *xlds, int q1, int q2, int q3)
 {
     constexpr int MODE = OFX_MODE_LK_FLOAT;
     using G = TileGeomP<R>;
     constexpr int NS = 2 * R + 1, H = R - 1, PR = 2 * R - H;
     constexpr int kLagSteps = 2 * R + 3;
     constexpr int WN = pair_warp_rows(R), FN = pair_flow_rows(R);
+    static_assert(PR + kLagSteps == pair_seg_steps(R), "a segment of r rows takes r + 3R + 4 steps");
 
-    if (wave >= T.first_block[T.n]) return;
-    int level = 0, hi = T.n;
-    while (hi - level > 1) {
-        const int mid = (level + hi) >> 1;
-        if (wave >= T.first_block[mid]) level = mid;
-        else hi = mid;
-    }
     LkArgs A = T.lv[level];
     pin_scalar(A.w);
     pin_scalar(A.h);
@@ -65,11 +71,7 @@ __device__ __forceinline__ void lk_wave_pair(const LkTable &T, int wave, int lan
     pin_scalar(A.min_det);
     pin_scalar(A.warp_scale);
     const SolveOpts sopt{A.min_det};
-    const int block = wave - T.first_block[level];
-    const int tile = block % A.tiles_x;
-    const int strip = block / A.tiles_x;
     const int cb = tile * G::OUT_W - G::LO_LANE * 4 + 4 * lane; // first of this lane's 4 image columns
-    const int ysB = A.out_y0 + strip * A.strip_h, yeB = min(ysB + A.strip_h, A.out_y1);
     const int ysA = ysB - (R + 1), yeA = min(yeB + R + 1, A.h);
 
     const int plane_bytes = A.h * A.pitch;
@@ -337,8 +339,6 @@ __device__ __forceinline__ void lk_wave_pair(const LkTable &T, int wave, int lan
             stepB(std::integral_constant<int, kb>{}, t - kLagSteps);
         }
     };
-    const int q1 = nsteps / 4, q2 = nsteps / 2, q3 = nsteps - nsteps / 4;
-    __builtin_amdgcn_s_setprio(3);
     int s = 0;
     while (true) {
         body(std::integral_constant<int, 0>{}, s);

@@ -39,10 +39,10 @@ int iter(int radius, const LkLevelIn *lv, int n, hipStream_t st)
 }
 
 template <bool FAST, bool WOUT>
-int iter_pair(int radius, const LkLevelIn *lv, int n, hipStream_t st)
+int iter_pair(int radius, const LkLevelIn *lv, int n, const ofx_pair_opts *opts, hipStream_t st)
 {
     int rc = OFX_E_UNSUPPORTED;
-    const bool known = dispatch_radius<kLkPairMaxR>(radius, [&](auto R) { rc = launch_pair_r<decltype(R)::value, FAST, WOUT>(lv, n, st); });
+    const bool known = dispatch_radius<kLkPairMaxR>(radius, [&](auto R) { rc = launch_pair_r<decltype(R)::value, FAST, WOUT>(lv, n, opts, st); });
     if (!known) ofx_set_error("ofx_lk_levels_pair: window %d not supported", 2 * radius + 1);
     return rc;
 }

@@ -2,5 +2,5 @@
 // the <= 1 ulp solve; the second iteration with and without the warped image of the one after it.
 #include "lk_inst.h"
 
-template int ofx_launch::iter_pair<true, false>(int, const LkLevelIn *, int, hipStream_t);
-template int ofx_launch::iter_pair<true, true>(int, const LkLevelIn *, int, hipStream_t);
+template int ofx_launch::iter_pair<true, false>(int, const LkLevelIn *, int, const ofx_pair_opts *, hipStream_t);
+template int ofx_launch::iter_pair<true, true>(int, const LkLevelIn *, int, const ofx_pair_opts *, hipStream_t);

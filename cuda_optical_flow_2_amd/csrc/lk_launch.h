@@ -9,6 +9,7 @@
 
 #include "corner_body.h"
 #include "lk_body.h"
+#include "pair_plan.h"
 #include "pyr_march.h"
 #include "stages_body.h"
 
@@ -39,9 +40,21 @@ struct LkLevelIn {
     LkArgs a;     // everything but strip_h / tiles_x
     int rows_out;
 };
+using ofx_plan::kPairMaxSegs;
+using ofx_plan::PairSeg;
+// The packed plan of a fused two-iteration launch (pair_plan.h) on the device: made and uploaded once per launch shape -- the
+// radius, the items' sizes and the wave count -- and kept in the caller's cache (lk_level.hip).  segs = NULL: no plan fits (the
+// launch keeps one strip per wave).
+struct PairPlanDev {
+    const PairSeg *segs;
+    int waves;
+};
+int pair_plan_get(ofx_pair_cache **cache, int radius, int out_w, const LkLevelIn *lv, int n, int capacity, PairPlanDev *out);
 } // namespace ofx_launch
 
 namespace {
+using ofx_plan::kPairMaxSegs;
+using ofx_plan::PairSeg;
 
 constexpr int kLkMinWaves = 3; // A/B on MI355X: capping at 128 VGPRs (4 waves) spills in the marching loop and is slower
 template <int R, int MODE, bool SUMS, bool FAST>
@@ -84,22 +97,60 @@ __global__ __launch_bounds__(64, NC == 8 ? 2 : 3) void lk_iter_kernel(const LkTa
 // Two refinement iterations per launch (lk_body_pair.h): the second trails the first by R + 2 rows in the same wave; flow and warped
 // image between them stay in per-wave LDS rings (19.1 KB at 9x9).  Two waves per SIMD, planned for: a wave holds the registers of
 // two marches.  WOUT: the second iteration also writes the warped image of the one after it.
+// segs: the packed plan (pair_plan.h): wave w marches segments segs[kPairMaxSegs * w ...], one after the other; NULL: the plan of
+// plan_table_g in T, one strip per wave.
 template <int R, bool FAST, bool WOUT>
-__global__ __launch_bounds__(64, 2) void lk_pair_kernel(const LkTable T)
+__global__ __launch_bounds__(64, 2) void lk_pair_kernel(const LkTable T, const PairSeg *__restrict__ segs)
 {
     __shared__ __attribute__((aligned(16))) uint8_t xlds[pair_wave_lds(R)];
     const int wave = (int)blockIdx.x, lane = (int)threadIdx.x;
-    if (wave >= T.first_block[T.n]) return;
-    int level = 0, hi = T.n;
-    while (hi - level > 1) {
-        const int mid = (level + hi) >> 1;
-        if (wave >= T.first_block[mid]) level = mid;
-        else hi = mid;
+    typedef int i32x4 __attribute__((ext_vector_type(4)));
+    const i32x4 *sg = reinterpret_cast<const i32x4 *>(segs) + kPairMaxSegs * wave;
+    int nsteps = 0; // of the whole wave: its priority falls along all of its work
+    int level = 0;
+    if (segs) {
+#pragma unroll
+        for (int i = 0; i < kPairMaxSegs; ++i) {
+            const i32x4 g = sg[i];
+            nsteps += g.w > g.z ? g.w - g.z + pair_seg_steps(R) : 0;
+        }
+    } else {
+        if (wave >= T.first_block[T.n]) return;
+        int hi = T.n;
+        while (hi - level > 1) {
+            const int mid = (level + hi) >> 1;
+            if (wave >= T.first_block[mid]) level = mid;
+            else hi = mid;
+        }
     }
-    const int tile = (wave - T.first_block[level]) % T.lv[level].tiles_x;
-    const int cb0 = tile * TileGeomP<R>::OUT_W - TileGeomP<R>::LO_LANE * 4;
-    if (cb0 >= 0 && cb0 + 256 <= T.lv[level].w) lk_wave_pair<R, FAST, true, WOUT>(T, wave, lane, xlds);
-    else lk_wave_pair<R, FAST, false, WOUT>(T, wave, lane, xlds);
+    int q1 = 0, q2 = 0, q3 = 0;
+    __builtin_amdgcn_s_setprio(3);
+#pragma nounroll
+    for (int i = 0; i < kPairMaxSegs; ++i) {
+        int tile, y0, y1;
+        if (segs) {
+            const i32x4 g = sg[i];
+            level = g.x, tile = g.y, y0 = g.z, y1 = g.w;
+            if (y1 <= y0) break;
+        } else {
+            if (i > 0) break;
+            const int block = wave - T.first_block[level];
+            tile = block % T.lv[level].tiles_x;
+            y0 = T.lv[level].out_y0 + (block / T.lv[level].tiles_x) * T.lv[level].strip_h;
+            y1 = min(y0 + T.lv[level].strip_h, T.lv[level].out_y1);
+            nsteps = y1 - y0 + pair_seg_steps(R);
+        }
+        if (i == 0) q1 = nsteps / 4, q2 = nsteps / 2, q3 = nsteps - nsteps / 4;
+        else { // the rings and the exchange row are reused: what the segment before still reads of them comes first
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+        const int cb0 = tile * TileGeomP<R>::OUT_W - TileGeomP<R>::LO_LANE * 4;
+        if (cb0 >= 0 && cb0 + 256 <= T.lv[level].w) lk_wave_pair<R, FAST, true, WOUT>(T, level, tile, y0, y1, lane, xlds, q1, q2, q3);
+        else lk_wave_pair<R, FAST, false, WOUT>(T, level, tile, y0, y1, lane, xlds, q1, q2, q3);
+        const int done = y1 - y0 + pair_seg_steps(R);
+        q1 -= done, q2 -= done, q3 -= done;
+    }
 }
 
 // ---- the stream kernel: one launch = one pipeline tick ---------------------------------------------------------------
@@ -288,16 +339,24 @@ int launch_iter_r(const LkLevelIn *lv, int n, hipStream_t st)
 }
 
 // two iterations per launch: two waves per SIMD (a launch carries the work of two, so its strips are about twice as tall)
+// opts (NULL: none): the caller's plan cache and switches.  With opts->pack the waves carry equal STEPS instead of one strip each
+// (pair_plan.h); opts->waves > 0 sets the wave count of that plan.
 template <int R, bool FAST, bool WOUT>
-int launch_pair_r(const LkLevelIn *lv, int n, hipStream_t st)
+int launch_pair_r(const LkLevelIn *lv, int n, const ofx_pair_opts *opts, hipStream_t st)
 {
     // Every slot is planned for: at two waves per SIMD a SIMD that gets one wave idles half the launch while the full ones set its
     // time -- measured at 4K, 9x9: 1 945 waves (95 %) 2.137 ms per tick, 2 048 waves 1.992, 1 800 waves 2.463 (the block is one
     // wave of 19.1 KB: eight fit every CU, so a plan of cus x 8 waves still runs in one round)
     static const int capacity = lk_wave_target(lk_pair_kernel<R, FAST, WOUT>, 64, 0, 0, 2, 100);
     LkTable t{};
-    const int blocks = plan_table_g<TileGeomP<R>>(lv, n, capacity, &t);
-    hipLaunchKernelGGL((lk_pair_kernel<R, FAST, WOUT>), dim3((unsigned)blocks), dim3(64), 0, st, t);
+    int blocks = plan_table_g<TileGeomP<R>>(lv, n, capacity, &t);
+    ofx_launch::PairPlanDev plan{nullptr, 0};
+    if (opts && opts->pack && opts->cache) {
+        const int want = opts->waves > 0 && opts->waves < capacity ? opts->waves : capacity;
+        OFX_TRY(ofx_launch::pair_plan_get(opts->cache, R, TileGeomP<R>::OUT_W, lv, n, want, &plan));
+        if (plan.segs) blocks = plan.waves;
+    }
+    hipLaunchKernelGGL((lk_pair_kernel<R, FAST, WOUT>), dim3((unsigned)blocks), dim3(64), 0, st, t, plan.segs);
     OFX_HIP(hipGetLastError());
     return OFX_OK;
 }
@@ -388,7 +447,7 @@ int iter(int radius, const LkLevelIn *lv, int n, hipStream_t st);
 // two refinement iterations per launch (lk_body_pair.h; radii 1..kLkPairMaxR, lk_float solves, whole levels): lv[i].a.flow_in is
 // the flow set read, .flow the one written; WOUT: the launch also writes the warped images of the iteration after its second
 template <bool FAST, bool WOUT>
-int iter_pair(int radius, const LkLevelIn *lv, int n, hipStream_t st);
+int iter_pair(int radius, const LkLevelIn *lv, int n, const ofx_pair_opts *opts, hipStream_t st);
 // one stream tick.  WOUT = 3: its LK stage also writes the warped images of its pairs' second iteration (5: on row windows);
 // NC = 8: eight columns per lane (lk_body_wide.h)
 template <int MODE, bool FAST, int WOUT = 0, int NC = 4>

@@ -24,6 +24,8 @@
 // (OptFlowCPU.cpp:182-191) -- i.e. the image and the derivative planes are zero-extended.
 #include <string.h>
 
+#include <vector>
+
 #include "lk_launch.h"
 
 
@@ -33,6 +35,63 @@ int g_stream_trace_blocks = 0;
 int g_trace_header[2 * OFX_STREAM_MAX_BATCH + 1] = {0};
 thread_local int g_stream_deep_fetch = 0;
 } // namespace ofx_launch
+
+// ---- the packed plans of the fused two-iteration launch (pair_plan.h), on the device --------------------------------------------
+// A session sees a handful of launch shapes (a full tick, the partial ticks at its start and in the drain); each gets its plan the
+// first time it is launched -- the planner on the host, one allocation, one blocking copy -- and every later launch finds it here.
+struct ofx_pair_cache {
+    struct Entry {
+        std::vector<int> key; // radius, tile width, wave count, then w, h per item
+        PairSeg *d_segs;      // NULL: no plan fits
+        int waves;
+    };
+    std::vector<Entry> entries;
+};
+
+void ofx_pair_cache_free(ofx_pair_cache *c)
+{
+    if (!c) return;
+    for (ofx_pair_cache::Entry &e : c->entries)
+        if (e.d_segs) (void)hipFree(e.d_segs);
+    delete c;
+}
+
+int ofx_launch::pair_plan_get(ofx_pair_cache **cache, int radius, int out_w, const LkLevelIn *lv, int n, int capacity, PairPlanDev *out)
+{
+    std::vector<int> key{radius, out_w, capacity};
+    for (int i = 0; i < n; ++i) key.push_back(lv[i].a.w), key.push_back(lv[i].a.h);
+    if (!*cache) *cache = new ofx_pair_cache;
+    for (const ofx_pair_cache::Entry &e : (*cache)->entries)
+        if (e.key == key) {
+            *out = PairPlanDev{e.d_segs, e.waves};
+            return OFX_OK;
+        }
+    std::vector<ofx_plan::PairItem> items(n);
+    for (int i = 0; i < n; ++i) items[i] = ofx_plan::PairItem{lv[i].a.w, lv[i].a.h};
+    ofx_plan::PairPlan plan;
+    ofx_pair_cache::Entry e{key, nullptr, 0};
+    const bool fits = ofx_plan::pair_plan_make(items.data(), n, out_w, pair_seg_steps(radius), env_int("OFX_LK_MIN_STRIP", 8), capacity, &plan);
+    if (fits) {
+        const size_t bytes = plan.segs.size() * sizeof(PairSeg);
+        OFX_HIP(hipMalloc(reinterpret_cast<void **>(&e.d_segs), bytes));
+        const hipError_t rc = hipMemcpy(e.d_segs, plan.segs.data(), bytes, hipMemcpyHostToDevice);
+        if (rc != hipSuccess) {
+            (void)hipFree(e.d_segs);
+            OFX_HIP(rc);
+        }
+        e.waves = plan.waves;
+    }
+    if (getenv("OFX_PAIR_DEBUG")) { // the plan, once per shape
+        fprintf(stderr, "ofx pair plan: window %d tile %d items %d capacity %d:", 2 * radius + 1, out_w, n, capacity);
+        if (fits) fprintf(stderr, " waves %d segments %d S %d; tile columns", plan.waves, plan.segments, plan.S);
+        else fprintf(stderr, " none fits (one strip per wave); tile columns");
+        for (int i = 0; i < n; ++i) fprintf(stderr, " %d", ofx_div_up(items[i].w, out_w));
+        fprintf(stderr, "\n");
+    }
+    (*cache)->entries.push_back(e);
+    *out = PairPlanDev{e.d_segs, e.waves};
+    return OFX_OK;
+}
 
 namespace {
 
@@ -321,7 +380,7 @@ extern "C" int ofx_lk_levels(const ofx_lk_desc *levels, int n, int window, int m
 // flow after the second -- a different buffer: waves read d_flow_in at pixels whose owner may already have stored.  With
 // d_warp_out the launch also writes the warped image of the iteration after the second (d_warp_src is needed either way: the
 // first iteration's warp runs inside the launch).
-int ofx_lk_levels_pair(const ofx_lk_desc *d, const float *const *d_flow_in, int n, int window, int mode, void *stream)
+int ofx_lk_levels_pair(const ofx_lk_desc *d, const float *const *d_flow_in, int n, int window, int mode, const ofx_pair_opts *opts, void *stream)
 {
     LkLevelIn lv[OFX_MAX_LK_ITEMS];
     int m = 0;
@@ -343,8 +402,8 @@ int ofx_lk_levels_pair(const ofx_lk_desc *d, const float *const *d_flow_in, int 
     }
     hipStream_t st = ofx_stream(stream);
     const int radius = window >> 1;
-    if (mode == OFX_MODE_LK_FLOAT_FAST) return wout ? ofx_launch::iter_pair<true, true>(radius, lv, n, st) : ofx_launch::iter_pair<true, false>(radius, lv, n, st);
-    return wout ? ofx_launch::iter_pair<false, true>(radius, lv, n, st) : ofx_launch::iter_pair<false, false>(radius, lv, n, st);
+    if (mode == OFX_MODE_LK_FLOAT_FAST) return wout ? ofx_launch::iter_pair<true, true>(radius, lv, n, opts, st) : ofx_launch::iter_pair<true, false>(radius, lv, n, opts, st);
+    return wout ? ofx_launch::iter_pair<false, true>(radius, lv, n, opts, st) : ofx_launch::iter_pair<false, false>(radius, lv, n, opts, st);
 }
 
 extern "C" int ofx_lk_level(const uint8_t *d_prev, const uint8_t *d_next, const ofx_geom *g, int window, int mode,

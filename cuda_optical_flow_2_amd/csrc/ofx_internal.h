@@ -84,7 +84,17 @@ int ofx_shard_margin_check(const float *d_uv, int levels, const int *heights, co
 
 // two refinement iterations in one launch (lk_level.hip, lk_body_pair.h): windows up to 9x9, lk_float solves, whole levels;
 // d_flow_in[i]: the flow so far (read), levels[i].d_flow: the flow after both (written; another buffer)
-int ofx_lk_levels_pair(const ofx_lk_desc *levels, const float *const *d_flow_in, int n, int window, int mode, void *stream);
+// opts (NULL: one strip per wave): how the launch is planned.  pack: waves of equal steps, each marching up to two segments
+// (pair_plan.h); the plans live on the device in *cache, which the first packed launch creates and its owner frees with
+// ofx_pair_cache_free -- one plan per launch shape, made and uploaded when the shape is first seen, nothing after that.  waves > 0:
+// the wave count of the packed plan instead of the device's (tests: small levels then straddle waves as large ones do).
+struct ofx_pair_cache;
+struct ofx_pair_opts {
+    int pack, waves;
+    ofx_pair_cache **cache;
+};
+void ofx_pair_cache_free(ofx_pair_cache *c);
+int ofx_lk_levels_pair(const ofx_lk_desc *levels, const float *const *d_flow_in, int n, int window, int mode, const ofx_pair_opts *opts, void *stream);
 
 // the stream pipeline's output stage (compose_ring.hip): the dense field (main.cu:138-147, = ofx_compose_flow at `level`) of
 // n <= OFX_STREAM_MAX_BATCH pairs in one launch.  Pair i reads lv[i][k] (k = level .. levels-1; each points at global row own0[k]

@@ -46,6 +46,10 @@ struct ofx_session {
     // the stream pipeline runs the iterations after the tick's two per launch (lk_body_pair.h): such a launch reads one flow set and
     // writes another, so every pair slot has a second set (flowset2); the last launch of a tick always writes flowset
     bool iter_pairs = false;
+    // the fused launches' plan (lk_launch.h): waves of equal steps (OFX_PAIR_PACK=0: one strip per wave, as before), the wave count
+    // OFX_PAIR_WAVES forces on that plan (0: the device's), and the plans this session has made (freed with it)
+    ofx_pair_opts pair_opts{1, 0, nullptr};
+    ofx_pair_cache *pair_cache = nullptr;
     float *flowset2[kMaxBatch][OFX_MAX_LEVELS]{};
     int cur = 0, sht = 0;                               // img[cur] = previous frame, img[(cur+1)%3] = next frame
     uint8_t *plane[3][OFX_MAX_LEVELS]{};                // role view: 0 prev, 1 next, 2 shifted scratch
@@ -416,6 +420,9 @@ extern "C" int ofx_session_create(const ofx_params *p_in, ofx_session **out)
         (size_t)(s->buf1[0] - s->buf0[0]) * (size_t)s->w[0] * 8 >= ((size_t)1 << 31))
         s->fused_iters = false;
     s->iter_pairs = want_pairs && s->fused_iters;
+    s->pair_opts.pack = [] { const char *e = getenv("OFX_PAIR_PACK"); return !e || atoi(e) != 0; }() ? 1 : 0;
+    s->pair_opts.waves = [] { const char *e = getenv("OFX_PAIR_WAVES"); return e && atoi(e) > 0 ? atoi(e) : 0; }();
+    s->pair_opts.cache = &s->pair_cache;
     repoint(s);
     *out = s;
     return OFX_OK;
@@ -435,6 +442,7 @@ extern "C" int ofx_session_destroy(ofx_session *s)
     if (s->arena) e = hipFree(s->arena);
     if (s->fe_arena && e == hipSuccess) e = hipFree(s->fe_arena);
     ofx_frontend_tables_free(s->fe);
+    ofx_pair_cache_free(s->pair_cache);
     delete s;
     if (e != hipSuccess) {
         ofx_set_error("ofx_session_destroy: hipFree: %s", hipGetErrorString(e));
@@ -1285,7 +1293,7 @@ static int stream_tick(ofx_session *s, const uint8_t *const *frames, const int *
             if (ns) OFX_TRY(timed_launch(s, OFX_TIME_SHIFT, stream, [&] { return ofx_shift_levels(sd, ns, stream); }));
             if (need_warp) OFX_TRY(timed_launch(s, OFX_TIME_WARP, stream, [&] { return ofx_warp_levels(wd, nw, stream); }));
             OFX_TRY(timed_launch(s, wout ? OFX_TIME_LK_ACC_WARP : OFX_TIME_LK_ACC, stream, [&] {
-                return two ? ofx_lk_levels_pair(ld, fin, nw, s->p.window, s->p.mode, stream) : ofx_lk_levels(ld, nw, s->p.window, s->p.mode, stream);
+                return two ? ofx_lk_levels_pair(ld, fin, nw, s->p.window, s->p.mode, &s->pair_opts, stream) : ofx_lk_levels(ld, nw, s->p.window, s->p.mode, stream);
             }));
             if (two) alt = !alt;
             wcur = wo;
