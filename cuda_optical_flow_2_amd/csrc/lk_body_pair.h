@@ -21,6 +21,17 @@
 //   * A's step t leaves warped rows up to ysB + t - (2R + 3) in the ring; B's step t - kLagSteps takes exactly that row as the
 //     bottom row of its entering window, so B takes its rows at the START of its step (after A's part of the same step), not a
 //     step ahead as the marches that read memory do.  LDS operations of a wave execute in order and the rings are private to it.
+//   * B does not compute 1 / det again (OFX_PAIR_SHARE_RCP).  det = a d - b b of the 2x2 solve is made of the three window sums of
+//     prev's derivatives alone, and B's three sums at a pixel are the very integers A had there: the same lane and column mask,
+//     the same row masks (both marches clip the window to the image, and a strip's own limits lie outside every window of a row
+//     it emits), sliding sums that are exact in int.  So det and the reciprocal the solve takes of it (lk_solve.h) are identical
+//     bit for bit, det == 0 with its +-Inf / NaN included, and no tolerance is involved.  A's emitting step t makes output row
+//     ysB - 2R - 2 + t, B's step t - kLagSteps makes ysB - 3R - 4 + t: B is R + 2 joint steps behind on a row, for every wave.
+//     The four doubles of a lane's row travel that long in registers: slots that rotate with the three-fold body (written at
+//     step t, read or moved on at t + 3 in the same k) give a delay of 3 per slot, a shift chain of (R + 2) % 3 stages the rest:
+//     9x9 two slots, 7x7 one slot and two stages, 5x5 one and one, 3x3 one slot; 8 (R + 2) registers, and at 9x9 8 v_mov_b64
+//     per step (B uses its value after A's solve of the same step: three values per k are alive, each double moves twice).  Only the reciprocal: the sums or the scaled matrix as well would be 24 - 36 more registers per row
+//     of lag.
 // Whole levels only (row0 = 0, all rows), no global shift (the shifted image was made before the tick), lk_float solves, R <= 4:
 // the host checks (lk_level.hip).  The arithmetic and its order are those of lk_wave_buf: results are bit-identical.
 #pragma once
@@ -43,6 +54,12 @@ static_assert(TileGeomP<3>::LO_LANE == 2 && TileGeomP<3>::HI_LANE == 61 && TileG
 static_assert(TileGeomP<2>::LO_LANE == 2 && TileGeomP<2>::HI_LANE == 61 && TileGeomP<2>::OUT_W == 240, "5x5: lanes 2..61");
 static_assert(TileGeomP<1>::LO_LANE == 1 && TileGeomP<1>::HI_LANE == 62 && TileGeomP<1>::OUT_W == 248, "3x3: lanes 1..62");
 
+#ifndef OFX_PAIR_SHARE_RCP
+#define OFX_PAIR_SHARE_RCP 1 // march B takes 1 / det from march A (above); 0: both compute it, as two launches would
+#endif
+// per instance, should one not fit its registers (profiles/pair_rcp_budget.txt: all sixteen do)
+constexpr bool pair_share_rcp(int r, bool fast) { return OFX_PAIR_SHARE_RCP != 0; }
+
 constexpr int kLkPairMaxR = 4;
 constexpr int pair_warp_rows(int r) { return 2 * r + 4; } // rows [yyB - 2R, yyB + 1] are live in a step: 2R + 2, and slack
 constexpr int pair_flow_rows(int r) { return r + 3; }     // LAG + 1
@@ -63,6 +80,19 @@ __device__ __forceinline__ void lk_wave_pair(const LkTable &T, int level, int ti
     constexpr int kLagSteps = 2 * R + 3;
     constexpr int WN = pair_warp_rows(R), FN = pair_flow_rows(R);
     static_assert(PR + kLagSteps == pair_seg_steps(R), "a segment of r rows takes r + 3R + 4 steps");
+    // A's reciprocals on their way to B, R + 2 steps: QD slots per k = t mod 3 (rq[0]: the younger), then QE chain stages.
+    // A segment primes its own line: B's first emitting step, 3R + 4, takes what A's step 2R + 2 >= PR of THIS segment put in (9x9:
+    // 16 and 10); what the line holds before that -- nothing, or an earlier segment's values -- moves through it and is never used.
+    constexpr bool SHARE = pair_share_rcp(R, FAST);
+    constexpr int QD = (R + 2) / 3, QE = (R + 2) % 3;
+    static_assert(QD >= 1 && 3 * QD + QE == kLagSteps - (R + 1), "the delay is B's lag behind A on an output row");
+    [[maybe_unused]] double rq[QD][3][4], rc[QE > 0 ? QE : 1][4];
+    if constexpr (SHARE) { // (volatile: equal asm statements would be merged into one value and copied out of it)
+#pragma unroll
+        for (int i = 0; i < QD * 3; ++i) asm volatile("" : "=v"(rq[i / 3][i % 3][0]), "=v"(rq[i / 3][i % 3][1]), "=v"(rq[i / 3][i % 3][2]), "=v"(rq[i / 3][i % 3][3]));
+#pragma unroll
+        for (int i = 0; i < QE; ++i) asm volatile("" : "=v"(rc[i][0]), "=v"(rc[i][1]), "=v"(rc[i][2]), "=v"(rc[i][3]));
+    }
 
     LkArgs A = T.lv[level];
     pin_scalar(A.w);
@@ -151,6 +181,10 @@ __device__ __forceinline__ void lk_wave_pair(const LkTable &T, int level, int ti
     }
     int axx[4] = {0, 0, 0, 0}, ayy[4] = {0, 0, 0, 0}, axy[4] = {0, 0, 0, 0}, axt[4] = {0, 0, 0, 0}, ayt[4] = {0, 0, 0, 0};
 
+    // a step of A that emits nothing leaves its slot of the line undefined (no copy to keep what it held)
+    auto no_rcp = [](double (&q)[4]) {
+        if constexpr (SHARE) asm("" : "=v"(q[0]), "=v"(q[1]), "=v"(q[2]), "=v"(q[3])); // (ONE asm: four alike are merged, then copied)
+    };
     // the warped row the step before prepared, into the ring (columns outside the image: zeros)
     auto ring_warped = [&](int y) {
         const uint32_t wn = finish_row(warp_row_finish(WA));
@@ -200,7 +234,8 @@ __device__ __forceinline__ void lk_wave_pair(const LkTable &T, int level, int ti
                 for (int j = 0; j < 4; ++j) va[0][j] = axx[j], va[1][j] = ayy[j], va[2][j] = axy[j], va[3][j] = axt[j], va[4][j] = ayt[j];
                 hbox4x5<R>(va, hb);
             }
-            solve_lane<MODE, FAST>(hb[0], hb[1], hb[2], hb[3], hb[4], sopt, uv);
+            if constexpr (SHARE) solve_lane_rcp_out<MODE, FAST>(hb[0], hb[1], hb[2], hb[3], hb[4], sopt, rq[0][k], uv);
+            else solve_lane<MODE, FAST>(hb[0], hb[1], hb[2], hb[3], hb[4], sopt, uv);
             uv[0] = old_a.x + uv[0], uv[1] = old_a.y + uv[1], uv[2] = old_a.z + uv[2], uv[3] = old_a.w + uv[3];
             uv[4] = old_b.x + uv[4], uv[5] = old_b.y + uv[5], uv[6] = old_b.z + uv[6], uv[7] = old_b.w + uv[7];
             // the warped row of the step before: second stage, into the ring (the first emitting step has none pending: its row
@@ -211,7 +246,7 @@ __device__ __forceinline__ void lk_wave_pair(const LkTable &T, int level, int ti
             const lds_ptr fr = fring + fslot(yw);
             *(__attribute__((address_space(3))) f32x4 *)(fr) = f32x4{uv[0], uv[1], uv[2], uv[3]};
             *(__attribute__((address_space(3))) f32x4 *)(fr + 16) = f32x4{uv[4], uv[5], uv[6], uv[7]};
-        }
+        } else no_rcp(rq[0][k]);
         unpack_pk(finish_row(pf_ip), finish_row(pf_in), finish_row(pf_op), finish_row(pf_on), wa[k]);
         pin_row(wa[k]);
     };
@@ -260,7 +295,7 @@ __device__ __forceinline__ void lk_wave_pair(const LkTable &T, int level, int ti
             __builtin_amdgcn_raw_buffer_store_b64(u32x2{qh.x, qh.y}, rs_flow, st_hi2 ? l16 + 1024u : (uint32_t)kOob, fso, kLkStoreAux);
         }
     };
-    auto stepB = [&](auto K, int s) {
+    auto stepB = [&](auto K, int s, [[maybe_unused]] const double (&rcp)[4]) {
         constexpr int k = decltype(K)::value; // s mod 3
         const int yy = y_lo0B + s, yo = yy - NS;
         const bool folded = H > 0 && s < H;
@@ -301,7 +336,8 @@ __device__ __forceinline__ void lk_wave_pair(const LkTable &T, int level, int ti
                 for (int j = 0; j < 4; ++j) va[0][j] = bxx[j], va[1][j] = byy[j], va[2][j] = bxy[j], va[3][j] = bxt[j], va[4][j] = byt[j];
                 hbox4x5<R>(va, hb);
             }
-            solve_lane<MODE, FAST>(hb[0], hb[1], hb[2], hb[3], hb[4], sopt, uv);
+            if constexpr (SHARE) solve_lane_rcp_in<MODE, FAST>(hb[0], hb[1], hb[2], hb[3], hb[4], sopt, rcp, uv);
+            else solve_lane<MODE, FAST>(hb[0], hb[1], hb[2], hb[3], hb[4], sopt, uv);
             uv[0] = old_a.x + uv[0], uv[1] = old_a.y + uv[1], uv[2] = old_a.z + uv[2], uv[3] = old_a.w + uv[3];
             uv[4] = old_b.x + uv[4], uv[5] = old_b.y + uv[5], uv[6] = old_b.z + uv[6], uv[7] = old_b.w + uv[7];
             if constexpr (WOUT) { // the warped image of iteration j + 2, as ITER = 2 writes it (lk_wave_buf)
@@ -327,8 +363,25 @@ __device__ __forceinline__ void lk_wave_pair(const LkTable &T, int level, int ti
     auto body = [&](auto K, int t) {
         constexpr int k = decltype(K)::value;                    // t mod 3
         constexpr int kb = (k + 3 - kLagSteps % 3) % 3;          // (t - kLagSteps) mod 3
+        // what A made R + 2 steps ago comes out of the line BEFORE A's part of this step writes slot k again
+        [[maybe_unused]] double rcpB[4];
+        if constexpr (SHARE) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const double out = rq[QD - 1][k][j];
+                rcpB[j] = QE > 0 ? rc[QE > 0 ? QE - 1 : 0][j] : out;
+#pragma unroll
+                for (int i = QE - 1; i > 0; --i) rc[i][j] = rc[i - 1][j];
+                if constexpr (QE > 0) rc[0][j] = out;
+#pragma unroll
+                for (int i = QD - 1; i > 0; --i) rq[i][k][j] = rq[i - 1][k][j];
+            }
+        }
         if (t < nstepsA) stepA(K, t);
-        else if (t == nstepsA) ring_warped(yeA - 1);
+        else {
+            if (t == nstepsA) ring_warped(yeA - 1);
+            no_rcp(rq[0][k]);
+        }
         if (t >= kLagSteps) {
             // (what A has just put into the rings is read by other lanes: LDS operations of a wave execute in order)
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -336,7 +389,7 @@ __device__ __forceinline__ void lk_wave_pair(const LkTable &T, int level, int ti
             if constexpr (kb == 0) {
                 if (t == kLagSteps) primeB();
             }
-            stepB(std::integral_constant<int, kb>{}, t - kLagSteps);
+            stepB(std::integral_constant<int, kb>{}, t - kLagSteps, rcpB);
         }
     };
     int s = 0;

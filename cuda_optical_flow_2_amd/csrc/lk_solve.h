@@ -41,11 +41,10 @@ struct SolveOpts {
     float min_det; // <= 0: the reference (no guard)
 };
 
-// the reference's operation order from the converted operands and the determinant on (exact replay)
+// the reference's operation order from the converted operands and pre = 1 / det on (exact replay)
 template <int MODE>
-__device__ __forceinline__ void solve_tail_exact(double a, double b, double d, double xt, double yt, double det, float &u, float &v)
+__device__ __forceinline__ void solve_tail_pre(double a, double b, double d, double xt, double yt, double pre, float &u, float &v)
 {
-    const double pre = recip_f64(det);
     double c = b;
     a *= pre;
     b *= pre;
@@ -53,6 +52,13 @@ __device__ __forceinline__ void solve_tail_exact(double a, double b, double d, d
     d *= pre;
     u = (float)(-d * xt + b * yt);
     v = (float)(c * xt - a * yt);
+}
+
+// ... and from the determinant on
+template <int MODE>
+__device__ __forceinline__ void solve_tail_exact(double a, double b, double d, double xt, double yt, double det, float &u, float &v)
+{
+    solve_tail_pre<MODE>(a, b, d, xt, yt, recip_f64(det), u, v);
 }
 
 // FAST: lk_float only.  The reference computes u = -(d/det)*xt + (b/det)*yt in double and rounds to float.  Here the
@@ -88,19 +94,38 @@ __device__ __forceinline__ void solve_operands(int sxx, int syy, int sxy, int sx
     }
 }
 
-// returns the wave mask of the lanes whose determinant is zero (their u, v are not the reference's yet: solve_fix_singular)
-__device__ __forceinline__ unsigned long long solve_fast(int sxx, int syy, int sxy, int sxt, int syt, float &u, float &v)
+// Where the reciprocal of a solve comes from (the fused two-iteration launch, lk_body_pair.h: its second march meets the very
+// sxx, syy, sxy its first one had at a pixel, hence the same det and the same reciprocal, bit for bit):
+//   kRcpOwn   computed here and kept here (every other caller);
+//   kRcpOut   computed here and handed out: the exact solve's correctly rounded 1 / det (+-Inf where det == 0), the fast solve's
+//             p after its Newton step, which is NaN where det == 0 (rcp gives Inf, fma(-0, Inf, 1) NaN) and finite elsewhere;
+//   kRcpIn    taken from a kRcpOut solve of the same three sums: neither det nor the reciprocal is computed.
+enum { kRcpOwn = 0, kRcpOut = 1, kRcpIn = 2 };
+
+// returns the wave mask of the lanes whose determinant is zero (their u, v are not the reference's yet: solve_fix_singular);
+// kRcpIn reads that off p, which is NaN there and nowhere else
+template <int RCP>
+__device__ __forceinline__ unsigned long long solve_fast_rcp(int sxx, int syy, int sxy, int sxt, int syt, double &p, float &u, float &v)
 {
     double a, b, d, xt, yt, det;
     solve_operands<OFX_MODE_LK_FLOAT>(sxx, syy, sxy, sxt, syt, a, b, d, xt, yt, det);
     const double nu = __builtin_fma(b, yt, -(d * xt));
     const double nv = __builtin_fma(b, xt, -(a * yt));
-    double p = __builtin_amdgcn_rcp(det);
-    const double e = __builtin_fma(-det, p, 1.0);
-    p = __builtin_fma(p, e, p);
+    if constexpr (RCP != kRcpIn) {
+        p = __builtin_amdgcn_rcp(det);
+        const double e = __builtin_fma(-det, p, 1.0);
+        p = __builtin_fma(p, e, p);
+    }
     u = (float)(nu * p);
     v = (float)(nv * p);
-    return __ballot(det == 0.0);
+    if constexpr (RCP == kRcpIn) return __ballot(p != p);
+    else return __ballot(det == 0.0);
+}
+
+__device__ __forceinline__ unsigned long long solve_fast(int sxx, int syy, int sxy, int sxt, int syt, float &u, float &v)
+{
+    double p;
+    return solve_fast_rcp<kRcpOwn>(sxx, syy, sxy, sxt, syt, p, u, v);
 }
 
 // the rare path behind solve_fast: the lanes of `zero` take the replay's result
@@ -148,17 +173,18 @@ __device__ __forceinline__ void solve2x2(int sxx, int syy, int sxy, int sxt, int
     }
 }
 
-// The 4 pixels of a lane of the level kernel.
-template <int MODE, bool FAST>
-__device__ __forceinline__ void solve_lane(const int (&sxx)[4], const int (&syy)[4], const int (&sxy)[4], const int (&sxt)[4],
-                                           const int (&syt)[4], const SolveOpts &opt, float (&uv)[8])
+// The 4 pixels of a lane of the level kernel; rcp: their reciprocals, out or in (RCP, above).  The guard computes its own
+// determinant on its rare branch whatever RCP is.
+template <int MODE, bool FAST, int RCP>
+__device__ __forceinline__ void solve_lane_rcp(const int (&sxx)[4], const int (&syy)[4], const int (&sxy)[4], const int (&sxt)[4],
+                                               const int (&syt)[4], const SolveOpts &opt, double (&rcp)[4], float (&uv)[8])
 {
     if constexpr (FAST) {
         // (pixel by pixel: a pixel's five sums die with its solve -- one branch per row step for all four pixels kept all
         // twenty sums alive for the singular path and spilled)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            if (__builtin_expect(solve_fast(sxx[j], syy[j], sxy[j], sxt[j], syt[j], uv[2 * j], uv[2 * j + 1]) != 0ull, 0)) {
+            if (__builtin_expect(solve_fast_rcp<RCP>(sxx[j], syy[j], sxy[j], sxt[j], syt[j], rcp[j], uv[2 * j], uv[2 * j + 1]) != 0ull, 0)) {
                 asm volatile("" : "+v"(uv[2 * j]), "+v"(uv[2 * j + 1]));
                 solve_fix_singular(sxx[j], syy[j], sxy[j], sxt[j], syt[j], uv[2 * j], uv[2 * j + 1]);
             }
@@ -168,7 +194,8 @@ __device__ __forceinline__ void solve_lane(const int (&sxx)[4], const int (&syy)
         for (int j = 0; j < 4; ++j) {
             double a, b, d, xt, yt, det;
             solve_operands<MODE>(sxx[j], syy[j], sxy[j], sxt[j], syt[j], a, b, d, xt, yt, det);
-            solve_tail_exact<MODE>(a, b, d, xt, yt, det, uv[2 * j], uv[2 * j + 1]);
+            if constexpr (RCP != kRcpIn) rcp[j] = recip_f64(det);
+            solve_tail_pre<MODE>(a, b, d, xt, yt, rcp[j], uv[2 * j], uv[2 * j + 1]);
         }
     }
     if (__builtin_expect(opt.min_det > 0.0f, 0)) {
@@ -176,4 +203,29 @@ __device__ __forceinline__ void solve_lane(const int (&sxx)[4], const int (&syy)
 #pragma unroll
         for (int j = 0; j < 4; ++j) solve_guard<MODE>(sxx[j], syy[j], sxy[j], opt.min_det, uv[2 * j], uv[2 * j + 1]);
     }
+}
+
+template <int MODE, bool FAST>
+__device__ __forceinline__ void solve_lane(const int (&sxx)[4], const int (&syy)[4], const int (&sxy)[4], const int (&sxt)[4],
+                                           const int (&syt)[4], const SolveOpts &opt, float (&uv)[8])
+{
+    double rcp[4];
+    solve_lane_rcp<MODE, FAST, kRcpOwn>(sxx, syy, sxy, sxt, syt, opt, rcp, uv);
+}
+
+// solve_lane, and the four reciprocals it used go out ...
+template <int MODE, bool FAST>
+__device__ __forceinline__ void solve_lane_rcp_out(const int (&sxx)[4], const int (&syy)[4], const int (&sxy)[4], const int (&sxt)[4],
+                                                   const int (&syt)[4], const SolveOpts &opt, double (&rcp)[4], float (&uv)[8])
+{
+    solve_lane_rcp<MODE, FAST, kRcpOut>(sxx, syy, sxy, sxt, syt, opt, rcp, uv);
+}
+
+// ... and solve_lane with the reciprocals of a solve_lane_rcp_out on the same sxx, syy, sxy
+template <int MODE, bool FAST>
+__device__ __forceinline__ void solve_lane_rcp_in(const int (&sxx)[4], const int (&syy)[4], const int (&sxy)[4], const int (&sxt)[4],
+                                                  const int (&syt)[4], const SolveOpts &opt, const double (&rcp)[4], float (&uv)[8])
+{
+    double r[4] = {rcp[0], rcp[1], rcp[2], rcp[3]};
+    solve_lane_rcp<MODE, FAST, kRcpIn>(sxx, syy, sxy, sxt, syt, opt, r, uv);
 }
