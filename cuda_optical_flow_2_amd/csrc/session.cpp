@@ -3,153 +3,14 @@
 // One hipMalloc arena holds, per pyramid level: the previous and the next frame's 1-channel planes, a scratch
 // plane for the shifted next frame, the flow field, and the 2-float shift vector.  Nothing is allocated or freed
 // while frames flow (the reference does 58 cudaMalloc/cudaFree calls per level).
-#include <stdlib.h>
-#include <string.h>
-
 #include <new>
-#include <vector>
 
 #include "compat_scratch.h"
-#include "ofx_internal.h"
+#include "session.h"
 
 #ifndef OFX_ITER_PAIRS_DEFAULT
 #define OFX_ITER_PAIRS_DEFAULT 1 // the stream pipeline's iterations two per launch (lk_body_pair.h); OFX_ITER_PAIRS=0 / 1 overrides
 #endif
-namespace {
-constexpr size_t kAlign = 256;
-// The stream pipeline with B frames per tick uses 3B + 2 image sets and 2B shift-vector slots (see stream_tick); the
-// pair-at-a-time paths rotate 3 sets and alternate 2 slots.
-constexpr int kMaxBatch = OFX_STREAM_MAX_BATCH;
-constexpr int kSets = 3 * kMaxBatch + 2;
-constexpr int kUvSlots = 2 * kMaxBatch;
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-} // namespace
-
-struct ofx_session {
-    ofx_params p{};
-    int w[OFX_MAX_LEVELS]{}, h[OFX_MAX_LEVELS]{}, pitch[OFX_MAX_LEVELS]{};
-    int own0[OFX_MAX_LEVELS]{}, own1[OFX_MAX_LEVELS]{}; // rows this rank computes
-    int buf0[OFX_MAX_LEVELS]{}, buf1[OFX_MAX_LEVELS]{}; // rows the plane buffers hold
-    int cmp0[OFX_MAX_LEVELS]{}, cmp1[OFX_MAX_LEVELS]{}; // rows this rank downsamples itself
-    // rows the flow buffers hold: the own rows, or -- sharded sessions with refinement iterations -- the own rows plus
-    // (radius + 1) * (iters - 1) either side: iteration j is computed on (radius + 1) * (iters - j) extra rows so that the
-    // warp of iteration j + 1 finds the flow of every row its LK stencils touch without asking a neighbour (stream_tick)
-    int fl0[OFX_MAX_LEVELS]{}, fl1[OFX_MAX_LEVELS]{};
-    size_t flow_own_offset(int k) const { return (size_t)(own0[k] - fl0[k]) * (size_t)w[k] * 2; } // floats from a flow set to the own rows
-    // storage: three image sets rotate through the roles prev -> (free) -> next, two shifted-scratch sets alternate, so
-    // that the pipelined path can build frame i+1's pyramid / corner / shift while pair i's LK launch is running
-    uint8_t *img[kSets][OFX_MAX_LEVELS]{};              // see kSets
-    uint8_t *sh[2][OFX_MAX_LEVELS]{};
-    // refinement iterations in the stream pipeline: per flow set (pair p -> set p mod B) the shifted and the warped next image
-    uint8_t *itsh[kMaxBatch][3][OFX_MAX_LEVELS]{};
-    bool fused_iters = false; // the accumulating launches also write the next iteration's warped image (lk_body_warp.h)
-    // the stream pipeline runs the iterations after the tick's two per launch (lk_body_pair.h): such a launch reads one flow set and
-    // writes another, so every pair slot has a second set (flowset2); the last launch of a tick always writes flowset
-    bool iter_pairs = false;
-    // the fused launches' plan (lk_launch.h): waves of equal steps (OFX_PAIR_PACK=0: one strip per wave, as before), the wave count
-    // OFX_PAIR_WAVES forces on that plan (0: the device's), and the plans this session has made (freed with it)
-    ofx_pair_opts pair_opts{1, 0, nullptr};
-    ofx_pair_cache *pair_cache = nullptr;
-    float *flowset2[kMaxBatch][OFX_MAX_LEVELS]{};
-    int cur = 0, sht = 0;                               // img[cur] = previous frame, img[(cur+1)%3] = next frame
-    uint8_t *plane[3][OFX_MAX_LEVELS]{};                // role view: 0 prev, 1 next, 2 shifted scratch
-    hipStream_t aux = nullptr;                          // pipelined path: staging stream owned by the session
-    hipEvent_t ev_ready = nullptr;                      // staging of the next pair finished (aux -> main)
-    hipEvent_t ev_set_done[3] = {nullptr, nullptr, nullptr}; // last LK launch that read img[i] as `prev` finished
-    bool set_busy[3] = {false, false, false};
-    bool staged = false;
-    int uv_slot = 0; // shift-vector slot of the pair in progress; alternates per pair so that the staging of the next
-                     // pair (aux stream) never overwrites vectors the running LK launch still reads
-    float *uv_cur() { return uv + (size_t)uv_slot * 2 * OFX_MAX_LEVELS; }
-    long stream_n = -1;      // ticks of the stream pipeline so far (-1: not streaming)
-    long stream_frames = -1; // total frames, known once draining starts (-1: still receiving)
-    int pitch0_next() const { return pitch[0]; }
-    // local_corner: the top-left patch of every frame as a pyramid of its own (same 5 sets as img)
-    uint8_t *pimg[kSets][OFX_MAX_LEVELS]{};
-    int pw[OFX_MAX_LEVELS]{}, ph[OFX_MAX_LEVELS]{}, ppitch[OFX_MAX_LEVELS]{};
-    // stream_two_stage: the patch planes the corner block of slot i builds for its pair (frame 0: previous, 1: next)
-    uint8_t *pscr[kMaxBatch][2][OFX_MAX_LEVELS]{};
-    // the repair of a shift that leaves the patch (ofx_corner_stage.d_patch_reloc): per corner slot one more set of patch planes,
-    // for the next frame's pyramid rebuilt around the shifted corner.  Allocated where the whole frames stay at hand
-    // (borrow_frames) and the chain reads a patch (stream_two_stage, local_corner).
-    uint8_t *preloc[kMaxBatch][OFX_MAX_LEVELS]{};
-    bool repair = false;
-    // pair-at-a-time sessions (neither local_corner nor stream_two_stage, whole frames): ofx_session_build_pyramid also walks the
-    // pair's corner chain in one more block of its launch (pyr_corner.hip) on patch planes that block builds: pscr[0][0 / 1] hold the
-    // patch pyramids of two image sets in turn (pset_img / pset_gen: which set's, and of which load), preloc[0] the repair's planes
-    bool plain_fuse = false;
-    bool corner_done = false; // the shift vectors of the pair (prev, next) are in uv_cur() already
-    int pset_img[2] = {-1, -1};
-    long pset_gen[2] = {0, 0}, img_gen[3] = {0, 0, 0};
-    int debug_extent = 0; // test hook (OFX_DEBUG_CORNER_EXTENT): the chain may only read this many level-0 columns / rows of its patch planes
-    int *corner_status = nullptr;
-    int *pair_status = nullptr; // one word per shift-vector slot (pair p -> slot p mod 2B)
-    const uint8_t *pframe[3] = {nullptr, nullptr, nullptr}; // borrow_frames, pair-at-a-time: the caller's frame behind img[i]'s level 0
-    float *flow[OFX_MAX_LEVELS]{};       // where results are read from: flowset[0], or the newest pair's set in a two-frame stream
-    float *flowset[kMaxBatch][OFX_MAX_LEVELS]{}; // stream pipeline: pair p's flow goes to set p mod stream_batch
-    const uint8_t *held_frame[kMaxBatch]{};      // multi-frame stream tick: the frames waiting for the tick to fill
-    int held_pitch[kMaxBatch]{};
-    int n_held = 0;
-    const uint8_t *bframe[kSets]{}; // borrow_frames: the caller's buffer behind image set i (level 0 is read from there)
-    int bpitch[kSets]{};
-    long reported = 0;                   // highest pair reported complete by the stream pipeline
-    long corner_newest = 0;              // highest pair whose corner stage has been enqueued (ofx_session_pair_status)
-    float *uv = nullptr;        // 2 floats per level
-    uint8_t *staging = nullptr; // one tightly packed 3ch level-0 frame for host uploads
-    void *arena = nullptr;
-    size_t arena_bytes = 0;
-    bool have_next = false, have_prev = false;
-    // optional timing of the level-0 fused LK launch: event pairs recorded on the launch stream
-    bool timing = false;
-    std::vector<hipEvent_t> ev;
-    std::vector<int> ev_kind; // OFX_TIME_* of event pair i
-    size_t ev_used = 0;
-    hipEvent_t ev_frame = nullptr; // staged path: the caller's frame is complete (caller's stream -> aux)
-    int n_sets = 0;                // image sets allocated (3B + 2; the pair-at-a-time paths rotate the first three)
-    // ofx_session_stream_compose: the caller's ring of composed fields (nullptr: off), and the newest pair composed into it
-    float *ring = nullptr;
-    size_t ring_stride = 0; // bytes from slot to slot
-    int ring_slots = 0, ring_level = 0;
-    long composed = 0;
-    // ofx_session_stream_arrows / _stream_tracks (sample_ring.hip): the caller's arrow ring, points, statuses and history ring
-    // (nullptr: off), and the newest pair sampled
-    int32_t *arrow_ring = nullptr;
-    size_t arrow_stride = 0;
-    int arrow_slots = 0, arrow_level = 0, arrow_offset = 0, arrow_ny = 0, arrow_nx = 0;
-    float *trk_points = nullptr, *trk_hist = nullptr;
-    int32_t *trk_status = nullptr;
-    size_t trk_stride = 0;
-    int trk_n = 0, trk_slots = 0, trk_level = 0;
-    long sampled = 0;
-    // ofx_session_stream_frontend: colour frames through the front end (frontend.hip).  fe_mode: what a frame gets
-    // (OFX_FRONTEND_GREY / _BILATERAL / _BILATERAL_FAST), 0 = off; frame 0 of a stream gets OFX_FRONTEND_GREY with
-    // OFX_FRONTEND_FLAG_FIRST_GREY.  borrow_frames: the filtered plane of image set i (fplane[i], at pitch[0]) stands in for the
-    // borrowed frame; otherwise the front end writes img[i][0] and the pyramid stage does not copy level 0.
-    int fe_mode = 0, fe_flags = 0;
-    ofx_frontend_tables *fe = nullptr;
-    void *fe_arena = nullptr;
-    uint8_t *fplane[kSets]{};
-    int stream_input = 0; // what the stream in progress has received: 0 = nothing yet, 1 = grey frames, 2 = colour frames
-};
-
-// Runs `launch` bracketed by a pair of timing events of kind `kind` when the session is armed (ofx_session_timing).
-template <typename F>
-static int timed_launch(ofx_session *s, int kind, void *stream, F &&launch)
-{
-    static const char *const names[OFX_TIME_KINDS] = {"ofx.lk_levels", "ofx.lk_levels_accumulate", "ofx.warp_levels", "ofx.stream_tick",
-                                                      "ofx.shift_levels", "ofx.corner_flows", "ofx.pyramid", "ofx.lk_levels_accumulate_warp",
-                                                      "ofx.compose_ring"};
-    OfxRange range(names[kind]); // (roctx, OFX_ROCTX=1: the launch's enqueue on the host side of a --marker-trace timeline)
-    const bool timed = s->timing && s->ev_used + 2 <= s->ev.size();
-    if (timed) OFX_HIP(hipEventRecord(s->ev[s->ev_used], ofx_stream(stream)));
-    OFX_TRY(launch());
-    if (timed) {
-        OFX_HIP(hipEventRecord(s->ev[s->ev_used + 1], ofx_stream(stream)));
-        s->ev_kind[s->ev_used / 2] = kind;
-        s->ev_used += 2;
-    }
-    return OFX_OK;
-}
 
 static void repoint(ofx_session *s)
 {
@@ -162,19 +23,6 @@ static void repoint(ofx_session *s)
     const size_t skip = (size_t)s->buf0[0] * (size_t)s->pitch[0];
     if (s->pframe[s->cur]) s->plane[0][0] = const_cast<uint8_t *>(s->pframe[s->cur]) + skip;
     if (s->pframe[(s->cur + 1) % 3]) s->plane[1][0] = const_cast<uint8_t *>(s->pframe[(s->cur + 1) % 3]) + skip;
-}
-
-static ofx_geom level_geom(const ofx_session *s, int k, int out0, int out1)
-{
-    ofx_geom g;
-    g.w = s->w[k];
-    g.h = s->h[k];
-    g.pitch = s->pitch[k];
-    g.row0 = s->buf0[k];
-    g.rows = s->buf1[k] - s->buf0[k];
-    g.out_y0 = out0;
-    g.out_y1 = out1;
-    return g;
 }
 
 extern "C" int ofx_session_create(const ofx_params *p_in, ofx_session **out)
@@ -219,11 +67,11 @@ extern "C" int ofx_session_create(const ofx_params *p_in, ofx_session **out)
     s->p = *p;
     // image sets: the stream pipeline cycles through 3B + 2 of them (B = frames per tick; a session created without a
     // stream_batch may still stream one frame per tick), the pair-at-a-time paths rotate the first three
-    const int n_sets = (p->stream_two_stage ? 2 : 3) * (p->stream_batch >= 2 ? p->stream_batch : 1) + 2;
+    const int B = stream_batch_of(s), n_sets = stream_sets(s);
     s->n_sets = n_sets;
     size_t total = 0;
     // (streamed refinement iterations: two more scratch planes per pair of a tick)
-    const int n_iter_sets = p->iters > 1 ? 3 * (p->stream_batch >= 2 ? p->stream_batch : 1) : 0; // per flow set: shifted, warped, warped'
+    const int n_iter_sets = p->iters > 1 ? 3 * B : 0; // per flow set: shifted, warped, warped'
     std::vector<size_t> off_plane[kSets + 2 + 3 * kMaxBatch], off_flow, off_flow2, off_flow_alt, flow_stride;
     // Two iterations per launch in the stream pipeline (lk_body_pair.h): unsharded lk_float sessions with three iterations or more,
     // windows up to 9x9, levels that do not take the deep fetch (below 16 Mpx).  OFX_ITER_PAIRS=0 / 1 overrides the default.
@@ -231,7 +79,6 @@ extern "C" int ofx_session_create(const ofx_params *p_in, ofx_session **out)
                             (p->window >> 1) >= 1 && (p->window >> 1) <= 4 && (long)p->width * p->height < 16l * 1000 * 1000 &&
                             [] { const char *e = getenv("OFX_ITER_DMA"); return !e || atoi(e) <= 0; }() &&
                             [] { const char *e = getenv("OFX_ITER_PAIRS"); return e ? atoi(e) != 0 : OFX_ITER_PAIRS_DEFAULT != 0; }();
-    const int n_flow_slots = p->stream_batch >= 2 ? p->stream_batch : 1;
     for (int k = 0; k < p->levels; ++k) {
         s->w[k] = p->width >> k;
         s->h[k] = p->height >> k;
@@ -282,13 +129,12 @@ extern "C" int ofx_session_create(const ofx_params *p_in, ofx_session **out)
         const size_t flow_bytes = align_up((own_rows ? own_rows : 1) * (size_t)s->w[k] * 2 * sizeof(float), kAlign);
         total += flow_bytes;
         off_flow2.push_back(total); // further flow sets: a B-frame stream tick writes the flows of B pairs
-        if (p->stream_batch >= 2) total += flow_bytes * (size_t)(p->stream_batch - 1);
+        total += flow_bytes * (size_t)(B - 1);
         flow_stride.push_back(flow_bytes);
     }
     std::vector<size_t> off_patch[kSets];
     std::vector<size_t> off_pscr; // (per level; slot i, frame f at + (F i + f) * pscr_frame, F = frames per slot)
     size_t pscr_frame = 0;
-    const int n_slots = p->stream_batch >= 2 ? p->stream_batch : 1;
     size_t patch_bytes[OFX_MAX_LEVELS] = {};
     // OFX_PLAIN_FUSED=1: the pair-at-a-time path's pyramid launch carries the pair's corner chain (two launches per pair instead of
     // three).  Off by default: measured SLOWER -- the chain's block takes 42-57 us (28-44 of them its patch build) against 13.5
@@ -356,7 +202,7 @@ extern "C" int ofx_session_create(const ofx_params *p_in, ofx_session **out)
             }
         }
         const size_t off_pscr_base = total;
-        total += pscr_frame * (size_t)frames_per_slot * (size_t)n_slots;
+        total += pscr_frame * (size_t)frames_per_slot * (size_t)B;
         for (size_t &o : off_pscr) o += off_pscr_base;
     }
     const size_t off_status = total; // the sticky word, then one word per shift-vector slot
@@ -368,7 +214,7 @@ extern "C" int ofx_session_create(const ofx_params *p_in, ofx_session **out)
     // the second flow set of every pair slot, behind everything else: the first sets lie where they do without it
     for (int k = 0; k < p->levels; ++k) {
         off_flow_alt.push_back(total);
-        if (want_pairs) total += flow_stride[k] * (size_t)n_flow_slots;
+        if (want_pairs) total += flow_stride[k] * (size_t)B;
     }
 
     hipError_t e = hipMalloc(&s->arena, total);
@@ -394,12 +240,12 @@ extern "C" int ofx_session_create(const ofx_params *p_in, ofx_session **out)
         for (int t = 1; t < kMaxBatch; ++t)
             s->flowset[t][k] = reinterpret_cast<float *>(base + (t < p->stream_batch ? off_flow2[k] + (size_t)(t - 1) * flow_stride[k] : off_flow[k]));
         s->flow[k] = s->flowset[0][k];
-        for (int t = 0; t < n_flow_slots && want_pairs; ++t) s->flowset2[t][k] = reinterpret_cast<float *>(base + off_flow_alt[k] + (size_t)t * flow_stride[k]);
+        for (int t = 0; t < B && want_pairs; ++t) s->flowset2[t][k] = reinterpret_cast<float *>(base + off_flow_alt[k] + (size_t)t * flow_stride[k]);
     }
     if (p->local_corner && !p->stream_two_stage)
         for (int k = 0; k < p->levels; ++k)
             for (int t = 0; t < n_sets; ++t) s->pimg[t][k] = base + off_patch[t][k];
-    for (int i = 0; i < n_slots && frames_per_slot > 0; ++i)
+    for (int i = 0; i < B && frames_per_slot > 0; ++i)
         for (int k = 1; k < p->levels; ++k) {
             uint8_t *slot = base + off_pscr[k] + (size_t)(frames_per_slot * i) * pscr_frame;
             if (p->stream_two_stage || s->plain_fuse) {
@@ -420,6 +266,8 @@ extern "C" int ofx_session_create(const ofx_params *p_in, ofx_session **out)
         (size_t)(s->buf1[0] - s->buf0[0]) * (size_t)s->w[0] * 8 >= ((size_t)1 << 31))
         s->fused_iters = false;
     s->iter_pairs = want_pairs && s->fused_iters;
+    s->n_iter_pass = ofx_plan::iter_plan_make(p->iters, s->fused_iters, s->iter_pairs, s->iter_plan);
+    s->n_iter_pass1 = ofx_plan::iter_plan_make(p->iters, s->fused_iters, false, s->iter_plan1);
     s->pair_opts.pack = [] { const char *e = getenv("OFX_PAIR_PACK"); return !e || atoi(e) != 0; }() ? 1 : 0;
     s->pair_opts.waves = [] { const char *e = getenv("OFX_PAIR_WAVES"); return e && atoi(e) > 0 ? atoi(e) : 0; }();
     s->pair_opts.cache = &s->pair_cache;
@@ -729,6 +577,7 @@ static int lk_all_levels(ofx_session *s, const float *uv, void *stream)
     auto src = [&](int k) { return k == L - 1 ? s->plane[1][k] : s->sh[0][k]; };
     // The warped image alternates between two planes (sh[1] and the iteration scratch's third): fused (lk_body_warp.h), every launch
     // but the last writes the warped image the iteration after it reads, from the flow it has in registers -- no warp launch at all.
+    // Which plane a launch reads and writes is the schedule's (iter_plan.h); iteration 1 writes plane 0.
     uint8_t *const *wbuf[2] = {s->sh[1], s->itsh[0][2]};
     int nl = 0;
     for (int k = L - 1; k >= 0; --k) {
@@ -737,34 +586,20 @@ static int lk_all_levels(ofx_session *s, const float *uv, void *stream)
         ++nl;
     }
     OFX_TRY(timed_lk_launch(s, lk, nl, stream));
-    for (int it = 1; it < s->p.iters; ++it) {
-        const bool fused = s->fused_iters, need_warp = !fused, wout = fused && it + 1 < s->p.iters;
-        uint8_t *const *win = fused ? wbuf[(it - 1) & 1] : s->sh[1], *const *wnext = wbuf[it & 1];
+    for (int i = 0; i < s->n_iter_pass1; ++i) {
+        const ofx_plan::IterPass &q = s->iter_plan1[i];
         ofx_warp_desc wd[OFX_MAX_LEVELS];
         nl = 0;
         for (int k = L - 1; k >= 0; --k) {
-            wd[nl] = ofx_warp_desc{src(k), win[k], level_geom(s, k, 0, s->h[k]), s->flow[k], 0, OFX_ITER_SCALE, nullptr, 0};
-            lk[nl] = ofx_lk_desc{s->plane[0][k], win[k], level_geom(s, k, 0, s->h[k]), s->flow[k], 0, nullptr, 1, s->p.min_det};
-            if (wout) lk[nl].d_warp_src = src(k), lk[nl].d_warp_out = wnext[k], lk[nl].warp_scale = OFX_ITER_SCALE;
+            wd[nl] = ofx_warp_desc{src(k), wbuf[q.win][k], level_geom(s, k, 0, s->h[k]), s->flow[k], 0, OFX_ITER_SCALE, nullptr, 0};
+            lk[nl] = ofx_lk_desc{s->plane[0][k], wbuf[q.win][k], level_geom(s, k, 0, s->h[k]), s->flow[k], 0, nullptr, 1, s->p.min_det};
+            if (q.wout) lk[nl].d_warp_src = src(k), lk[nl].d_warp_out = wbuf[q.wo][k], lk[nl].warp_scale = OFX_ITER_SCALE;
             ++nl;
         }
-        if (need_warp) OFX_TRY(timed_launch(s, OFX_TIME_WARP, stream, [&] { return ofx_warp_levels(wd, nl, stream); }));
+        if (q.warp) OFX_TRY(timed_launch(s, OFX_TIME_WARP, stream, [&] { return ofx_warp_levels(wd, nl, stream); }));
         OFX_TRY(timed_lk_launch(s, lk, nl, stream));
     }
     return OFX_OK;
-}
-
-// per level: the image rows the LK stencils of this shard's own rows touch (before the shift) and the rows its buffers hold
-static void shard_reach(const ofx_session *s, int (*rows)[4])
-{
-    const int reach = s->p.window / 2 + 1; // the LK stencil of the rows it computes reaches radius + 1 rows beyond them
-    for (int k = 0; k < s->p.levels; ++k) {
-        const int n0 = s->fl0[k] - reach, n1 = s->fl1[k] + reach;
-        rows[k][0] = n0 < 0 ? 0 : n0;
-        rows[k][1] = n1 > s->h[k] ? s->h[k] : n1;
-        rows[k][2] = s->buf0[k]; // (rows outside comp but inside buf are the caller's to fill: the halo exchange)
-        rows[k][3] = s->buf1[k];
-    }
 }
 
 extern "C" int ofx_session_run_levels(ofx_session *s, void *stream)
@@ -962,7 +797,7 @@ extern "C" int ofx_session_corner_status(ofx_session *s, int *h_status, void *st
 extern "C" int ofx_session_pair_status(ofx_session *s, int pair, int *h_status, void *stream)
 {
     OFX_REQUIRE(s && h_status, "ofx_session_pair_status: null argument");
-    const int slots = 2 * (s->p.stream_batch >= 2 ? s->p.stream_batch : 1);
+    const int slots = 2 * stream_batch_of(s);
     OFX_REQUIRE(pair >= 1, "ofx_session_pair_status: pairs are counted from 1 (frame 0 -> frame 1)");
     OFX_REQUIRE(pair <= s->corner_newest && pair > s->corner_newest - slots,
                 "ofx_session_pair_status: pair %d is not among the newest %d pairs whose corner stage has run (newest: %ld)", pair, slots, s->corner_newest);
@@ -971,706 +806,6 @@ extern "C" int ofx_session_pair_status(ofx_session *s, int pair, int *h_status, 
     OFX_HIP(hipStreamSynchronize(st));
     return OFX_OK;
 }
-
-// ---- stream pipeline: one launch per tick of B frames ----------------------------------------------------------------
-// Frame f (0-based) belongs to tick f / B (B = stream_batch: 1, 2 or 4).  Pair p is (frame p-1 -> frame p).  The tick
-// whose first frame is f0 runs, side by side in one grid,
-//     pyramid(frames f0 .. f0+B-1) | corner(pairs f0-B .. f0-1) | LK(pairs f0-2B .. f0-B-1, shift fused)
-// (with ofx_params.stream_two_stage: pyramid(f0 .. f0+B-1) | corner(pairs f0 .. f0+B-1, on patch pyramids the corner blocks
-// build themselves) | LK(pairs f0-B .. f0-1): 2B + 2 image sets, a pair done one tick earlier)
-// so every stage consumes what earlier ticks wrote and the ticks are ordered by the stream.  Frame f lives in image set
-// f mod (3B+2) and pair p's shift vectors in slot p mod 2B: a set is last read by LK(pair f+1), at the latest in the tick
-// that starts with frame f+2B+1, and rewritten by the tick that holds frame f+3B+2; a slot is read by LK(pair p) one tick
-// after the corner stage wrote it and rewritten two ticks after.  The flows of pair p go to flow set p mod B.  After a
-// tick every pair <= f0-B-1 is done.
-static int stream_batch_of(const ofx_session *s) { return s->p.stream_batch >= 2 ? s->p.stream_batch : 1; }
-// image sets the stream pipeline cycles through: (D + 1) B + 2 (stream_tick)
-static int stream_sets(const ofx_session *s) { return (s->p.stream_two_stage ? 2 : 3) * stream_batch_of(s) + 2; }
-
-// One launch composing pairs first .. last (the pairs a call of the pipeline completes) into their ring slots.
-static int compose_ring(ofx_session *s, long first, long last, void *stream)
-{
-    const int B = stream_batch_of(s), lv = s->ring_level;
-    static thread_local ofx_compose_batch cb; // (1.7 KB)
-    memset(&cb, 0, sizeof cb);
-    cb.w = s->w[lv];
-    cb.rows = s->own1[lv] - s->own0[lv];
-    cb.n_px = (unsigned)((size_t)cb.w * (size_t)cb.rows);
-    cb.levels = s->p.levels;
-    cb.level = lv;
-    for (int k = 0; k < s->p.levels; ++k) cb.own0[k] = s->own0[k];
-    for (long p = first; p <= last; ++p, ++cb.n) {
-        for (int k = lv; k < s->p.levels; ++k) cb.lv[cb.n][k] = s->flowset[p % B][k] + s->flow_own_offset(k);
-        cb.dst[cb.n] = reinterpret_cast<float *>(reinterpret_cast<char *>(s->ring) + (size_t)((p - 1) % s->ring_slots) * s->ring_stride);
-    }
-    s->composed = last;
-    return timed_launch(s, OFX_TIME_COMPOSE, stream, [&] { return ofx_compose_batch_launch(&cb, stream); });
-}
-
-// One launch sampling pairs first .. last: their arrow fields into the arrow ring, the tracked points through them in order.
-static int sample_ring(ofx_session *s, long first, long last, void *stream)
-{
-    const int B = stream_batch_of(s);
-    static thread_local ofx_sample_batch sb; // (2 KB)
-    memset(&sb, 0, sizeof sb);
-    sb.levels = s->p.levels;
-    for (int k = 0; k < s->p.levels; ++k) sb.own0[k] = s->own0[k];
-    if (s->arrow_ring) {
-        sb.a_level = s->arrow_level, sb.a_w = s->w[s->arrow_level], sb.a_h = s->h[s->arrow_level];
-        sb.a_offset = s->arrow_offset, sb.a_ny = s->arrow_ny, sb.a_nx = s->arrow_nx;
-    }
-    if (s->trk_points) {
-        sb.points = s->trk_points, sb.status = s->trk_status, sb.n_points = s->trk_n;
-        sb.t_level = s->trk_level, sb.t_w = s->w[s->trk_level], sb.t_h = s->h[s->trk_level];
-        sb.pair0 = (int)first;
-    }
-    for (long p = first; p <= last; ++p, ++sb.n) {
-        for (int k = 0; k < s->p.levels; ++k) sb.lv[sb.n][k] = s->flowset[p % B][k] + s->flow_own_offset(k);
-        if (s->arrow_ring)
-            sb.arrows[sb.n] = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(s->arrow_ring) + (size_t)((p - 1) % s->arrow_slots) * s->arrow_stride);
-        if (s->trk_points && s->trk_hist)
-            sb.hist[sb.n] = reinterpret_cast<float *>(reinterpret_cast<char *>(s->trk_hist) + (size_t)((p - 1) % s->trk_slots) * s->trk_stride);
-    }
-    s->sampled = last;
-    OfxRange range("ofx.sample_ring");
-    return ofx_sample_batch_launch(&sb, stream);
-}
-
-static int stream_tick(ofx_session *s, const uint8_t *const *frames, const int *pitches, int n_frames, void *stream, int *completed_pair)
-{
-    const int B = stream_batch_of(s);
-    // D = ticks between a frame's arrival and the LK stage of the pair it completes: 2 (pyramid | corner | LK), or 1 with
-    // stream_two_stage (the corner stage runs in the frame's own tick, on patch pyramids it builds itself)
-    const int D = s->p.stream_two_stage ? 1 : 2;
-    const int sets = (D + 1) * B + 2, slots = 2 * B;
-    const long f0 = s->stream_n; // index of the first frame of this tick
-    const int L = s->p.levels;
-    auto uvslot = [&](long pair) { return s->uv + (size_t)(pair % slots) * 2 * OFX_MAX_LEVELS; };
-    auto set_of = [&](long frame) { return (int)(frame % sets); };
-    const long last_frame = s->stream_frames >= 0 ? s->stream_frames - 1 : f0 + n_frames - 1;
-    // level k of a frame as the LK / corner stages see it: the session's plane, or (borrow_frames, level 0) the caller's buffer
-    auto plane_of = [&](long frame, int k) -> const uint8_t * {
-        const int set = set_of(frame);
-        if (k == 0 && s->p.borrow_frames) return s->bframe[set] + (size_t)s->buf0[0] * (size_t)s->bpitch[set];
-        return s->img[set][k];
-    };
-    auto patch_of = [&](long frame, int k) -> const uint8_t * {
-        const int set = set_of(frame);
-        return (k == 0 && s->p.borrow_frames) ? s->bframe[set] : s->pimg[set][k];
-    };
-    auto pitch_of = [&](long frame, int k, bool patch) {
-        if (k == 0 && s->p.borrow_frames) return s->bpitch[set_of(frame)];
-        return patch ? s->ppitch[k] : s->pitch[k];
-    };
-    // columns / rows of level k's patch planes the corner chain may read (all of them, unless the test hook narrows them)
-    auto chain_extent = [&](int k, int full) {
-        if (s->debug_extent <= 0 || k == 0) return full;
-        const int need = (s->p.window >> 1) + 2, lim = s->debug_extent >> k;
-        const int e = lim > need ? lim : need;
-        return e < full ? e : full;
-    };
-    // the stages struct is several KB: keep it off the stack of callers with small stacks
-    static thread_local ofx_stream_stages g;
-    memset(&g, 0, sizeof g);
-    for (int i = 0; i < n_frames; ++i) { // pyramid(frame f0 + i)
-        OFX_REQUIRE(pitches[i] >= s->w[0] && (pitches[i] & 3) == 0 && ((uintptr_t)frames[i] & 3) == 0,
-                    "ofx_session_stream_submit: frame must be 4-byte aligned with a pitch multiple of 4 and >= width");
-        if (s->p.borrow_frames && f0 + i >= 1)
-            OFX_REQUIRE(pitches[i] == s->bpitch[set_of(f0 + i - 1)] || (i > 0 && pitches[i] == pitches[i - 1]),
-                        "ofx_session_stream_submit: borrowed frames must all have the same pitch");
-        ofx_pyramid_stage &P = g.pyr[g.n_pyr++];
-        const int set = set_of(f0 + i);
-        P.d_frame = frames[i];
-        P.frame_pitch = pitches[i];
-        P.w = s->w[0];
-        P.h = s->h[0];
-        P.levels = L;
-        P.windowed = s->p.sharded ? 1 : 0;
-        for (int k = 0; k < L; ++k) {
-            P.d_levels[k] = s->img[set][k];
-            P.pitches[k] = s->pitch[k];
-            P.row0[k] = s->buf0[k];
-            P.rows[k] = s->buf1[k] - s->buf0[k];
-        }
-        if (s->p.local_corner && D == 2) { // the same frame's top-left patch, as a pyramid of its own
-            P.patch_w = s->pw[0];
-            P.patch_h = s->ph[0];
-            P.patch_levels = L;
-            for (int k = 0; k < L; ++k) {
-                P.d_patch_levels[k] = s->pimg[set][k];
-                P.patch_pitches[k] = s->ppitch[k];
-            }
-        }
-        if (s->p.borrow_frames) { // no copies of level 0: the later stages read the caller's buffer
-            s->bframe[set] = frames[i];
-            s->bpitch[set] = pitches[i];
-            P.d_levels[0] = nullptr;
-            P.d_patch_levels[0] = nullptr;
-        } else if (s->stream_input == 2) { // the front end wrote level 0 of the set itself (frontend_tick): nothing to copy
-            P.d_levels[0] = nullptr;
-        }
-    }
-    for (long pc = f0 - (D - 1) * B; pc <= f0 - (D - 1) * B + B - 1; ++pc) { // corner(pair pc)
-        if (pc < 1 || pc > last_frame) continue;
-        const int slot_i = g.n_corner;
-        if (pc > s->corner_newest) s->corner_newest = pc;
-        ofx_corner_stage &C = g.corner[g.n_corner++];
-        C.levels = L;
-        C.d_uv = uvslot(pc);
-        if (D == 1) {
-            // two stages: the pair's second frame arrived with this tick; the block builds the patch pyramids of both frames
-            // (levels >= 1) into its slot's planes and walks the chain on them (level 0: the frames themselves, borrowed)
-            C.build_patch = 1;
-            C.patch_w = s->pw[0];
-            C.patch_h = s->ph[0];
-            for (int f = 0; f < 2; ++f) {
-                C.d_patch_src[f] = s->bframe[set_of(pc - 1 + f)];
-                C.patch_src_pitch[f] = s->bpitch[set_of(pc - 1 + f)];
-            }
-            for (int k = 0; k < L; ++k) {
-                C.patch_pitch[k] = s->ppitch[k];
-                C.d_patch[0][k] = s->pscr[slot_i][0][k];
-                C.d_patch[1][k] = s->pscr[slot_i][1][k];
-                C.d_patch_reloc[k] = s->repair ? s->preloc[slot_i][k] : nullptr;
-                const uint8_t *pp = k ? s->pscr[slot_i][0][k] : C.d_patch_src[0], *pn = k ? s->pscr[slot_i][1][k] : C.d_patch_src[1];
-                // level 0 is the frames themselves, whole (every rank of a sharded stream is handed whole frames)
-                ofx_geom pg{s->w[k], s->h[k], k ? s->ppitch[k] : C.patch_src_pitch[1], 0, k ? chain_extent(k, s->ph[k]) : s->h[0], 0,
-                            k ? chain_extent(k, s->ph[k]) : s->h[0]};
-                C.level[k] = ofx_lk_desc{pp, pn, pg, nullptr, 0, nullptr, 0, s->p.min_det};
-                C.cols[k] = k ? chain_extent(k, s->pw[k]) : 0;
-            }
-            C.d_status = s->corner_status;
-            C.d_pair_status = s->pair_status + (pc % slots);
-            if (s->p.sharded) shard_reach(s, C.shard_rows);
-            continue;
-        }
-        // (three stages: both pyramids are complete since the previous tick)
-        for (int k = 0; k < L; ++k) {
-            // (both frames of a pair come through the same API with the same pitch; a borrowed level 0 uses the caller's)
-            if (s->p.local_corner) {
-                // (a borrowed level 0 is the whole frame: the chain may read all of it, and the repair rebuilds from it)
-                const bool whole0 = k == 0 && s->p.borrow_frames && !s->p.frames_partial; // (partial frames: the patch's extent only)
-                const int rows_k = whole0 ? s->h[0] : chain_extent(k, s->ph[k]);
-                ofx_geom pg{s->w[k], s->h[k], pitch_of(pc, k, true), 0, rows_k, 0, rows_k};
-                C.level[k] = ofx_lk_desc{patch_of(pc - 1, k), patch_of(pc, k), pg, nullptr, 0, nullptr, 0, s->p.min_det};
-                C.cols[k] = whole0 ? 0 : chain_extent(k, s->pw[k]);
-            } else {
-                ofx_geom cg = level_geom(s, k, 0, s->h[k]);
-                cg.pitch = pitch_of(pc, k, false);
-                C.level[k] = ofx_lk_desc{plane_of(pc - 1, k), plane_of(pc, k), cg, nullptr, 0, nullptr, 0, s->p.min_det};
-            }
-        }
-        C.d_pair_status = s->pair_status + (pc % slots);
-        if (s->p.local_corner) {
-            C.d_status = s->corner_status;
-            if (s->p.sharded) shard_reach(s, C.shard_rows);
-            if (s->repair) {
-                C.patch_w = s->pw[0];
-                C.patch_h = s->ph[0];
-                for (int k = 0; k < L; ++k) {
-                    C.patch_pitch[k] = s->ppitch[k];
-                    C.d_patch_reloc[k] = s->preloc[slot_i][k];
-                }
-            }
-        }
-    }
-    long newest = -1, oldest = -1; // the pairs this call completes: oldest .. newest
-    static thread_local ofx_shift_desc sd0[OFX_MAX_LK_ITEMS];
-    int ns0 = 0;
-    for (long pl = f0 - D * B; pl <= f0 - D * B + B - 1; ++pl) { // LK(pair pl), reading next through the shift vectors the previous tick wrote
-        if (pl < 1 || pl > last_frame) continue;
-        const int b = (int)(pl % B);
-        // (iterations two per launch: each such launch moves the flow to the slot's other set, and the last one must leave it in
-        // flowset -- with an odd number of them the tick starts in flowset2)
-        float *const *fl = s->iter_pairs && (((s->p.iters - 1) / 2) & 1) ? s->flowset2[b] : s->flowset[b];
-        if (s->fused_iters)
-            OFX_REQUIRE(!s->p.borrow_frames || (pitch_of(pl, 0, false) == s->pitch[0] && pitch_of(pl - 1, 0, false) == s->pitch[0]),
-                        "ofx_session_stream_submit: with refinement iterations borrowed frames need a row pitch of %d bytes (the "
-                        "width rounded up to 64), got %d", s->pitch[0], pitch_of(pl, 0, false));
-        for (int k = L - 1; k >= 0; --k) {
-            ofx_geom lg = level_geom(s, k, s->fl0[k], s->fl1[k]); // (the own rows, unless iterations follow on a shard)
-            lg.pitch = pitch_of(pl, k, false);
-            ofx_lk_desc &d = g.lk[g.n_lk++];
-            d = ofx_lk_desc{plane_of(pl - 1, k), plane_of(pl, k), lg, fl[k], s->fl0[k], k == L - 1 ? nullptr : uvslot(pl) + 2 * k, 0, s->p.min_det};
-            if (s->fused_iters) {
-                // refinement iterations follow (lk_body_warp.h): the LK stage is iteration 1 of the pair and also writes the warped
-                // image of iteration 2, so the globally shifted next image (the warp's source) is made BEFORE the tick -- its
-                // vectors are a tick old -- and the LK stage reads it as it is instead of shifting on the fly
-                const uint8_t *src = d.d_next;
-                if (k != L - 1) {
-                    sd0[ns0++] = ofx_shift_desc{d.d_next, s->itsh[b][0][k], level_geom(s, k, s->buf0[k], s->buf1[k]), uvslot(pl) + 2 * k};
-                    src = s->itsh[b][0][k];
-                }
-                d.d_next = src, d.d_uv = nullptr;
-                d.d_warp_src = src, d.d_warp_out = s->itsh[b][1][k], d.warp_scale = OFX_ITER_SCALE;
-                if (s->p.sharded) d.d_warp_status = s->corner_status, d.warp_status_bit = 16 + k; // (a tap row beyond the halo rows)
-            }
-        }
-        if (oldest < 0) oldest = pl;
-        newest = pl;
-    }
-    if (ns0) OFX_TRY(timed_launch(s, OFX_TIME_SHIFT, stream, [&] { return ofx_shift_levels(sd0, ns0, stream); }));
-    *completed_pair = -1;
-    if (newest > s->reported) {
-        *completed_pair = (int)newest;
-        s->reported = newest;
-        for (int k = 0; k < L; ++k) s->flow[k] = s->flowset[newest % B][k];
-    }
-    bool time_it = g.n_lk > 0;
-    g.deep_fetch = s->p.deep_fetch; // (ofx_params.deep_fetch: where the caller's frames come from)
-#ifdef OFX_EXPERIMENTS
-    // stage ablation for timing experiments (tools/stream_timeline.py): the flows reported complete are then NOT computed, so
-    // the knob only exists in builds made with -DOFX_EXPERIMENTS (OFX_BUILD_DEFS)
-    static const int skip = [] { const char *e = getenv("OFX_STREAM_SKIP"); return e ? atoi(e) : 0; }();
-    if (skip & 1) g.n_pyr = 0;
-    if (skip & 2) g.n_corner = 0;
-    if (skip & 8) g.n_lk = 0;
-    time_it = time_it || (skip & 8);
-#endif
-    if (time_it)
-        OFX_TRY(timed_launch(s, OFX_TIME_STREAM, stream, [&] { return ofx_stream_launch(&g, s->p.window, s->p.mode, stream); }));
-    else
-        OFX_TRY(ofx_stream_launch(&g, s->p.window, s->p.mode, stream));
-    // Extension (lk_iter): the tick's LK stage was iteration 1 of its pairs.  Every further iteration is
-    // one warp launch and one accumulating LK launch over ALL levels of ALL those pairs (B x levels items: the strips are B
-    // times as tall as in the pair-at-a-time path), after one launch that materialises the globally shifted next images the
-    // warp reads.  Same arithmetic, same bits as ofx_session_run_flow with iters > 1.
-    if (s->p.iters > 1 && newest >= 1) {
-        static thread_local ofx_shift_desc sd[OFX_MAX_LK_ITEMS];
-        static thread_local ofx_warp_desc wd[OFX_MAX_LK_ITEMS];
-        static thread_local ofx_lk_desc ld[OFX_MAX_LK_ITEMS];
-        static thread_local const float *fin[OFX_MAX_LK_ITEMS];
-        // iterations two per launch (lk_body_pair.h), paired from the front; a left-over one runs alone, in place.  alt: the pairs'
-        // flow is in flowset2 (the tick's LK stage chose where it started, above)
-        bool alt = s->iter_pairs && (((s->p.iters - 1) / 2) & 1);
-        int wcur = 1; // the warped plane the next launch reads (itsh[b][1] / [2] alternate; the tick wrote [1])
-        const int reach = s->p.window / 2 + 1;
-        auto clip = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
-        for (int it = 1; it < s->p.iters;) { // it = iterations done so far; this pass computes iteration it + 1 (two: and it + 2)
-            const bool two = s->iter_pairs && it + 2 <= s->p.iters;
-            // fused (lk_body_warp.h): every launch but the last also writes the warped images of the pass after it, into the other of
-            // the flow set's two warped planes (the tick's LK stage wrote those of this loop's first pass): no warp launch
-            const bool fused = s->fused_iters, need_warp = !fused, wout = fused && it + (two ? 2 : 1) < s->p.iters;
-            const int wi = fused ? wcur : 1, wo = 3 - wi;
-            int ns = 0, nw = 0;
-            for (long pl = f0 - D * B; pl <= f0 - D * B + B - 1; ++pl) {
-                if (pl < 1 || pl > last_frame) continue;
-                const int b = (int)(pl % B);
-                // (a borrowed level 0 is read in place here too; the launches below address a level's planes -- the caller's
-                // frame, the shifted and the warped image -- with ONE pitch, so borrowed frames must have the session's)
-                OFX_REQUIRE(!s->p.borrow_frames || (pitch_of(pl, 0, false) == s->pitch[0] && pitch_of(pl - 1, 0, false) == s->pitch[0]),
-                            "ofx_session_stream_submit: with refinement iterations borrowed frames need a row pitch of %d bytes (the "
-                            "width rounded up to 64), got %d", s->pitch[0], pitch_of(pl, 0, false));
-                for (int k = L - 1; k >= 0; --k) {
-                    // rows of this iteration on a shard: the own rows + (radius + 1) * (iters - 1 - it) either side, so that the
-                    // next warp finds the flow of every row its LK touches (whole levels: everything)
-                    const int ext = s->p.sharded ? reach * (s->p.iters - 1 - it) : 0;
-                    const int a = clip(s->own0[k] - ext, 0, s->h[k]), e = clip(s->own1[k] + ext, 0, s->h[k]);
-                    const int wa = clip(a - reach, s->buf0[k], s->buf1[k]), we = clip(e + reach, s->buf0[k], s->buf1[k]);
-                    const uint8_t *next_k = plane_of(pl, k);
-                    const uint8_t *src = next_k;
-                    if (k != L - 1) {
-                        // the globally shifted next image, every row the buffers hold (once per pair, before iteration 2)
-                        if (it == 1 && !fused) sd[ns++] = ofx_shift_desc{next_k, s->itsh[b][0][k], level_geom(s, k, s->buf0[k], s->buf1[k]), uvslot(pl) + 2 * k};
-                        src = s->itsh[b][0][k];
-                    }
-                    float *const fcur = alt ? s->flowset2[b][k] : s->flowset[b][k];
-                    wd[nw] = ofx_warp_desc{src, s->itsh[b][wi][k], level_geom(s, k, wa, we), fcur, s->fl0[k], OFX_ITER_SCALE,
-                                           s->p.sharded ? s->corner_status : nullptr, 16 + k};
-                    ld[nw] = ofx_lk_desc{plane_of(pl - 1, k), s->itsh[b][wi][k], level_geom(s, k, a, e), fcur, s->fl0[k], nullptr, 1, s->p.min_det};
-                    if (two) { // reads fcur, writes the slot's other set; its first iteration's warp needs the source either way
-                        fin[nw] = fcur;
-                        ld[nw].d_flow = alt ? s->flowset[b][k] : s->flowset2[b][k];
-                        ld[nw].d_warp_src = src, ld[nw].warp_scale = OFX_ITER_SCALE;
-                    }
-                    if (wout) {
-                        ld[nw].d_warp_src = src, ld[nw].d_warp_out = s->itsh[b][wo][k], ld[nw].warp_scale = OFX_ITER_SCALE;
-                        if (s->p.sharded) ld[nw].d_warp_status = s->corner_status, ld[nw].warp_status_bit = 16 + k;
-                    }
-                    ++nw;
-                }
-            }
-            if (ns) OFX_TRY(timed_launch(s, OFX_TIME_SHIFT, stream, [&] { return ofx_shift_levels(sd, ns, stream); }));
-            if (need_warp) OFX_TRY(timed_launch(s, OFX_TIME_WARP, stream, [&] { return ofx_warp_levels(wd, nw, stream); }));
-            OFX_TRY(timed_launch(s, wout ? OFX_TIME_LK_ACC_WARP : OFX_TIME_LK_ACC, stream, [&] {
-                return two ? ofx_lk_levels_pair(ld, fin, nw, s->p.window, s->p.mode, &s->pair_opts, stream) : ofx_lk_levels(ld, nw, s->p.window, s->p.mode, stream);
-            }));
-            if (two) alt = !alt;
-            wcur = wo;
-            it += two ? 2 : 1;
-        }
-    }
-    // the output stage (ofx_session_stream_compose): behind the tick's last launch on the same stream, before the next tick
-    // rewrites flow set p mod B
-    if (s->ring && newest >= 1) OFX_TRY(compose_ring(s, oldest, newest, stream));
-    // the sampled output stage (ofx_session_stream_arrows / _stream_tracks): one launch, under the same rule
-    if ((s->arrow_ring || s->trk_points) && newest >= 1) OFX_TRY(sample_ring(s, oldest, newest, stream));
-    s->stream_n = f0 + B;
-    return OFX_OK;
-}
-
-extern "C" int ofx_session_stream_begin(ofx_session *s)
-{
-    OFX_REQUIRE(s, "ofx_session_stream_begin: null session");
-    OFX_REQUIRE(!s->p.sharded || s->p.local_corner,
-                "ofx_session_stream_begin: on a sharded session the stream pipeline needs local_corner (the corner flows "
-                "computed from each frame's top-left patch); otherwise drive the staged API");
-    OFX_REQUIRE(s->p.levels >= 2 && s->p.levels - 1 <= 6, "ofx_session_stream_begin: %d levels unsupported (2..7)", s->p.levels);
-    // staging work of the pair-at-a-time pipelined path may still be in flight on the session's own stream; the stream
-    // pipeline is about to reuse the same image sets from the caller's stream
-    if (s->aux) OFX_HIP(hipStreamSynchronize(s->aux));
-    for (bool &b : s->set_busy) b = false;
-    s->stream_n = 0;
-    s->stream_frames = -1;
-    s->n_held = 0;
-    s->reported = 0;
-    s->corner_newest = 0;
-    s->composed = 0;
-    s->sampled = 0;
-    s->stream_input = 0;
-    s->have_prev = s->have_next = s->staged = false;
-    s->corner_done = false;
-    s->pset_img[0] = s->pset_img[1] = -1;
-    for (int k = 0; k < s->p.levels; ++k) s->flow[k] = s->flowset[0][k];
-    return OFX_OK;
-}
-
-// A tick of colour frames: ONE front-end launch writes the filtered planes of the tick's frames (the sets they are assigned to,
-// frame f -> set f mod stream_sets), then the tick runs on those planes as its frames.
-static int frontend_tick(ofx_session *s, const uint8_t *const *img3, const int *pitch3, int n, void *stream, int *completed_pair)
-{
-    const uint8_t *fr[kMaxBatch];
-    int pt[kMaxBatch];
-    if (n > 0) {
-        uint8_t *dst[kMaxBatch];
-        int dp[kMaxBatch], md[kMaxBatch];
-        const int sets = stream_sets(s);
-        for (int i = 0; i < n; ++i) {
-            const long f = s->stream_n + i;
-            dst[i] = s->p.borrow_frames ? s->fplane[f % sets] : s->img[f % sets][0];
-            dp[i] = s->pitch[0];
-            md[i] = f == 0 && (s->fe_flags & OFX_FRONTEND_FLAG_FIRST_GREY) ? OFX_FRONTEND_GREY : s->fe_mode;
-            fr[i] = dst[i];
-            pt[i] = s->pitch[0];
-        }
-        OfxRange range("ofx.frontend");
-        OFX_TRY(ofx_frontend_run(s->fe, img3, pitch3, dst, dp, md, n, s->w[0], s->h[0], ofx_stream(stream)));
-    }
-    return stream_tick(s, fr, pt, n, stream, completed_pair);
-}
-
-// Submit the next frame of the stream (input 1: a grey frame, 2: a colour frame for the front end).  *completed_pair (may be
-// NULL) receives the highest pair (frame p-1 -> frame p, frames counted from 0) whose flow is complete after this call in `stream`
-// order, or -1 when the call completed none.
-static int stream_submit(ofx_session *s, const uint8_t *frame, int pitch, void *stream, int *completed_pair, int input, const char *who)
-{
-    OFX_REQUIRE(s && frame, "%s: null argument", who);
-    if (s->stream_n < 0) {
-        ofx_set_error("%s: call ofx_session_stream_begin first", who);
-        return OFX_E_STATE;
-    }
-    OFX_REQUIRE(s->stream_frames < 0, "%s: the stream is being drained", who);
-    if (input == 2 && !s->fe_mode) {
-        ofx_set_error("%s: colour frames need the front end (ofx_session_stream_frontend)", who);
-        return OFX_E_STATE;
-    }
-    if (s->stream_input != 0 && s->stream_input != input) {
-        ofx_set_error("%s: this stream has received %s frames; a stream takes grey frames or colour frames, not both", who,
-                      s->stream_input == 1 ? "grey" : "colour");
-        return OFX_E_STATE;
-    }
-    if (input == 2)
-        OFX_REQUIRE(pitch >= 3 * s->w[0] && ((uintptr_t)frame & 3) == 0,
-                    "%s: a colour frame must be 4-byte aligned with a pitch of at least 3 * %d bytes (got %d)", who, s->w[0], pitch);
-    s->stream_input = input;
-    int dummy = -1;
-    if (!completed_pair) completed_pair = &dummy;
-    const int B = stream_batch_of(s);
-    if (s->n_held + 1 < B) { // the tick is not full yet: remember the frame
-        s->held_frame[s->n_held] = frame;
-        s->held_pitch[s->n_held] = pitch;
-        ++s->n_held;
-        *completed_pair = -1;
-        return OFX_OK;
-    }
-    const uint8_t *fr[kMaxBatch];
-    int pt[kMaxBatch];
-    for (int i = 0; i < s->n_held; ++i) fr[i] = s->held_frame[i], pt[i] = s->held_pitch[i];
-    fr[s->n_held] = frame;
-    pt[s->n_held] = pitch;
-    const int n = s->n_held + 1;
-    s->n_held = 0;
-    return input == 2 ? frontend_tick(s, fr, pt, n, stream, completed_pair) : stream_tick(s, fr, pt, n, stream, completed_pair);
-}
-
-extern "C" int ofx_session_stream_submit(ofx_session *s, const uint8_t *d_gray1, int pitch, void *stream, int *completed_pair)
-{
-    return stream_submit(s, d_gray1, pitch, stream, completed_pair, 1, "ofx_session_stream_submit");
-}
-
-extern "C" int ofx_session_stream_submit_3ch(ofx_session *s, const uint8_t *d_img3, int pitch, void *stream, int *completed_pair)
-{
-    return stream_submit(s, d_img3, pitch, stream, completed_pair, 2, "ofx_session_stream_submit_3ch");
-}
-
-extern "C" int ofx_session_stream_submit_frames_3ch(ofx_session *s, const uint8_t *const *d_img3, const int *pitches, int pitch0, int n,
-                                                    void *stream, int *completed_pair)
-{
-    OFX_REQUIRE(s && d_img3 && n >= 1, "ofx_session_stream_submit_frames_3ch: bad arguments");
-    int newest = -1;
-    for (int i = 0; i < n; ++i) {
-        int done = -1;
-        OFX_TRY(ofx_session_stream_submit_3ch(s, d_img3[i], pitches ? pitches[i] : pitch0, stream, &done));
-        newest = done > newest ? done : newest;
-    }
-    if (completed_pair) *completed_pair = newest;
-    return OFX_OK;
-}
-
-extern "C" int ofx_session_stream_frontend(ofx_session *s, int mode, int window, double sigma_s, double sigma_b, int flags)
-{
-    OFX_REQUIRE(s, "ofx_session_stream_frontend: null session");
-    if (s->p.sharded) {
-        ofx_set_error("ofx_session_stream_frontend: not on a sharded session (each rank would filter the whole frame)");
-        return OFX_E_UNSUPPORTED;
-    }
-    if (s->stream_n > 0 || s->n_held > 0) {
-        ofx_set_error("ofx_session_stream_frontend: the stream has frames already; set the front end before the first frame of a stream");
-        return OFX_E_STATE;
-    }
-    OFX_REQUIRE(mode == OFX_FRONTEND_OFF || mode == OFX_FRONTEND_GREY || mode == OFX_FRONTEND_BILATERAL,
-                "ofx_session_stream_frontend: mode %d (OFX_FRONTEND_OFF / _GREY / _BILATERAL)", mode);
-    OFX_REQUIRE((flags & ~(OFX_FRONTEND_FLAG_FAST | OFX_FRONTEND_FLAG_FIRST_GREY)) == 0, "ofx_session_stream_frontend: unknown flags %#x", flags);
-    OFX_HIP(hipSetDevice(s->p.device));
-    if (mode == OFX_FRONTEND_OFF) {
-        ofx_frontend_tables_free(s->fe);
-        s->fe = nullptr;
-        s->fe_mode = s->fe_flags = 0;
-        for (uint8_t *&pl : s->fplane) pl = nullptr;
-        void *a = s->fe_arena;
-        s->fe_arena = nullptr;
-        if (a) OFX_HIP(hipFree(a));
-        return OFX_OK;
-    }
-    ofx_frontend_tables *t = nullptr;
-    OFX_TRY(ofx_frontend_tables_make(mode == OFX_FRONTEND_BILATERAL ? window : 0, sigma_s, sigma_b, &t));
-    if (s->p.borrow_frames && !s->fe_arena) {
-        // one plane per image set at the level-0 pitch, plus the three readable bytes the fused warp may fetch past level 0
-        const size_t plane = align_up((size_t)s->pitch[0] * (size_t)s->h[0] + 64, 256);
-        const hipError_t e = hipMalloc(&s->fe_arena, plane * (size_t)s->n_sets);
-        if (e != hipSuccess) {
-            ofx_frontend_tables_free(t);
-            s->fe_arena = nullptr;
-            ofx_set_error("ofx_session_stream_frontend: hipMalloc(%zu bytes): %s", plane * (size_t)s->n_sets, hipGetErrorString(e));
-            return OFX_E_HIP;
-        }
-        for (int i = 0; i < s->n_sets; ++i) s->fplane[i] = static_cast<uint8_t *>(s->fe_arena) + plane * (size_t)i;
-    }
-    ofx_frontend_tables_free(s->fe);
-    s->fe = t;
-    s->fe_mode = mode == OFX_FRONTEND_GREY ? OFX_FRONTEND_GREY : (flags & OFX_FRONTEND_FLAG_FAST) ? OFX_FRONTEND_BILATERAL_FAST : OFX_FRONTEND_BILATERAL;
-    s->fe_flags = flags;
-    return OFX_OK;
-}
-
-extern "C" int ofx_session_stream_submit_frames(ofx_session *s, const uint8_t *const *d_gray1, const int *pitches, int pitch0, int n,
-                                                void *stream, int *completed_pair)
-{
-    OFX_REQUIRE(s && d_gray1 && n >= 1, "ofx_session_stream_submit_frames: bad arguments");
-    int newest = -1;
-    for (int i = 0; i < n; ++i) {
-        int done = -1;
-        OFX_TRY(ofx_session_stream_submit(s, d_gray1[i], pitches ? pitches[i] : pitch0, stream, &done));
-        newest = done > newest ? done : newest;
-    }
-    if (completed_pair) *completed_pair = newest;
-    return OFX_OK;
-}
-
-// Run one more tick without a new frame (frames still waiting for their tick to fill go out with it); call until it
-// reports -2 in *completed_pair (pipeline empty).  Two ticks drain a full pipeline.
-extern "C" int ofx_session_stream_drain(ofx_session *s, void *stream, int *completed_pair)
-{
-    OFX_REQUIRE(s && completed_pair, "ofx_session_stream_drain: null argument");
-    if (s->stream_n < 0) {
-        ofx_set_error("ofx_session_stream_drain: not streaming");
-        return OFX_E_STATE;
-    }
-    const uint8_t *fr[kMaxBatch];
-    int pt[kMaxBatch];
-    const int n = s->n_held;
-    for (int i = 0; i < n; ++i) fr[i] = s->held_frame[i], pt[i] = s->held_pitch[i];
-    s->n_held = 0;
-    if (s->stream_frames < 0) s->stream_frames = s->stream_n + n; // number of frames the stream received
-    if (n == 0 && s->reported >= s->stream_frames - 1) { // every pair (the last one is stream_frames - 1) has been reported
-        *completed_pair = -2;
-        s->stream_n = -1;
-        s->stream_frames = -1;
-        return OFX_OK;
-    }
-    return s->stream_input == 2 ? frontend_tick(s, fr, pt, n, stream, completed_pair) : stream_tick(s, fr, pt, n, stream, completed_pair);
-}
-
-extern "C" int ofx_session_flow_of(ofx_session *s, int pair, int level, float **d_ptr, int *row0, int *rows)
-{
-    OFX_REQUIRE(s && level >= 0 && level < s->p.levels, "ofx_session_flow_of: bad arguments");
-    const int B = stream_batch_of(s);
-    OFX_REQUIRE(pair >= 1 && pair <= s->reported && pair > s->reported - B,
-                "ofx_session_flow_of: pair %d is not among the newest %d completed pairs (newest: %ld)", pair, B, s->reported);
-    if (d_ptr) *d_ptr = s->flowset[pair % B][level] + s->flow_own_offset(level);
-    if (row0) *row0 = s->own0[level];
-    if (rows) *rows = s->own1[level] - s->own0[level];
-    return OFX_OK;
-}
-
-extern "C" int ofx_session_stream_compose(ofx_session *s, int level, float *d_ring, size_t slot_stride_bytes, int n_slots)
-{
-    OFX_REQUIRE(s, "ofx_session_stream_compose: null session");
-    if (s->stream_n > 0 || s->n_held > 0) {
-        ofx_set_error("ofx_session_stream_compose: the stream has frames already; set the ring before the first frame of a stream");
-        return OFX_E_STATE;
-    }
-    if (!d_ring) {
-        s->ring = nullptr;
-        s->composed = 0;
-        return OFX_OK;
-    }
-    const int B = stream_batch_of(s);
-    OFX_REQUIRE(level >= 0 && level < s->p.levels, "ofx_session_stream_compose: level %d out of range (0 .. %d)", level, s->p.levels - 1);
-    OFX_REQUIRE(n_slots >= B, "ofx_session_stream_compose: %d slots, the ring needs at least stream_batch = %d (the pairs one call completes)",
-                n_slots, B);
-    const size_t slot_bytes = (size_t)(s->own1[level] - s->own0[level]) * (size_t)s->w[level] * 2 * sizeof(float);
-    OFX_REQUIRE(((uintptr_t)d_ring & 15) == 0, "ofx_session_stream_compose: the ring must be 16-byte aligned");
-    OFX_REQUIRE(slot_stride_bytes % 16 == 0 && slot_stride_bytes >= slot_bytes,
-                "ofx_session_stream_compose: slot stride %zu bytes must be a multiple of 16 and at least the slot's %zu bytes", slot_stride_bytes,
-                slot_bytes);
-    if (slot_bytes / 8 >= ((size_t)1 << 31)) {
-        ofx_set_error("ofx_session_stream_compose: a slot of %zu pixels is more than this build composes (2^31)", slot_bytes / 8);
-        return OFX_E_UNSUPPORTED;
-    }
-    // a rank composes its own rows: own row y at `level` reads row y >> (k - level) of level k, which must be one of the rows the
-    // rank computes there (ShardPlan's rows are the coarsest level's, doubled per level)
-    for (int k = level + 1; k < s->p.levels && s->own1[level] > s->own0[level]; ++k) {
-        const int sc = k - level;
-        if ((s->own0[level] >> sc) < s->own0[k] || ((s->own1[level] - 1) >> sc) >= s->own1[k]) {
-            ofx_set_error("ofx_session_stream_compose: own rows [%d,%d) of level %d read rows [%d,%d] of level %d, which owns [%d,%d)", s->own0[level],
-                          s->own1[level], level, s->own0[level] >> sc, (s->own1[level] - 1) >> sc, k, s->own0[k], s->own1[k]);
-            return OFX_E_UNSUPPORTED;
-        }
-    }
-    s->ring = d_ring;
-    s->ring_stride = slot_stride_bytes;
-    s->ring_slots = n_slots;
-    s->ring_level = level;
-    s->composed = 0;
-    return OFX_OK;
-}
-
-extern "C" int ofx_session_composed_of(ofx_session *s, int pair, float **d_ptr, int *row0, int *rows)
-{
-    OFX_REQUIRE(s, "ofx_session_composed_of: null session");
-    if (!s->ring) {
-        ofx_set_error("ofx_session_composed_of: no ring set (ofx_session_stream_compose)");
-        return OFX_E_STATE;
-    }
-    OFX_REQUIRE(pair >= 1 && pair <= s->composed && pair > s->composed - s->ring_slots,
-                "ofx_session_composed_of: pair %d is not among the newest %d composed pairs (newest: %ld)", pair, s->ring_slots, s->composed);
-    const int lv = s->ring_level;
-    if (d_ptr) *d_ptr = reinterpret_cast<float *>(reinterpret_cast<char *>(s->ring) + (size_t)((pair - 1) % s->ring_slots) * s->ring_stride);
-    if (row0) *row0 = s->own0[lv];
-    if (rows) *rows = s->own1[lv] - s->own0[lv];
-    return OFX_OK;
-}
-
-// what ofx_session_stream_arrows / _stream_tracks share: the session may take a new output setting, and the ring fits
-static int sampled_settable(ofx_session *s, const char *who)
-{
-    if (s->stream_n > 0 || s->n_held > 0) {
-        ofx_set_error("%s: the stream has frames already; set the output before the first frame of a stream", who);
-        return OFX_E_STATE;
-    }
-    if (s->p.sharded) {
-        ofx_set_error("%s: not on a sharded session (sampled positions cross shard boundaries)", who);
-        return OFX_E_UNSUPPORTED;
-    }
-    return OFX_OK;
-}
-
-static int sampled_ring_ok(const ofx_session *s, const void *ring, size_t stride, size_t slot_bytes, int n_slots, const char *who)
-{
-    const int B = stream_batch_of(s);
-    OFX_REQUIRE(n_slots >= B, "%s: %d slots, the ring needs at least stream_batch = %d (the pairs one call completes)", who, n_slots, B);
-    OFX_REQUIRE(((uintptr_t)ring & 15) == 0, "%s: the ring must be 16-byte aligned", who);
-    OFX_REQUIRE(stride % 16 == 0 && stride >= slot_bytes, "%s: slot stride %zu bytes must be a multiple of 16 and at least the slot's %zu bytes", who,
-                stride, slot_bytes);
-    return OFX_OK;
-}
-
-extern "C" int ofx_session_stream_arrows(ofx_session *s, int level, int arrow_res, int32_t *d_ring, size_t slot_stride_bytes, int n_slots)
-{
-    const char *who = "ofx_session_stream_arrows";
-    OFX_REQUIRE(s, "%s: null session", who);
-    OFX_TRY(sampled_settable(s, who));
-    if (!d_ring) {
-        s->arrow_ring = nullptr;
-        s->sampled = 0;
-        return OFX_OK;
-    }
-    OFX_REQUIRE(level >= 0 && level < s->p.levels, "%s: level %d out of range (0 .. %d)", who, level, s->p.levels - 1);
-    int offset, ny, nx;
-    OFX_TRY(ofx_arrow_grid(s->w[level], s->h[level], arrow_res, &offset, &ny, &nx, who));
-    OFX_TRY(ofx_check_sample_pyramid(s->w[level], s->h[level], s->p.levels, level, who));
-    OFX_TRY(sampled_ring_ok(s, d_ring, slot_stride_bytes, (size_t)ny * (size_t)nx * 16, n_slots, who));
-    s->arrow_ring = d_ring;
-    s->arrow_stride = slot_stride_bytes;
-    s->arrow_slots = n_slots;
-    s->arrow_level = level;
-    s->arrow_offset = offset, s->arrow_ny = ny, s->arrow_nx = nx;
-    s->sampled = 0;
-    return OFX_OK;
-}
-
-extern "C" int ofx_session_arrows_of(ofx_session *s, int pair, int32_t **d_ptr, int *ny, int *nx)
-{
-    OFX_REQUIRE(s, "ofx_session_arrows_of: null session");
-    if (!s->arrow_ring) {
-        ofx_set_error("ofx_session_arrows_of: no ring set (ofx_session_stream_arrows)");
-        return OFX_E_STATE;
-    }
-    OFX_REQUIRE(pair >= 1 && pair <= s->sampled && pair > s->sampled - s->arrow_slots,
-                "ofx_session_arrows_of: pair %d is not among the newest %d sampled pairs (newest: %ld)", pair, s->arrow_slots, s->sampled);
-    if (d_ptr) *d_ptr = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(s->arrow_ring) + (size_t)((pair - 1) % s->arrow_slots) * s->arrow_stride);
-    if (ny) *ny = s->arrow_ny;
-    if (nx) *nx = s->arrow_nx;
-    return OFX_OK;
-}
-
-extern "C" int ofx_session_stream_tracks(ofx_session *s, int level, float *d_points, int32_t *d_status, int n_points, float *d_history,
-                                         size_t slot_stride_bytes, int n_slots)
-{
-    const char *who = "ofx_session_stream_tracks";
-    OFX_REQUIRE(s, "%s: null session", who);
-    OFX_TRY(sampled_settable(s, who));
-    if (!d_points) {
-        s->trk_points = s->trk_hist = nullptr;
-        s->trk_status = nullptr;
-        return OFX_OK;
-    }
-    OFX_REQUIRE(level >= 0 && level < s->p.levels, "%s: level %d out of range (0 .. %d)", who, level, s->p.levels - 1);
-    OFX_REQUIRE(d_status && n_points >= 1, "%s: %d points need a status word each", who, n_points);
-    OFX_REQUIRE(((uintptr_t)d_points & 7) == 0 && ((uintptr_t)d_status & 3) == 0, "%s: points must be 8-byte, statuses 4-byte aligned", who);
-    OFX_TRY(ofx_check_sample_pyramid(s->w[level], s->h[level], s->p.levels, level, who));
-    if (d_history) OFX_TRY(sampled_ring_ok(s, d_history, slot_stride_bytes, (size_t)n_points * 8, n_slots, who));
-    s->trk_points = d_points;
-    s->trk_status = d_status;
-    s->trk_n = n_points;
-    s->trk_level = level;
-    s->trk_hist = d_history;
-    s->trk_stride = d_history ? slot_stride_bytes : 0;
-    s->trk_slots = d_history ? n_slots : 0;
-    return OFX_OK;
-}
-
 // gpu::calc_opt_flow (OptFlowGpu.cuh:33, OptFlowGpu.cu:1909-1979) with host pointers: upload both images and the
 // two floats of every coarser flow level that the shift reads, run one level on the device, download its flow.
 extern "C" int ofx_calc_opt_flow_host(const uint8_t *h_prev3, const uint8_t *h_next3, int w, int h, float **h_flow_pyr, int level,

@@ -34,7 +34,7 @@ def planner(tmp_path_factory):
 
 
 def pyramid(w, h, levels, pairs):
-    """the items of a tick: per pair, the coarsest level first (session.cpp)"""
+    """the items of a tick: per pair, the coarsest level first (session_stream.cpp)"""
     return [(w >> k, h >> k) for _ in range(pairs) for k in range(levels - 1, -1, -1)]
 
 
