@@ -135,6 +135,23 @@ int ofx_arrow_grid(int w, int h, int arrow_res, int *offset, int *ny, int *nx, c
 // (y >> s, x >> s) of level k exists for every pixel of level `level`
 int ofx_check_sample_pyramid(int w, int h, int levels, int level, const char *who);
 
+// the stream pipeline's motion-compensation stage (motion_ring.hip; the definition: "motion compensation" in include/ofx.h) for
+// n <= OFX_STREAM_MAX_BATCH pairs of one w x h level in ONE launch.  Pair i reads prev[i] / next[i] (u8 planes, each with its own
+// pitch >= w), flow[i] (w x h interleaved float32, 8-byte aligned) and uv[i] (two floats on the device; NULL = no shift), and
+// writes the image at dst[i] (rows dst_pitch apart, bytes beyond column w - 1 untouched; NULL = none) and ADDS its four sums to
+// stats[i] (8-byte aligned; NULL = none), which the launch function zeroes on the stream first, consecutive slots by one memset.  dst_dwords: every dst and
+// dst_pitch is 4-byte aligned, whole quads are stored as one dword.  Every argument is checked before anything is enqueued.
+struct ofx_motion_batch {
+    const uint8_t *prev[OFX_STREAM_MAX_BATCH], *next[OFX_STREAM_MAX_BATCH];
+    const float *flow[OFX_STREAM_MAX_BATCH], *uv[OFX_STREAM_MAX_BATCH];
+    uint8_t *dst[OFX_STREAM_MAX_BATCH];
+    unsigned long long *stats[OFX_STREAM_MAX_BATCH];
+    int prev_pitch[OFX_STREAM_MAX_BATCH], next_pitch[OFX_STREAM_MAX_BATCH];
+    int n, w, h, dst_pitch, dst_dwords;
+    float scale;
+};
+int ofx_motion_batch_launch(const ofx_motion_batch *a, void *stream);
+
 // the stream pipeline's colour front end (frontend.hip): the filter's tables for one (window, sigma_s, sigma_b), built once on the
 // host (window 0: grey frames only; an unsupported window is OFX_E_UNSUPPORTED), and one launch over n <= OFX_STREAM_MAX_BATCH
 // frames (modes[i]: OFX_FRONTEND_GREY / _BILATERAL / _BILATERAL_FAST; a call that mixes the two bilateral forms launches twice)

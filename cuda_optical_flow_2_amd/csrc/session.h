@@ -121,6 +121,14 @@ struct ofx_session {
     size_t trk_stride = 0;
     int trk_n = 0, trk_slots = 0, trk_level = 0;
     long sampled = 0;
+    // ofx_session_stream_motion (motion_ring.hip): the caller's image ring and stats ring (either may be nullptr; both: off), and
+    // the newest pair written
+    uint8_t *mc_ring = nullptr;
+    int64_t *mc_stats = nullptr;
+    size_t mc_stride = 0;
+    int mc_pitch = 0, mc_slots = 0, mc_level = 0;
+    float mc_scale = 0.0f;
+    long motioned = 0;
     // ofx_session_stream_frontend: colour frames through the front end (frontend.hip).  fe_mode: what a frame gets
     // (OFX_FRONTEND_GREY / _BILATERAL / _BILATERAL_FAST), 0 = off; frame 0 of a stream gets OFX_FRONTEND_GREY with
     // OFX_FRONTEND_FLAG_FIRST_GREY.  borrow_frames: the filtered plane of image set i (fplane[i], at pitch[0]) stands in for the

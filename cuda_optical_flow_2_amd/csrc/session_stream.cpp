@@ -99,6 +99,35 @@ struct Tick {
     }
 };
 
+// One launch for pairs first .. last (the pairs a call of the pipeline completes): each pair's motion-compensated next image into
+// its ring slot and its four sums into its stats slot (ofx_session_stream_motion).  Reads what the call's own LK stage read -- both
+// frames' planes of the level, each with the pitch its frame came with, and the pair's shift vector -- and the final flow (flowset: the last
+// launch of a tick always writes it, whichever set the tick started in).
+static int motion_ring(const Tick &t, long first, long last, void *stream)
+{
+    ofx_session *s = t.s;
+    const int lv = s->mc_level;
+    static thread_local ofx_motion_batch mb; // (1 KB)
+    memset(&mb, 0, sizeof mb);
+    mb.w = s->w[lv], mb.h = s->h[lv], mb.scale = s->mc_scale;
+    mb.dst_pitch = s->mc_pitch, mb.dst_dwords = 1; // (ofx_session_stream_motion checked the alignment)
+    for (long p = first; p <= last; ++p, ++mb.n) {
+        const long slot = (p - 1) % s->mc_slots;
+        mb.prev[mb.n] = t.plane_of(p - 1, lv), mb.prev_pitch[mb.n] = t.pitch_of(p - 1, lv, false);
+        mb.next[mb.n] = t.plane_of(p, lv), mb.next_pitch[mb.n] = t.pitch_of(p, lv, false);
+        mb.flow[mb.n] = s->flowset[p % t.B][lv];
+        mb.uv[mb.n] = lv == t.L - 1 ? nullptr : t.uvslot(p) + 2 * lv; // (the coarsest level is not shifted)
+        if (s->mc_ring) mb.dst[mb.n] = s->mc_ring + (size_t)slot * s->mc_stride;
+        if (s->mc_stats) mb.stats[mb.n] = reinterpret_cast<unsigned long long *>(s->mc_stats + 4 * slot);
+    }
+    {
+        OfxRange range("ofx.motion_ring");
+        OFX_TRY(ofx_motion_batch_launch(&mb, stream)); // (zeroes the pairs' stats slots, then the one kernel launch)
+    }
+    s->motioned = last;
+    return OFX_OK;
+}
+
 // pyramid(frame f0 + i) for the tick's frames
 static int pyramid_stages(const Tick &t, const uint8_t *const *frames, const int *pitches, int n_frames, ofx_stream_stages &g)
 {
@@ -363,6 +392,8 @@ static int stream_tick(ofx_session *s, const uint8_t *const *frames, const int *
     if (s->ring && newest >= 1) OFX_TRY(compose_ring(s, oldest, newest, stream));
     // the sampled output stage (ofx_session_stream_arrows / _stream_tracks): one launch, under the same rule
     if ((s->arrow_ring || s->trk_points) && newest >= 1) OFX_TRY(sample_ring(s, oldest, newest, stream));
+    // the motion-compensation stage (ofx_session_stream_motion): one launch, under the same rule
+    if ((s->mc_ring || s->mc_stats) && newest >= 1) OFX_TRY(motion_ring(t, oldest, newest, stream));
     s->stream_n = t.f0 + t.B;
     return OFX_OK;
 }
@@ -385,6 +416,7 @@ extern "C" int ofx_session_stream_begin(ofx_session *s)
     s->corner_newest = 0;
     s->composed = 0;
     s->sampled = 0;
+    s->motioned = 0;
     s->stream_input = 0;
     s->have_prev = s->have_next = s->staged = false;
     s->corner_done = false;
@@ -726,5 +758,63 @@ extern "C" int ofx_session_stream_tracks(ofx_session *s, int level, float *d_poi
     s->trk_hist = d_history;
     s->trk_stride = d_history ? slot_stride_bytes : 0;
     s->trk_slots = d_history ? n_slots : 0;
+    return OFX_OK;
+}
+
+extern "C" int ofx_session_stream_motion(ofx_session *s, int level, float scale, uint8_t *d_ring, int row_pitch, size_t slot_stride_bytes,
+                                         int n_slots, int64_t *d_stats_ring)
+{
+    const char *who = "ofx_session_stream_motion";
+    OFX_REQUIRE(s, "%s: null session", who);
+    if (s->stream_n > 0 || s->n_held > 0) {
+        ofx_set_error("%s: the stream has frames already; set the output before the first frame of a stream", who);
+        return OFX_E_STATE;
+    }
+    if (!d_ring && !d_stats_ring) {
+        s->mc_ring = nullptr;
+        s->mc_stats = nullptr;
+        s->motioned = 0;
+        return OFX_OK;
+    }
+    if (s->p.sharded || s->p.frames_partial) {
+        ofx_set_error("%s: not on a sharded session or with partial frames (a warp crosses shard rows)", who);
+        return OFX_E_UNSUPPORTED;
+    }
+    const int B = stream_batch_of(s);
+    OFX_REQUIRE(level >= 0 && level < s->p.levels, "%s: level %d out of range (0 .. %d)", who, level, s->p.levels - 1);
+    OFX_REQUIRE(n_slots >= B, "%s: %d slots, the rings need at least stream_batch = %d (the pairs one call completes)", who, n_slots, B);
+    if (d_ring) {
+        const size_t slot_bytes = (size_t)s->h[level] * (size_t)row_pitch;
+        OFX_REQUIRE(row_pitch >= s->w[level] && (row_pitch & 3) == 0, "%s: row pitch %d must be a multiple of 4 and at least the level's width %d", who,
+                    row_pitch, s->w[level]);
+        OFX_REQUIRE(((uintptr_t)d_ring & 15) == 0, "%s: the ring must be 16-byte aligned", who);
+        OFX_REQUIRE(slot_stride_bytes % 16 == 0 && slot_stride_bytes >= slot_bytes,
+                    "%s: slot stride %zu bytes must be a multiple of 16 and at least the slot's %zu bytes", who, slot_stride_bytes, slot_bytes);
+    }
+    OFX_REQUIRE(((uintptr_t)d_stats_ring & 7) == 0, "%s: the stats ring must be 8-byte aligned", who);
+    s->mc_ring = d_ring;
+    s->mc_stats = d_stats_ring;
+    s->mc_pitch = d_ring ? row_pitch : 0;
+    s->mc_stride = d_ring ? slot_stride_bytes : 0;
+    s->mc_slots = n_slots;
+    s->mc_level = level;
+    s->mc_scale = scale;
+    s->motioned = 0;
+    return OFX_OK;
+}
+
+extern "C" int ofx_session_motion_of(ofx_session *s, int pair, uint8_t **d_ptr, int *row_pitch, int64_t **d_stats)
+{
+    OFX_REQUIRE(s, "ofx_session_motion_of: null session");
+    if (!s->mc_ring && !s->mc_stats) {
+        ofx_set_error("ofx_session_motion_of: the stage is off (ofx_session_stream_motion)");
+        return OFX_E_STATE;
+    }
+    OFX_REQUIRE(pair >= 1 && pair <= s->motioned && pair > s->motioned - s->mc_slots,
+                "ofx_session_motion_of: pair %d is not among the newest %d pairs of the stage (newest: %ld)", pair, s->mc_slots, s->motioned);
+    const size_t slot = (size_t)((pair - 1) % s->mc_slots);
+    if (d_ptr) *d_ptr = s->mc_ring ? s->mc_ring + slot * s->mc_stride : nullptr;
+    if (row_pitch) *row_pitch = s->mc_pitch;
+    if (d_stats) *d_stats = s->mc_stats ? s->mc_stats + 4 * slot : nullptr;
     return OFX_OK;
 }

@@ -111,7 +111,7 @@ class Session:
         check(self.L.ofx_session_create(C.byref(p), C.byref(self._h)), "ofx_session_create")
         self._keep = []
         self._ring, self._ring_level = None, 0
-        self._arrows = self._tracks = None
+        self._arrows = self._tracks = self._motion = None
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -410,6 +410,48 @@ class Session:
         check(self.L.ofx_session_stream_tracks(self._h, level, points.data_ptr(), status.data_ptr(), n, hp, hs, hn), "stream_tracks")
         self._tracks = (points, status, history)   # (kept alive while the pipeline may write them; replaces the previous ones)
 
+    def stream_motion(self, ring=None, stats=None, level: int = 0, scale: float = None):
+        """The stream pipeline's motion-compensation stage (ofx_session_stream_motion; the definition: "motion compensation" in
+        include/ofx.h): for every pair it completes, the next image of `level` pulled back onto the previous one by the pair's
+        shift and flow -- bit for bit shift_1ch then warp_u8 -- into slot (p - 1) mod n_slots of `ring`, and (w*h, sum |prev - next|,
+        sum |prev - mc|, pixels not warped) into slot (p - 1) mod n_slots of `stats`, by one more launch per completing call.
+        ring: uint8 CUDA tensor [n_slots, rows, width >> level], unit column stride, row stride a multiple of 4, slot stride a
+        multiple of 16 bytes (row padding is left untouched); stats: int64 CUDA tensor [n_slots, 4], contiguous; n_slots >=
+        stream_batch.  Either may be None (image only / stats only); both None turns the stage off.  Only before the first frame
+        of a stream; stays in effect for later streams."""
+        if ring is None and stats is None:
+            check(self.L.ofx_session_stream_motion(self._h, 0, 0.0, None, 0, 0, 0, None), "stream_motion")
+            self._motion = None
+            return
+        import torch
+
+        w, rows = self.width >> level, self.height >> level
+        n_slots = int((ring if ring is not None else stats).shape[0])
+        rp, pitch, stride = None, 0, 0
+        if ring is not None:
+            assert ring.is_cuda and ring.dtype == torch.uint8 and ring.dim() == 3, "ring: uint8 CUDA tensor [n_slots, rows, w]"
+            assert tuple(ring.shape[1:]) == (rows, w) and ring.stride(2) == 1, f"ring slots must be [{rows}, {w}] with unit column stride"
+            rp, pitch, stride = ring.data_ptr(), int(ring.stride(1)), int(ring.stride(0))
+        sp = None
+        if stats is not None:
+            assert stats.is_cuda and stats.dtype == torch.int64 and tuple(stats.shape) == (n_slots, 4) and stats.is_contiguous(), \
+                f"stats: contiguous int64 CUDA tensor [{n_slots}, 4]"
+            sp = stats.data_ptr()
+        check(self.L.ofx_session_stream_motion(self._h, level, ITER_SCALE if scale is None else float(scale), rp, pitch, stride, n_slots, sp),
+              "stream_motion")
+        self._motion = (ring, stats, level)   # (kept alive while the pipeline may write them)
+
+    def motion_of(self, pair: int):
+        """(torch uint8 view [rows, width >> level] or None, torch int64 view [4] or None) of `pair`'s slots in the motion stage's
+        rings (ofx_session_motion_of), while it is one of the newest n_slots pairs; valid once the launch of the call that
+        reported the pair has run."""
+        ptr, pitch, st = _vp(), C.c_int(), _vp()
+        check(self.L.ofx_session_motion_of(self._h, pair, C.byref(ptr), C.byref(pitch), C.byref(st)), "session_motion_of")
+        level = self._motion[2]
+        w, rows = self.width >> level, self.height >> level
+        img = DeviceView(ptr.value, (rows, pitch.value), "|u1").tensor()[:, :w] if ptr.value else None
+        return img, (DeviceView(st.value, (4,), "<i8").tensor() if st.value else None)
+
     def uv(self, level: int):
         """Shift vector of `level` for the pair in progress (the slot alternates per pair: query after every swap)."""
         ptr = _vp()
@@ -541,6 +583,30 @@ def warp_u8(src1: np.ndarray, flow: np.ndarray, scale: float) -> np.ndarray:
     check(L.ofx_warp_levels(C.byref(d), 1, _stream_ptr()), "ofx_warp_levels")
     torch.cuda.synchronize()
     return td[:, :w].cpu().numpy()
+
+
+ITER_SCALE = float(np.float32(8.0 / 15.0))   # OFX_ITER_SCALE: the reference's flow units -> pixels
+
+
+def motion_compensate(prev1: np.ndarray, next1: np.ndarray, flow: np.ndarray, uv=None, scale: float = ITER_SCALE):
+    """ofx_motion_compensate on host arrays: (mc uint8 [h, w], stats int64 [4]) of "motion compensation" in include/ofx.h --
+    next1 shifted by uv (None: not shifted) and warped by scale * flow, and (w*h, sum |prev1 - next1|, sum |prev1 - mc|, pixels
+    not warped)."""
+    import torch
+
+    L = _lib.load()
+    h, w = prev1.shape
+    assert next1.shape == (h, w) and tuple(flow.shape) == (h, w, 2)
+    tp, pp = _u8_plane(prev1)
+    tn, pn = _u8_plane(next1)
+    td = torch.zeros_like(tp)
+    tf = torch.from_numpy(np.ascontiguousarray(flow, dtype=np.float32)).cuda()
+    tuv = None if uv is None else torch.tensor(list(uv), dtype=torch.float32, device="cuda")
+    ts = torch.zeros(4, dtype=torch.int64, device="cuda")
+    check(L.ofx_motion_compensate(tp.data_ptr(), pp, tn.data_ptr(), pn, w, h, tf.data_ptr(), None if tuv is None else tuv.data_ptr(),
+                                  float(scale), td.data_ptr(), pp, ts.data_ptr(), _stream_ptr()), "ofx_motion_compensate")
+    torch.cuda.synchronize()
+    return td[:, :w].cpu().numpy(), ts.cpu().numpy()
 
 
 def flow_pair(prev1: np.ndarray, next1: np.ndarray, levels: int, window: int, mode: str, iters: int = 1, min_det: float = 0.0) -> List[np.ndarray]:
@@ -713,3 +779,25 @@ def video_tracks(frames, points, levels: int, window: int, mode: str = "lk_float
     _run_clip(frames, levels, window, mode, iters, min_det, batch, frontend, bilateral, fast,
               lambda s: s.stream_tracks(state, status, positions[1:], level))
     return positions, status
+
+
+def video_motion(frames, levels: int, window: int, mode: str = "lk_float", level: int = 0, iters: int = 1, min_det: float = 0.0,
+                 batch: Optional[int] = None, scale: float = ITER_SCALE, frontend: Optional[str] = None, bilateral=(9, 2.0, 10.0),
+                 fast: bool = False):
+    """Every frame of a clip pulled back onto its predecessor by the pair's flow, and the pair's quality sums, by the pipeline's
+    motion-compensation stage (Session.stream_motion).  frames and the other arguments as video_flow.  Returns (uint8
+    [N-1, H >> level, W >> level], int64 [N-1, 4]): out[p-1] is frame p of `level` motion-compensated onto frame p-1, stats[p-1] =
+    (pixels, sum |prev - next|, sum |prev - mc|, pixels not warped) of pair p."""
+    import torch
+
+    N, H, W = _clip_shape(frames)
+    assert 0 <= level < levels
+    hl, wl = H >> level, W >> level
+    pitch = (wl + 3) // 4 * 4
+    stride = (hl * pitch + 15) // 16 * 16     # bytes from slot to slot
+    flat = torch.zeros((N - 1) * stride, dtype=torch.uint8, device=frames.device)
+    ring = flat.as_strided((N - 1, hl, wl), (stride, pitch, 1))
+    stats = torch.zeros((N - 1, 4), dtype=torch.int64, device=frames.device)
+    _run_clip(frames, levels, window, mode, iters, min_det, batch, frontend, bilateral, fast,
+              lambda s: s.stream_motion(ring, stats, level, scale))
+    return ring, stats

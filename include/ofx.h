@@ -281,6 +281,31 @@ typedef struct ofx_warp_desc {
 } ofx_warp_desc;
 int ofx_warp_levels(const ofx_warp_desc *levels, int n, void *stream);
 
+/* ---- motion compensation -------------------------------------------------
+ * The next image of a pair pulled back onto the previous one by the pair's flow -- "the image the next refinement iteration
+ * would have read" -- and four sums that say how good the flow was.  THE definition (everything else quotes it), for one
+ * level of w x h pixels:
+ *   inputs  prev, next: u8 planes, each with its own row pitch; flow: interleaved (u, v) float32, w x h, tightly packed;
+ *           uv: two floats on the device, the level's global shift (NULL = (0, 0)); scale.
+ *   sh    = what ofx_shift_1ch(next, ., uv) writes, its out-of-image rule included: next((int)(x+u), (int)(y+v)) when that
+ *           lands inside the image, else next(x, y) if 3*(y*w+x) < w*h, else 0.  (uv = (0, 0) is the identity.)
+ *   mc    = what ofx_warp_levels writes for {src = sh, flow, scale}: orc_warp_bilinear_u8's operation order, replicate
+ *           border, and a pixel with |x + scale*u| > 1e9, |y + scale*v| > 1e9 or a NaN there is NOT WARPED: mc = sh.
+ *   stats = four int64:  [0] w*h   [1] sum |prev - next| (the unshifted next: no motion model at all)
+ *                        [2] sum |prev - mc|             [3] the number of pixels that were not warped.
+ * mc equals that two-launch chain bit for bit, and the sums are integers: they depend on no order, tile or batch.
+ * stats[2] is the photometric error the solve was minimising; stats[2] / stats[1] says what the flow bought, and a scene
+ * cut or a failed pair shows as a ratio near (or above) 1.
+ *
+ * ofx_motion_compensate: one level, stateless, one launch with the shift fused (no shifted plane is written).  Pitches >= w;
+ * d_flow and d_stats 8-byte aligned; otherwise OFX_E_INVALID.  d_dst (rows dst_pitch apart; bytes beyond column w - 1 are
+ * left untouched) or d_stats (4 values, overwritten) may be NULL on its own.  No tap reads outside the h x pitch bytes of
+ * d_prev / d_next, whatever the flow holds. */
+int ofx_motion_compensate(const uint8_t *d_prev, int prev_pitch, const uint8_t *d_next, int next_pitch, int w, int h,
+                          const float *d_flow, const float *d_uv /* NULL = no shift */, float scale,
+                          uint8_t *d_dst /* may be NULL */, int dst_pitch, int64_t *d_stats /* may be NULL; 4 values, overwritten */,
+                          void *stream);
+
 /* main.cu:138-147: dense flow at `level` = sum_k 2^(k-level) flow_k(y>>s, x>>s). */
 int ofx_compose_flow(const float *const *d_flow_levels, int w, int h, int levels, int level, float *d_dst,
                      void *stream);
@@ -580,6 +605,33 @@ int ofx_session_stream_arrows(ofx_session *s, int level, int arrow_res, int32_t 
 int ofx_session_arrows_of(ofx_session *s, int pair, int32_t **d_ptr, int *ny, int *nx);
 int ofx_session_stream_tracks(ofx_session *s, int level, float *d_points, int32_t *d_status, int n_points, float *d_history,
                               size_t slot_stride_bytes, int n_slots);
+/* The stream pipeline's motion-compensation stage: mc and stats of "motion compensation" above, at `level` with `scale`
+ * (OFX_ITER_SCALE for the session's own flows), for every pair the pipeline completes.  Pair p's image goes to slot
+ * (p - 1) mod n_slots at d_ring + slot * slot_stride_bytes, rows x row_pitch bytes (the bytes of a row beyond the level's
+ * width are left untouched), its four int64 to d_stats_ring + 4 * slot.  Every call of ofx_session_stream_submit /
+ * _submit_frames / _drain that completes pairs enqueues ONE more kernel launch on its `stream` for all those pairs, after the
+ * compose ring's and the sampled stage's (preceded by the memset that zeroes the pairs' stats slots; no timing kind records
+ * it).
+ *   row_pitch a multiple of 4 and >= the level's width, d_ring 16-byte aligned, slot_stride_bytes a multiple of 16 and at
+ *   least rows * row_pitch, n_slots >= stream_batch, d_stats_ring 8-byte aligned, 0 <= level < levels; otherwise OFX_E_INVALID.
+ *   d_ring or d_stats_ring may be NULL on its own: image only, or stats only (which moves one byte per pixel less).  Both
+ *   NULL turns the stage off (the default: nothing is launched or allocated).
+ * Only before the first frame of a stream (OFX_E_STATE once a stream has frames); stays in effect for later streams, whose
+ * pairs count from 1 again.  Sharded sessions and frames_partial: OFX_E_UNSUPPORTED (a warp crosses shard rows).
+ * Sources: the launch reads, for pair p, level `level` of frames p - 1 and p as the LK stage saw them (each with the pitch it was
+ * submitted with: the borrowed level-0 frames of ONE stream must share a pitch, a later stream may bring another), the pair's shift vector of that level (none at the coarsest) and the flow
+ * ofx_session_flow_of points to.  All of them are intact in the call that completes the pair: that call's own LK stage reads
+ * both image sets and the pair's shift-vector slot, a set is rewritten 3B + 2 (two stages: 2B + 2) frames later and a slot
+ * by the corner stage of a later tick, and the last launch of a tick always leaves the final flow in the set flow_of reports.
+ * LIFETIME of borrowed frames: unchanged.  Frames p - 1 and p are read by the LK launch of the very call that enqueues this
+ * one, so frame f is still last read by a launch of the submit of frame f + dB (ofx_params.borrow_frames).
+ * Lifetime of a slot: as the compose ring's. */
+int ofx_session_stream_motion(ofx_session *s, int level, float scale, uint8_t *d_ring, int row_pitch, size_t slot_stride_bytes,
+                              int n_slots, int64_t *d_stats_ring /* n_slots x 4, may be NULL */);
+/* Slot of `pair` while it is one of the newest n_slots pairs of the motion stage: its image (NULL without an image ring) and
+ * row pitch, and its four sums (NULL without a stats ring).  OFX_E_STATE without the stage, OFX_E_INVALID for a pair not (or no
+ * longer) in the ring. */
+int ofx_session_motion_of(ofx_session *s, int pair, uint8_t **d_ptr, int *row_pitch, int64_t **d_stats);
 /* Colour frames into the stream pipeline (main.cu:222-272 as one device-resident pipeline): with the front end set, every call
  * that launches a tick first enqueues ONE launch of the front end (ofx_frontend_1ch) for that tick's colour frames on its `stream`,
  * writing the filtered one-channel planes the tick then reads as its frames:
