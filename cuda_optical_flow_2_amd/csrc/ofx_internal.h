@@ -152,6 +152,23 @@ struct ofx_motion_batch {
 };
 int ofx_motion_batch_launch(const ofx_motion_batch *a, void *stream);
 
+// the forward-backward check (consistency.hip; the definition: "forward-backward consistency" in include/ofx.h) for
+// n <= OFX_STREAM_MAX_BATCH pairs of one w x h level in ONE launch.  Pair i reads fwd[i] and bwd[i] (w x h interleaved float32,
+// 8-byte aligned) and writes the classes at mask[i] (rows mask_pitch apart, bytes beyond column w - 1 untouched; NULL = none), e at
+// err[i] (w floats per row, 4-byte aligned; NULL = none) and ADDS its four counts to stats[i] (8-byte aligned; NULL = none), which
+// the launch function zeroes on the stream first, consecutive slots by one memset.  A pair needs one output at least.  The launch
+// function works out by itself whether whole quads go out as one dword (every mask and mask_pitch 4-byte aligned) and as four
+// floats (every err 16-byte aligned, w a multiple of 4).  Every argument is checked before anything is enqueued.
+struct ofx_consistency_batch {
+    const float *fwd[OFX_STREAM_MAX_BATCH], *bwd[OFX_STREAM_MAX_BATCH];
+    uint8_t *mask[OFX_STREAM_MAX_BATCH];
+    float *err[OFX_STREAM_MAX_BATCH];
+    unsigned long long *stats[OFX_STREAM_MAX_BATCH];
+    int n, w, h, mask_pitch;
+    float scale, alpha, beta;
+};
+int ofx_consistency_batch_launch(const ofx_consistency_batch *a, void *stream);
+
 // the stream pipeline's colour front end (frontend.hip): the filter's tables for one (window, sigma_s, sigma_b), built once on the
 // host (window 0: grey frames only; an unsupported window is OFX_E_UNSUPPORTED), and one launch over n <= OFX_STREAM_MAX_BATCH
 // frames (modes[i]: OFX_FRONTEND_GREY / _BILATERAL / _BILATERAL_FAST; a call that mixes the two bilateral forms launches twice)

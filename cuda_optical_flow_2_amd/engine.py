@@ -673,15 +673,18 @@ def _ring_for(N, H, W, level, device, out):
     return out
 
 
-def _run_clip(frames, levels, window, mode, iters, min_det, batch, frontend, bilateral, fast, attach):
+def _run_clip(frames, levels, window, mode, iters, min_det, batch, frontend, bilateral, fast, attach, order=None):
     """What video_flow, video_arrows and video_tracks share: the clip (grey [N, H, W] or colour [N, H, W, 3]) through the stream
     pipeline, in the configuration video_flow documents; attach(session) sets the output stages before the stream begins.
+    order: the frame indices in the order they are submitted (a permutation of range(N); None = range(N)) -- the frames
+    themselves are not moved.
     Grey frames are read in place when their pitch and alignment allow it, otherwise through copies.  A colour clip's front end
     writes the session's own planes, so the pipeline always runs in its fast configuration (borrowed planes, two stages)
     whatever the clip's layout; only the colour frames' own alignment matters."""
     import torch
 
     N, H, W = _clip_shape(frames)
+    assert order is None or sorted(order) == list(range(N)), "order: every frame index once"
     colour = frames.dim() == 4
     if colour:
         frontend = frontend or "main_cu"
@@ -718,7 +721,7 @@ def _run_clip(frames, levels, window, mode, iters, min_det, batch, frontend, bil
         attach(s)
         s.stream_begin()
         submit = s.stream_submit_3ch if colour else s.stream_submit
-        for i in range(N):
+        for i in (range(N) if order is None else order):
             submit(frames[i])
         while s.stream_drain() != -2:
             pass
@@ -801,3 +804,95 @@ def video_motion(frames, levels: int, window: int, mode: str = "lk_float", level
     _run_clip(frames, levels, window, mode, iters, min_det, batch, frontend, bilateral, fast,
               lambda s: s.stream_motion(ring, stats, level, scale))
     return ring, stats
+
+
+def _beta(beta_px2: float, scale: float) -> float:
+    """beta of "forward-backward consistency" from a floor in pixels^2: beta_px2 / scale^2 in float64, rounded once to float32"""
+    return float(np.float32(np.float64(beta_px2) / (np.float64(np.float32(scale)) * np.float64(np.float32(scale)))))
+
+
+def flow_consistency(fwd: np.ndarray, bwd: np.ndarray, scale: float = ITER_SCALE, alpha: float = 0.01, beta_px2: float = 0.5,
+                     want_err: bool = False):
+    """ofx_flow_consistency on host arrays [h, w, 2]: the forward-backward check of include/ofx.h ("forward-backward
+    consistency") of fwd (frame a -> b) against bwd (frame b -> a).  Returns (mask uint8 [h, w], stats int64 [4]) -- the class of
+    every pixel (0 consistent, 1 inconsistent, 2 leaves the frame, 3 undefined) and (w*h, pixels of class 1, 2, 3) -- and, with
+    want_err, err float32 [h, w] as well: the squared round-trip error in field units, +Inf for classes 2 and 3.  The
+    tolerance is alpha * (|fwd|^2 + |bwd there|^2) + beta_px2 / scale^2."""
+    import torch
+
+    L = _lib.load()
+    h, w, _ = fwd.shape
+    assert tuple(fwd.shape) == (h, w, 2) and tuple(bwd.shape) == (h, w, 2)
+    tf = torch.from_numpy(np.array(fwd, dtype=np.float32, order="C")).cuda()    # (a copy: the caller's array may be read-only)
+    tb = torch.from_numpy(np.array(bwd, dtype=np.float32, order="C")).cuda()
+    tm = torch.zeros((h, w), dtype=torch.uint8, device="cuda")
+    ts = torch.zeros(4, dtype=torch.int64, device="cuda")
+    te = torch.zeros((h, w), dtype=torch.float32, device="cuda") if want_err else None
+    check(L.ofx_flow_consistency(tf.data_ptr(), tb.data_ptr(), w, h, float(scale), float(alpha), _beta(beta_px2, scale), tm.data_ptr(), w,
+                                 te.data_ptr() if want_err else None, ts.data_ptr(), _stream_ptr()), "ofx_flow_consistency")
+    torch.cuda.synchronize()
+    out = (tm.cpu().numpy(), ts.cpu().numpy())
+    return out + (te.cpu().numpy(),) if want_err else out
+
+
+def _slot_ptrs(ring):
+    return [ring.data_ptr() + p * int(ring.stride(0)) * ring.element_size() for p in range(int(ring.shape[0]))]
+
+
+def _consistency_pairs(fwd_ptrs, bwd_ptrs, h, w, device, scale, alpha, beta):
+    """ofx_flow_consistency_batch over P pairs of device fields [h, w, 2] given by their addresses (fwd_ptrs[i] against
+    bwd_ptrs[i]), up to OFX_STREAM_MAX_BATCH pairs per launch: (mask uint8 [P, h, w], stats int64 [P, 4])."""
+    import torch
+
+    L = _lib.load()
+    P = len(fwd_ptrs)
+    mask = torch.empty((P, h, w), dtype=torch.uint8, device=device)
+    stats = torch.empty((P, 4), dtype=torch.int64, device=device)
+    mp, sp = _slot_ptrs(mask), _slot_ptrs(stats)
+    for p0 in range(0, P, 16):
+        n = min(16, P - p0)
+        arr = [(_vp * n)(*ptrs[p0:p0 + n]) for ptrs in (fwd_ptrs, bwd_ptrs, mp, sp)]
+        check(L.ofx_flow_consistency_batch(arr[0], arr[1], n, w, h, scale, alpha, beta, arr[2], w, None, arr[3], _stream_ptr()),
+              "ofx_flow_consistency_batch")
+    return mask, stats
+
+
+def video_consistency(frames, levels: int, window: int, mode: str = "lk_float", level: int = 0, iters: int = 1, min_det: float = 0.0,
+                      batch: Optional[int] = None, alpha: float = 0.01, beta_px2: float = 0.5, both: bool = False,
+                      return_flows: bool = False, frontend: Optional[str] = None, bilateral=(9, 2.0, 10.0), fast: bool = False):
+    """Which pixels of every pair's flow can be trusted: the forward-backward check of include/ofx.h ("forward-backward
+    consistency") for every consecutive pair of a clip.  The clip goes through the stream pipeline twice with a compose ring at
+    `level` -- once as it is, once in reverse frame order (the frames are not copied) -- and the pairs then go through
+    ofx_flow_consistency_batch, up to 16 per launch, straight out of the two rings.  frames and the other arguments as
+    video_flow; the tolerance is alpha * (|fwd|^2 + |bwd there|^2) + beta_px2 / OFX_ITER_SCALE^2.
+
+    Returns (mask uint8 [N-1, H >> level, W >> level], stats int64 [N-1, 4]): mask[p] holds the class of every pixel of the flow
+    frame p -> frame p+1 (0 consistent, 1 inconsistent, 2 leaves the frame, 3 undefined), stats[p] = (pixels, pixels of class
+    1, 2, 3).  both=True appends (mask_b, stats_b), the same for the backward direction (the flow frame p+1 -> frame p checked
+    against the forward one: occlusion as seen from frame p+1).  return_flows=True appends the two rings, float32
+    [N-1, H >> level, W >> level, 2]: fwd[p] is the flow frame p -> p+1, and bwd, in the REVERSED run's order, holds the flow
+    frame p+1 -> p in bwd[N-2-p].
+
+    Memory: the two rings take 2 * (N-1) * h * w * 8 bytes (h, w of `level`) whether they are returned or not.
+
+    A colour clip's default front end here is "bilateral": "main_cu" treats the first frame of a run differently from the
+    others, so the reversed run would see other images than the forward one, and it is refused."""
+    N, H, W = _clip_shape(frames)
+    assert 0 <= level < levels
+    if frames.dim() == 4:
+        frontend = frontend or "bilateral"
+        assert frontend != "main_cu", ("video_consistency: frontend 'main_cu' filters every frame but a run's first, and the reversed run starts "
+                                       "at the other end of the clip: use 'bilateral' or 'grey'")
+    rings = []
+    for order in (None, range(N - 1, -1, -1)):
+        ring = _ring_for(N, H, W, level, frames.device, None)
+        _run_clip(frames, levels, window, mode, iters, min_det, batch, frontend, bilateral, fast,
+                  lambda s, ring=ring: s.stream_compose(ring, level), order=order)
+        rings.append(ring)
+    fwd, bwd = rings
+    beta, hl, wl = _beta(beta_px2, ITER_SCALE), H >> level, W >> level
+    fp, bp = _slot_ptrs(fwd), _slot_ptrs(bwd)[::-1]    # the backward field of forward pair p is slot N-2-p of the reversed run's ring
+    out = _consistency_pairs(fp, bp, hl, wl, frames.device, ITER_SCALE, float(alpha), beta)
+    if both:
+        out += _consistency_pairs(bp, fp, hl, wl, frames.device, ITER_SCALE, float(alpha), beta)
+    return out + (fwd, bwd) if return_flows else out

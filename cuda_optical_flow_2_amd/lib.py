@@ -111,6 +111,9 @@ _SIGS = {
     "ofx_motion_compensate": [_vp, _i, _vp, _i, _i, _i, _vp, _vp, C.c_float, _vp, _i, _vp, _vp],
     "ofx_session_stream_motion": [_vp, _i, C.c_float, _vp, _i, C.c_size_t, _i, _vp],
     "ofx_session_motion_of": [_vp, _i, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_vp)],
+    "ofx_flow_consistency": [_vp, _vp, _i, _i, C.c_float, C.c_float, C.c_float, _vp, _i, _vp, _vp, _vp],
+    "ofx_flow_consistency_batch": [C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, C.c_float, C.c_float, C.c_float, C.POINTER(_vp), _i,
+                                   C.POINTER(_vp), C.POINTER(_vp), _vp],
     "ofx_session_stream_frontend": [_vp, _i, _i, _d, _d, _i],
     "ofx_session_stream_submit_3ch": [_vp, _vp, _i, _vp, C.POINTER(_i)],
     "ofx_session_stream_submit_frames_3ch": [_vp, C.POINTER(_vp), C.POINTER(_i), _i, _i, _vp, C.POINTER(_i)],

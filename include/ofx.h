@@ -329,6 +329,51 @@ int ofx_sample_arrows(const float *const *d_flow_levels, int w, int h, int level
 int ofx_advect_points(const float *const *d_flow_levels, int w, int h, int levels, int level, int pair, float *d_points, int32_t *d_status,
                       int n_points, void *stream);
 
+/* ---- forward-backward consistency -------------------------------------------
+ * Which pixels of a dense field can be trusted: follow the forward vector into the next frame, read the backward field
+ * there, and see whether the two cancel.  THE definition (everything else quotes it), for one pair at one level of w x h
+ * pixels:
+ *   inputs  fwd: the field of frame a -> frame b; bwd: the field of frame b -> frame a (the same clip through the same
+ *           pipeline in reverse order).  Both interleaved (u, v) float32, w x h, tightly packed, 8-byte aligned -- in practice
+ *           two ofx_compose_flow fields.  scale: field units -> pixels (OFX_ITER_SCALE for this library's flows, 1 for fields
+ *           in pixels).  alpha >= 0, beta >= 0, both finite; beta is in squared FIELD units.
+ * Every float32 operation is rounded once, nothing is fused, denormals are kept.  For pixel (x, y) with (u, v) = fwd(y, x):
+ *   1. px = (float)x + scale*u, py = (float)y + scale*v: the product rounded, then the sum (ofx_warp_levels' order).
+ *   2. unless |px| <= 1e9 && |py| <= 1e9 (a NaN fails): class 3, UNDEFINED.
+ *   3. else if px < 0 || px > (float)(w-1) || py < 0 || py > (float)(h-1): class 2, LEAVES -- the vector points out of the
+ *      frame.  Nothing is clamped and bwd is not read.
+ *   4. else x0 = (int)px, y0 = (int)py, fx = px - (float)x0, fy = py - (float)y0, x1 = min(x0+1, w-1), y1 = min(y0+1, h-1).
+ *   5. for each component c of bwd, with b00 = bwd(y0,x0), b01 = bwd(y0,x1), b10 = bwd(y1,x0), b11 = bwd(y1,x1):
+ *        a = b00 + fx*(b01 - b00);  c' = b10 + fx*(b11 - b10);  r_c = a + fy*(c' - a)
+ *      (the blend of orc_warp_bilinear_u8, on floats).  In the last column x1 == x0, so b01 IS b00 (and b11 is b10) whatever
+ *      lies behind the pixel in memory; likewise in the last row.
+ *   6. du = u + r_u, dv = v + r_v, e = du*du + dv*dv, m = (u*u + v*v) + (r_u*r_u + r_v*r_v), thr = alpha*m + beta.
+ *   7. unless |e| <= FLT_MAX: class 3.  Else class 0, CONSISTENT, when e <= thr, else class 1, INCONSISTENT.
+ *   outputs, each may be absent but not all of them:
+ *     mask  = u8, rows mask_pitch >= w apart, the class; bytes beyond column w - 1 are left untouched.
+ *     err   = float32, w per row, tightly packed: e for classes 0 and 1, +Inf (0x7f800000) for classes 2 and 3; never a NaN.
+ *     stats = four int64:  [0] w*h   [1] pixels of class 1   [2] of class 2   [3] of class 3.
+ * The counts are integers: they depend on no order, tile or batch.  The check is one-sided: the other direction (occlusion
+ * as seen from frame b) is the same call with the fields swapped.  e is the squared round-trip error in field units; alpha
+ * scales the tolerance with the squared magnitudes of the two vectors, beta is its floor (0.01 and 0.5 px^2 are the usual
+ * choice: beta = 0.5 / scale^2).
+ *
+ * ofx_flow_consistency: one pair, one launch.  ofx_flow_consistency_batch: 1 <= n <= OFX_STREAM_MAX_BATCH pairs of one size in
+ * ONE launch; an output array may be NULL (that output is then off for all pairs), the entries of a non-NULL array must be
+ * non-NULL, at least one output array is required; the host arrays are read before the call returns.  w*h < 2^28; fwd and bwd
+ * 8-byte, err 4-byte, stats 8-byte aligned; mask_pitch >= w; scale, alpha and beta as above; otherwise OFX_E_INVALID, before
+ * anything is enqueued.  No tap reads outside the w*h*8 bytes of a field, whatever the fields hold. */
+#define OFX_FB_CONSISTENT 0
+#define OFX_FB_INCONSISTENT 1
+#define OFX_FB_LEAVES 2
+#define OFX_FB_UNDEFINED 3
+int ofx_flow_consistency(const float *d_fwd, const float *d_bwd, int w, int h, float scale, float alpha, float beta,
+                         uint8_t *d_mask /* may be NULL */, int mask_pitch, float *d_err /* may be NULL */,
+                         int64_t *d_stats /* may be NULL; 4 values, overwritten */, void *stream);
+int ofx_flow_consistency_batch(const float *const *d_fwd, const float *const *d_bwd, int n, int w, int h, float scale,
+                               float alpha, float beta, uint8_t *const *d_mask, int mask_pitch, float *const *d_err,
+                               int64_t *const *d_stats, void *stream);
+
 /* ---- layout helpers ------------------------------------------------------ */
 int ofx_extract_ch0(const uint8_t *d_src3, uint8_t *d_dst1, int w, int h, int dst_pitch, void *stream);
 int ofx_replicate_3ch(const uint8_t *d_src1, int src_pitch, uint8_t *d_dst3, int w, int h, void *stream);
