@@ -1,0 +1,370 @@
+// The pixel displacement (ofx_flow_displacement, the stream pipeline's ofx_session_stream_displacement) and frame interpolation
+// (ofx_interpolate_frames, ofx_interpolate_frames_batch).  The definitions are the comment blocks "pixel displacement" and "frame
+// interpolation" in include/ofx.h; every float32 operation below is the definition's, in its order, and the build compiles with
+// -ffp-contract=off, so nothing is fused.
+//
+// Displacement: elementwise, blockIdx.y = pair, floorf(uv) once per thread.  Where every flow and destination of the launch is
+// 16-byte aligned a thread moves two pixels per 16-byte load and store, and an odd last pixel goes by 8 bytes; otherwise every
+// pixel goes by 8 bytes (the fields are 8-byte aligned by contract).
+//
+// Interpolation: a thread owns four adjacent pixels of a row (a quad) and takes kQuads quads, one after the other, as
+// consistency.hip and motion_ring.hip do.  A quad's Dab and Dba arrive as four 16-byte buffer loads ONCE -- the NEXT quad's go
+// out before this quad's taps -- and the thread then loops over the launch's times with the fields in registers: per pair the
+// launch reads 16 B/px of fields whatever the number of frames it writes, and the tap bytes come from two planes that stay
+// cache-resident across the passes.  Every load goes through a buffer resource of exactly the plane's (h - 1) * pitch + w bytes
+// or the field's w * h * 8 bytes; a pixel past the row's ragged end gets offsets beyond the resource and loads zeros nobody looks
+// at, and the sampling position is clamped (or the pixel's own) before it becomes an offset, so no field value, however wild,
+// reads outside a plane.
+//
+// The two taps of a tap row are the 2 adjacent bytes at y * pitch + x0: one 16-bit load -- EXCEPT in the last column, where the
+// definition's right tap is the pixel itself (x1 == x0) and the byte behind it belongs to the row's padding, the next row, or
+// nothing (the lk_body_warp.h / motion_ring.hip rule).  So a lane proves x0 < w - 1 for its four pixels on both sides and then
+// takes sixteen 16-bit loads per time; any other lane takes thirty-two byte loads, the right tap AT column x1.  (A wave with such
+// a lane runs both branches in turn; only waves whose positions reach the last column have one.)  All taps of a time are issued
+// before the first is used.
+//
+// A quad of a frame leaves as one dword where the quad is whole and every destination, dst_pitch and the time stride are 4-byte
+// aligned, else as bytes.  The counts: a thread keeps one packed counter per time (8 bits per class: at most 16 pixels a thread)
+// in its own LDS word, touched only for a quad that has a pixel of class 1, 2 or 3; at the end each time's counters go through a
+// wave reduction by __shfl_xor, the block's four waves through LDS, then one 64-bit atomicAdd per non-zero count per block;
+// block 0 adds w * h.  ofx_interp_batch_launch zeroes the words of every slot on the stream first.
+#include <string.h>
+
+#include "ofx_internal.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kQuads = 4;                      // quads (four pixels) per thread, kThreads apart in row-major order
+constexpr int kVecs = 4;                       // displacement: 16-byte (or 8-byte) items per thread, kThreads apart
+constexpr uint32_t kNowhere = 0x80000000u;     // a buffer offset beyond every plane and field (both are < 2^31 bytes): loads 0
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base, int bytes)
+{
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, bytes, 0x00027000);
+}
+
+__global__ __launch_bounds__(kThreads) void displacement_kernel(const ofx_displacement_batch A, const int vec16)
+{
+    const int b = blockIdx.y;
+    const float *flow = A.flow[b];
+    float *dst = A.dst[b];
+    const float scale = A.scale;
+    float fu = 0.0f, fv = 0.0f; // (NULL: the first term is 0.0f, and the add is still performed)
+    if (A.uv[b]) fu = __builtin_floorf(A.uv[b][0]), fv = __builtin_floorf(A.uv[b][1]);
+    const uint32_t n_px = (uint32_t)A.w * (uint32_t)A.h;
+    if (vec16) {
+        const uint32_t n_vec = n_px >> 1;
+#pragma unroll
+        for (int g = 0; g < kVecs; ++g) {
+            const uint32_t i = (blockIdx.x * kVecs + g) * kThreads + threadIdx.x;
+            if (i >= n_vec) break;
+            const f32x4 f = reinterpret_cast<const f32x4 *>(flow)[i];
+            f32x4 d;
+            d[0] = fu + scale * f[0], d[1] = fv + scale * f[1], d[2] = fu + scale * f[2], d[3] = fv + scale * f[3];
+            reinterpret_cast<f32x4 *>(dst)[i] = d;
+        }
+        if ((n_px & 1u) && blockIdx.x == 0 && threadIdx.x == 0) { // the odd last pixel
+            const f32x2 f = reinterpret_cast<const f32x2 *>(flow)[n_px - 1];
+            f32x2 d;
+            d[0] = fu + scale * f[0], d[1] = fv + scale * f[1];
+            reinterpret_cast<f32x2 *>(dst)[n_px - 1] = d;
+        }
+    } else {
+#pragma unroll
+        for (int g = 0; g < kVecs; ++g) {
+            const uint32_t i = (blockIdx.x * kVecs + g) * kThreads + threadIdx.x;
+            if (i >= n_px) break;
+            const f32x2 f = reinterpret_cast<const f32x2 *>(flow)[i];
+            f32x2 d;
+            d[0] = fu + scale * f[0], d[1] = fv + scale * f[1];
+            reinterpret_cast<f32x2 *>(dst)[i] = d;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void interp_kernel(const ofx_interp_batch A, const int dwords)
+{
+    __shared__ uint32_t cnt[OFX_INTERP_MAX_TIMES][kThreads];
+    __shared__ uint32_t red[kThreads / 64][OFX_INTERP_MAX_TIMES][3];
+    const int b = blockIdx.y;
+    const int w = A.w, h = A.h, wmax = w - 1, hmax = h - 1, nt = A.n_times;
+    const int ap = A.a_pitch[b], bp = A.b_pitch[b];
+    const __amdgpu_buffer_rsrc_t rs_a = make_rsrc(A.a[b], hmax * ap + w), rs_b = make_rsrc(A.b[b], hmax * bp + w);
+    const __amdgpu_buffer_rsrc_t rs_ab = make_rsrc(A.dab[b], w * h * 8), rs_ba = make_rsrc(A.dba[b], w * h * 8);
+    uint8_t *dst = A.dst[b];
+    unsigned long long *stats = A.stats[b];
+    const float wmaxf = (float)wmax, hmaxf = (float)hmax;
+    const uint32_t qrow = (uint32_t)(w + 3) >> 2, n_quads = qrow * (uint32_t)h;
+    if (stats)
+        for (int ti = 0; ti < nt; ++ti) cnt[ti][threadIdx.x] = 0; // (a thread's own words: no barrier needed)
+
+    // a quad's place, and its two fields by four 16-byte loads: no branch for the row's ragged end (its last pixels get the next
+    // row's vectors, or zeros past the field: they take no taps and are never looked at) nor for a quad past the end
+    auto place = [&](int g, int &y, int &x0) -> bool {
+        const uint32_t q = (blockIdx.x * kQuads + g) * kThreads + threadIdx.x;
+        y = (int)(q / qrow), x0 = 4 * (int)(q - (uint32_t)y * qrow);
+        return q < n_quads;
+    };
+    auto load_fields = [&](bool in, int y, int x0, float (&f)[16]) {
+        const uint32_t o = in ? 8u * ((uint32_t)y * (uint32_t)w + (uint32_t)x0) : kNowhere;
+        const f32x4 a0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_ab, o, 0, 0));
+        const f32x4 a1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_ab, o, 16, 0));
+        const f32x4 b0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_ba, o, 0, 0));
+        const f32x4 b1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_ba, o, 16, 0));
+#pragma unroll
+        for (int k = 0; k < 4; ++k) f[k] = a0[k], f[4 + k] = a1[k], f[8 + k] = b0[k], f[12 + k] = b1[k];
+    };
+    // steps 3 to 5 of one side of one pixel, up to the taps: the offsets of the left taps of its two tap rows, whether the right
+    // taps are one byte further (x0 < w - 1) or the same byte, and the fractions.  Returns "usable".
+    auto side = [&](float px, float py, float xf, float yf, int pitch, bool live, uint32_t &o0, uint32_t &o1, uint32_t &dx, float &fx,
+                    float &fy) -> bool {
+        const bool fin = __builtin_fabsf(px) <= 1e9f && __builtin_fabsf(py) <= 1e9f; // (a NaN fails)
+        const bool usable = fin && px >= 0.0f && px <= wmaxf && py >= 0.0f && py <= hmaxf;
+        const float sx = fin ? __builtin_amdgcn_fmed3f(px, 0.0f, wmaxf) : xf;
+        const float sy = fin ? __builtin_amdgcn_fmed3f(py, 0.0f, hmaxf) : yf;
+        const int xi = (int)sx, yi = (int)sy;
+        fx = sx - (float)xi, fy = sy - (float)yi;
+        const int y1 = min(yi + 1, hmax);
+        o0 = live ? (uint32_t)(yi * pitch + xi) : kNowhere, o1 = live ? (uint32_t)(y1 * pitch + xi) : kNowhere;
+        dx = xi < wmax ? 1u : 0u;
+        return usable;
+    };
+
+    int y, x0, y_next = 0, x0_next = 0;
+    float f[16], f_next[16];
+    bool have = place(0, y, x0), have_next = false;
+    load_fields(have, y, x0, f);
+#pragma nounroll
+    for (int g = 0; g < kQuads; ++g) {
+        if (!have) break;
+        // the next quad's fields go out before this quad's taps: their latency runs under them
+        have_next = g + 1 < kQuads && place(g + 1, y_next, x0_next);
+        load_fields(have_next, y_next, x0_next, f_next);
+        const int npx = w - x0 < 4 ? w - x0 : 4;
+        const float yf = (float)y;
+        uint8_t *row = dst + (size_t)y * (size_t)A.dst_pitch + (size_t)x0;
+#pragma nounroll
+        for (int ti = 0; ti < nt; ++ti) {
+            const float t = A.t[ti], c00 = A.c00[ti], c01 = A.c01[ti], c10 = A.c10[ti];
+            // steps 1 to 5, up to the taps.  Index [0]: side a, [1]: side b
+            float fx[2][4], fy[2][4];
+            uint32_t o0[2][4], o1[2][4], dx[2][4], cls[4];
+            bool wide = true;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float abx = f[2 * k], aby = f[2 * k + 1], bax = f[8 + 2 * k], bay = f[8 + 2 * k + 1];
+                const float tax = c00 * abx + c01 * bax, tay = c00 * aby + c01 * bay;
+                const float tbx = c10 * abx + c00 * bax, tby = c10 * aby + c00 * bay;
+                const float xf = (float)(x0 + k);
+                const bool live = k < npx;
+                const bool ua = side(xf + tax, yf + tay, xf, yf, ap, live, o0[0][k], o1[0][k], dx[0][k], fx[0][k], fy[0][k]);
+                const bool ub = side(xf + tbx, yf + tby, xf, yf, bp, live, o0[1][k], o1[1][k], dx[1][k], fx[1][k], fy[1][k]);
+                cls[k] = ua ? (ub ? 0u : 1u) : (ub ? 2u : 3u);
+                wide = wide && (!live || (dx[0][k] & dx[1][k]));
+            }
+            // the taps: per side and pixel (left, right) of the two tap rows in bytes 0 and 1
+            uint32_t r0[2][4], r1[2][4];
+            if (wide) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    r0[0][k] = __builtin_amdgcn_raw_buffer_load_b16(rs_a, o0[0][k], 0, 0);
+                    r1[0][k] = __builtin_amdgcn_raw_buffer_load_b16(rs_a, o1[0][k], 0, 0);
+                    r0[1][k] = __builtin_amdgcn_raw_buffer_load_b16(rs_b, o0[1][k], 0, 0);
+                    r1[1][k] = __builtin_amdgcn_raw_buffer_load_b16(rs_b, o1[1][k], 0, 0);
+                }
+            } else {
+                uint32_t l[2][2][4], r[2][2][4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    l[0][0][k] = __builtin_amdgcn_raw_buffer_load_b8(rs_a, o0[0][k], 0, 0);
+                    r[0][0][k] = __builtin_amdgcn_raw_buffer_load_b8(rs_a, o0[0][k] + dx[0][k], 0, 0);
+                    l[0][1][k] = __builtin_amdgcn_raw_buffer_load_b8(rs_a, o1[0][k], 0, 0);
+                    r[0][1][k] = __builtin_amdgcn_raw_buffer_load_b8(rs_a, o1[0][k] + dx[0][k], 0, 0);
+                    l[1][0][k] = __builtin_amdgcn_raw_buffer_load_b8(rs_b, o0[1][k], 0, 0);
+                    r[1][0][k] = __builtin_amdgcn_raw_buffer_load_b8(rs_b, o0[1][k] + dx[1][k], 0, 0);
+                    l[1][1][k] = __builtin_amdgcn_raw_buffer_load_b8(rs_b, o1[1][k], 0, 0);
+                    r[1][1][k] = __builtin_amdgcn_raw_buffer_load_b8(rs_b, o1[1][k] + dx[1][k], 0, 0);
+                }
+#pragma unroll
+                for (int s = 0; s < 2; ++s)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) r0[s][k] = l[s][0][k] | (r[s][0][k] << 8), r1[s][k] = l[s][1][k] | (r[s][1][k] << 8);
+            }
+            // the taps have arrived: the blends of step 5, then step 6
+            uint32_t out = 0, pk = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float V[2];
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const float p00 = (float)(r0[s][k] & 0xffu), p01 = (float)((r0[s][k] >> 8) & 0xffu);
+                    const float p10 = (float)(r1[s][k] & 0xffu), p11 = (float)((r1[s][k] >> 8) & 0xffu);
+                    const float q0 = p00 + fx[s][k] * (p01 - p00);
+                    const float q1 = p10 + fx[s][k] * (p11 - p10);
+                    V[s] = q0 + fy[s][k] * (q1 - q0);
+                }
+                const float mix = V[0] + t * (V[1] - V[0]);
+                const float v = cls[k] == 1u ? V[0] : cls[k] == 2u ? V[1] : mix;
+                out |= ((uint32_t)(int)(v + 0.5f) & 0xffu) << (8 * k);
+                if (k < npx && cls[k]) pk += 1u << (8 * (cls[k] - 1u));
+            }
+            uint8_t *d = row + (size_t)ti * A.time_stride;
+            if (npx == 4 && dwords) {
+                *reinterpret_cast<uint32_t *>(d) = out;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (k < npx) d[k] = (uint8_t)(out >> (8 * k));
+            }
+            if (stats && pk) cnt[ti][threadIdx.x] += pk;
+        }
+        have = have_next, y = y_next, x0 = x0_next;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) f[k] = f_next[k];
+    }
+    if (!stats) return; // (block-uniform)
+    for (int ti = 0; ti < nt; ++ti) {
+        const uint32_t pk = cnt[ti][threadIdx.x];
+        uint32_t n1 = pk & 0xffu, n2 = (pk >> 8) & 0xffu, n3 = (pk >> 16) & 0xffu;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            n1 += __shfl_xor(n1, o);
+            n2 += __shfl_xor(n2, o);
+            n3 += __shfl_xor(n3, o);
+        }
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][ti][0] = n1, red[threadIdx.x >> 6][ti][1] = n2, red[threadIdx.x >> 6][ti][2] = n3;
+    }
+    __syncthreads();
+    const int ti = threadIdx.x >> 2, c = threadIdx.x & 3; // thread 4 * ti + c: word c of time ti
+    if (ti < nt) {
+        if (c) {
+            unsigned long long s = 0;
+#pragma unroll
+            for (int i = 0; i < kThreads / 64; ++i) s += red[i][ti][c - 1];
+            if (s) atomicAdd(stats + 4 * ti + c, s);
+        } else if (blockIdx.x == 0) {
+            atomicAdd(stats + 4 * ti, (unsigned long long)w * (unsigned long long)h);
+        }
+    }
+}
+
+} // namespace
+
+int ofx_displacement_batch_launch(const ofx_displacement_batch *a, void *stream)
+{
+    const char *who = "ofx_displacement_batch_launch";
+    OFX_REQUIRE(a && a->n >= 1 && a->n <= OFX_STREAM_MAX_BATCH, "%s: bad arguments", who);
+    OFX_REQUIRE(a->w > 0 && a->h > 0, "%s: w = %d, h = %d must be positive", who, a->w, a->h);
+    OFX_REQUIRE((size_t)a->w * (size_t)a->h < ((size_t)1 << 28), "%s: w * h = %d x %d is more than this build takes (2^28 pixels)", who, a->w, a->h);
+    OFX_REQUIRE(__builtin_isfinite(a->scale), "%s: the scale must be finite", who);
+    bool vec16 = true;
+    for (int i = 0; i < a->n; ++i) {
+        OFX_REQUIRE(a->flow[i], "%s: pair %d: d_flow is null", who, i);
+        OFX_REQUIRE(a->dst[i], "%s: pair %d: d_dst is null", who, i);
+        OFX_REQUIRE((((uintptr_t)a->flow[i] | (uintptr_t)a->dst[i]) & 7) == 0, "%s: pair %d: d_flow and d_dst must be 8-byte aligned", who, i);
+        OFX_REQUIRE(((uintptr_t)a->uv[i] & 3) == 0, "%s: pair %d: d_uv must be 4-byte aligned", who, i);
+        vec16 = vec16 && (((uintptr_t)a->flow[i] | (uintptr_t)a->dst[i]) & 15) == 0;
+    }
+    const unsigned n_px = (unsigned)a->w * (unsigned)a->h, items = vec16 ? (n_px >> 1) : n_px, per_block = kThreads * kVecs;
+    dim3 grid(items ? (items + per_block - 1) / per_block : 1, a->n); // (a single pixel on the 16-byte path: the odd-pixel thread alone)
+    hipLaunchKernelGGL(displacement_kernel, grid, dim3(kThreads), 0, ofx_stream(stream), *a, (int)vec16);
+    OFX_HIP(hipGetLastError());
+    return OFX_OK;
+}
+
+extern "C" int ofx_flow_displacement(const float *d_flow, int w, int h, const float *d_uv, float scale, float *d_dst, void *stream)
+{
+    static thread_local ofx_displacement_batch db;
+    memset(&db, 0, sizeof db);
+    db.n = 1, db.w = w, db.h = h, db.scale = scale;
+    db.flow[0] = d_flow, db.uv[0] = d_uv, db.dst[0] = d_dst;
+    return ofx_displacement_batch_launch(&db, stream); // (checks every argument before it enqueues anything)
+}
+
+int ofx_interp_batch_launch(const ofx_interp_batch *a, void *stream)
+{
+    const char *who = "ofx_interp_batch_launch";
+    OFX_REQUIRE(a && a->n >= 1 && a->n <= OFX_STREAM_MAX_BATCH, "%s: bad arguments", who);
+    OFX_REQUIRE(a->w > 0 && a->h > 0, "%s: w = %d, h = %d must be positive", who, a->w, a->h);
+    // (the fields are read through buffer resources: 8 bytes per pixel, below 2^31 bytes)
+    OFX_REQUIRE((size_t)a->w * (size_t)a->h < ((size_t)1 << 28), "%s: w * h = %d x %d is more than this build takes (2^28 pixels)", who, a->w, a->h);
+    OFX_REQUIRE(a->n_times >= 1 && a->n_times <= OFX_INTERP_MAX_TIMES, "%s: n_times = %d is not in 1 .. %d", who, a->n_times, OFX_INTERP_MAX_TIMES);
+    for (int k = 0; k < a->n_times; ++k)
+        OFX_REQUIRE(__builtin_isfinite(a->t[k]) && a->t[k] > 0.0f && a->t[k] < 1.0f, "%s: h_times[%d] = %g is not in (0, 1)", who, k, (double)a->t[k]);
+    OFX_REQUIRE(a->dst_pitch >= a->w, "%s: dst_pitch %d is below the width %d", who, a->dst_pitch, a->w);
+    OFX_REQUIRE(a->n_times == 1 || a->time_stride >= (size_t)a->h * (size_t)a->dst_pitch,
+                "%s: time_stride_bytes %zu is below a frame's h * dst_pitch = %zu bytes", who, a->time_stride, (size_t)a->h * (size_t)a->dst_pitch);
+    bool dwords = (a->dst_pitch & 3) == 0 && (a->n_times == 1 || (a->time_stride & 3) == 0);
+    for (int i = 0; i < a->n; ++i) {
+        OFX_REQUIRE(a->a[i] && a->b[i], "%s: pair %d: a null plane (d_a, d_b)", who, i);
+        OFX_REQUIRE(a->dab[i] && a->dba[i], "%s: pair %d: a null field (d_disp_ab, d_disp_ba)", who, i);
+        OFX_REQUIRE(a->dst[i], "%s: pair %d: d_dst is null", who, i);
+        OFX_REQUIRE(a->a_pitch[i] >= a->w && a->b_pitch[i] >= a->w, "%s: pair %d: a row pitch (a_pitch, b_pitch) below the width %d", who, i, a->w);
+        OFX_REQUIRE((size_t)a->h * (size_t)a->a_pitch[i] < ((size_t)1 << 31) && (size_t)a->h * (size_t)a->b_pitch[i] < ((size_t)1 << 31),
+                    "%s: pair %d: a plane of 2^31 bytes or more", who, i);
+        OFX_REQUIRE((((uintptr_t)a->dab[i] | (uintptr_t)a->dba[i]) & 7) == 0, "%s: pair %d: the fields (d_disp_ab, d_disp_ba) must be 8-byte aligned", who, i);
+        OFX_REQUIRE(((uintptr_t)a->stats[i] & 7) == 0, "%s: pair %d: d_stats must be 8-byte aligned", who, i);
+        dwords = dwords && ((uintptr_t)a->dst[i] & 3) == 0;
+    }
+    // everything is checked: zero the stats slots (4 * n_times words a pair), one memset per run of consecutive slots
+    const size_t words = 4 * (size_t)a->n_times;
+    for (int i = 0; i < a->n;) {
+        int e = i + 1;
+        if (!a->stats[i]) {
+            i = e;
+            continue;
+        }
+        while (e < a->n && a->stats[e] == a->stats[i] + words * (size_t)(e - i)) ++e;
+        OFX_HIP(hipMemsetAsync(a->stats[i], 0, (size_t)(e - i) * words * sizeof(unsigned long long), ofx_stream(stream)));
+        i = e;
+    }
+    const unsigned quads = (unsigned)((a->w + 3) >> 2) * (unsigned)a->h, per_block = kThreads * kQuads;
+    dim3 grid((quads + per_block - 1) / per_block, a->n);
+    hipLaunchKernelGGL(interp_kernel, grid, dim3(kThreads), 0, ofx_stream(stream), *a, (int)dwords);
+    OFX_HIP(hipGetLastError());
+    return OFX_OK;
+}
+
+extern "C" int ofx_interpolate_frames_batch(const uint8_t *const *d_a, const int *a_pitches, const uint8_t *const *d_b, const int *b_pitches, int n,
+                                            int w, int h, const float *const *d_disp_ab, const float *const *d_disp_ba, const float *h_times,
+                                            int n_times, uint8_t *const *d_dst, int dst_pitch, size_t time_stride_bytes, int64_t *const *d_stats,
+                                            void *stream)
+{
+    const char *who = "ofx_interpolate_frames_batch";
+    OFX_REQUIRE(d_a && d_b && a_pitches && b_pitches, "%s: null plane or pitch array (d_a, d_b, a_pitches, b_pitches)", who);
+    OFX_REQUIRE(d_disp_ab && d_disp_ba, "%s: null field array (d_disp_ab, d_disp_ba)", who);
+    OFX_REQUIRE(d_dst, "%s: d_dst is null", who);
+    OFX_REQUIRE(h_times, "%s: h_times is null", who);
+    OFX_REQUIRE(n >= 1 && n <= OFX_STREAM_MAX_BATCH, "%s: n = %d is not in 1 .. %d", who, n, OFX_STREAM_MAX_BATCH);
+    OFX_REQUIRE(n_times >= 1 && n_times <= OFX_INTERP_MAX_TIMES, "%s: n_times = %d is not in 1 .. %d", who, n_times, OFX_INTERP_MAX_TIMES);
+    static thread_local ofx_interp_batch ib;
+    memset(&ib, 0, sizeof ib);
+    ib.n = n, ib.w = w, ib.h = h, ib.n_times = n_times, ib.dst_pitch = dst_pitch, ib.time_stride = time_stride_bytes;
+    for (int k = 0; k < n_times; ++k) { // the definition's host step, in float32
+        const float t = h_times[k], omt = 1.0f - t;
+        ib.t[k] = t, ib.c00[k] = -(omt * t), ib.c01[k] = t * t, ib.c10[k] = omt * omt;
+    }
+    for (int i = 0; i < n; ++i) {
+        OFX_REQUIRE(d_a[i] && d_b[i] && d_disp_ab[i] && d_disp_ba[i] && d_dst[i] && (!d_stats || d_stats[i]), "%s: pair %d: a null entry in an array", who, i);
+        ib.a[i] = d_a[i], ib.a_pitch[i] = a_pitches[i], ib.b[i] = d_b[i], ib.b_pitch[i] = b_pitches[i];
+        ib.dab[i] = d_disp_ab[i], ib.dba[i] = d_disp_ba[i], ib.dst[i] = d_dst[i];
+        ib.stats[i] = d_stats ? reinterpret_cast<unsigned long long *>(d_stats[i]) : nullptr;
+    }
+    return ofx_interp_batch_launch(&ib, stream); // (checks every argument before it enqueues anything)
+}
+
+extern "C" int ofx_interpolate_frames(const uint8_t *d_a, int a_pitch, const uint8_t *d_b, int b_pitch, int w, int h, const float *d_disp_ab,
+                                      const float *d_disp_ba, const float *h_times, int n_times, uint8_t *d_dst, int dst_pitch,
+                                      size_t time_stride_bytes, int64_t *d_stats, void *stream)
+{
+    const char *who = "ofx_interpolate_frames";
+    OFX_REQUIRE(d_a && d_b, "%s: a null plane (d_a, d_b)", who);
+    OFX_REQUIRE(d_disp_ab && d_disp_ba, "%s: a null field (d_disp_ab, d_disp_ba)", who);
+    OFX_REQUIRE(d_dst, "%s: d_dst is null", who);
+    return ofx_interpolate_frames_batch(&d_a, &a_pitch, &d_b, &b_pitch, 1, w, h, &d_disp_ab, &d_disp_ba, h_times, n_times, &d_dst, dst_pitch,
+                                        time_stride_bytes, d_stats ? &d_stats : nullptr, stream);
+}

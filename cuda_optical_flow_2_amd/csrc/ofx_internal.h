@@ -169,6 +169,36 @@ struct ofx_consistency_batch {
 };
 int ofx_consistency_batch_launch(const ofx_consistency_batch *a, void *stream);
 
+// the pixel displacement (interp.hip; the definition: "pixel displacement" in include/ofx.h) of n <= OFX_STREAM_MAX_BATCH pairs of
+// one w x h level in ONE launch.  Pair i reads flow[i] (w x h interleaved float32, 8-byte aligned) and uv[i] (two floats on the
+// device; NULL = none) and writes w x h x 2 floats tightly packed at dst[i] (8-byte aligned).  Every argument is checked before
+// anything is enqueued.
+struct ofx_displacement_batch {
+    const float *flow[OFX_STREAM_MAX_BATCH], *uv[OFX_STREAM_MAX_BATCH];
+    float *dst[OFX_STREAM_MAX_BATCH];
+    int n, w, h;
+    float scale;
+};
+int ofx_displacement_batch_launch(const ofx_displacement_batch *a, void *stream);
+
+// frame interpolation (interp.hip; the definition: "frame interpolation" in include/ofx.h) of n <= OFX_STREAM_MAX_BATCH pairs of one
+// w x h size at n_times <= OFX_INTERP_MAX_TIMES times in ONE launch.  Pair i reads a[i] / b[i] (u8 planes, each with its own pitch
+// >= w) and dab[i] / dba[i] (w x h interleaved float32, 8-byte aligned), writes frame k at dst[i] + k * time_stride (rows dst_pitch
+// apart, bytes beyond column w - 1 untouched) and ADDS its counts to stats[i] + 4 * k (8-byte aligned; NULL = none), which the
+// launch function zeroes on the stream first.  c00 / c01 / c10 / t: the definition's host step per time.  The launch function works
+// out by itself whether whole quads go out as one dword.  Every argument is checked before anything is enqueued.
+struct ofx_interp_batch {
+    const uint8_t *a[OFX_STREAM_MAX_BATCH], *b[OFX_STREAM_MAX_BATCH];
+    const float *dab[OFX_STREAM_MAX_BATCH], *dba[OFX_STREAM_MAX_BATCH];
+    uint8_t *dst[OFX_STREAM_MAX_BATCH];
+    unsigned long long *stats[OFX_STREAM_MAX_BATCH];
+    int a_pitch[OFX_STREAM_MAX_BATCH], b_pitch[OFX_STREAM_MAX_BATCH];
+    float t[OFX_INTERP_MAX_TIMES], c00[OFX_INTERP_MAX_TIMES], c01[OFX_INTERP_MAX_TIMES], c10[OFX_INTERP_MAX_TIMES];
+    int n, w, h, n_times, dst_pitch;
+    size_t time_stride;
+};
+int ofx_interp_batch_launch(const ofx_interp_batch *a, void *stream);
+
 // the stream pipeline's colour front end (frontend.hip): the filter's tables for one (window, sigma_s, sigma_b), built once on the
 // host (window 0: grey frames only; an unsupported window is OFX_E_UNSUPPORTED), and one launch over n <= OFX_STREAM_MAX_BATCH
 // frames (modes[i]: OFX_FRONTEND_GREY / _BILATERAL / _BILATERAL_FAST; a call that mixes the two bilateral forms launches twice)

@@ -129,6 +129,13 @@ struct ofx_session {
     int mc_pitch = 0, mc_slots = 0, mc_level = 0;
     float mc_scale = 0.0f;
     long motioned = 0;
+    // ofx_session_stream_displacement (interp.hip): the caller's ring of displacement fields (nullptr: off), and the newest pair
+    // written
+    float *disp_ring = nullptr;
+    size_t disp_stride = 0; // bytes from slot to slot
+    int disp_slots = 0, disp_level = 0;
+    float disp_scale = 0.0f;
+    long displaced = 0;
     // ofx_session_stream_frontend: colour frames through the front end (frontend.hip).  fe_mode: what a frame gets
     // (OFX_FRONTEND_GREY / _BILATERAL / _BILATERAL_FAST), 0 = off; frame 0 of a stream gets OFX_FRONTEND_GREY with
     // OFX_FRONTEND_FLAG_FIRST_GREY.  borrow_frames: the filtered plane of image set i (fplane[i], at pitch[0]) stands in for the

@@ -128,6 +128,28 @@ static int motion_ring(const Tick &t, long first, long last, void *stream)
     return OFX_OK;
 }
 
+// One launch for pairs first .. last: each pair's pixel displacement at the stage's level into its ring slot
+// (ofx_session_stream_displacement).  Reads the pair's shift vector and the final flow, as motion_ring does.
+static int displacement_ring(const Tick &t, long first, long last, void *stream)
+{
+    ofx_session *s = t.s;
+    const int lv = s->disp_level;
+    static thread_local ofx_displacement_batch db;
+    memset(&db, 0, sizeof db);
+    db.w = s->w[lv], db.h = s->h[lv], db.scale = s->disp_scale;
+    for (long p = first; p <= last; ++p, ++db.n) {
+        db.flow[db.n] = s->flowset[p % t.B][lv];
+        db.uv[db.n] = lv == t.L - 1 ? nullptr : t.uvslot(p) + 2 * lv; // (the coarsest level is not shifted)
+        db.dst[db.n] = reinterpret_cast<float *>(reinterpret_cast<char *>(s->disp_ring) + (size_t)((p - 1) % s->disp_slots) * s->disp_stride);
+    }
+    {
+        OfxRange range("ofx.displacement_ring");
+        OFX_TRY(ofx_displacement_batch_launch(&db, stream));
+    }
+    s->displaced = last;
+    return OFX_OK;
+}
+
 // pyramid(frame f0 + i) for the tick's frames
 static int pyramid_stages(const Tick &t, const uint8_t *const *frames, const int *pitches, int n_frames, ofx_stream_stages &g)
 {
@@ -394,6 +416,8 @@ static int stream_tick(ofx_session *s, const uint8_t *const *frames, const int *
     if ((s->arrow_ring || s->trk_points) && newest >= 1) OFX_TRY(sample_ring(s, oldest, newest, stream));
     // the motion-compensation stage (ofx_session_stream_motion): one launch, under the same rule
     if ((s->mc_ring || s->mc_stats) && newest >= 1) OFX_TRY(motion_ring(t, oldest, newest, stream));
+    // the displacement stage (ofx_session_stream_displacement): one launch, under the same rule
+    if (s->disp_ring && newest >= 1) OFX_TRY(displacement_ring(t, oldest, newest, stream));
     s->stream_n = t.f0 + t.B;
     return OFX_OK;
 }
@@ -417,6 +441,7 @@ extern "C" int ofx_session_stream_begin(ofx_session *s)
     s->composed = 0;
     s->sampled = 0;
     s->motioned = 0;
+    s->displaced = 0;
     s->stream_input = 0;
     s->have_prev = s->have_next = s->staged = false;
     s->corner_done = false;
@@ -816,5 +841,52 @@ extern "C" int ofx_session_motion_of(ofx_session *s, int pair, uint8_t **d_ptr, 
     if (d_ptr) *d_ptr = s->mc_ring ? s->mc_ring + slot * s->mc_stride : nullptr;
     if (row_pitch) *row_pitch = s->mc_pitch;
     if (d_stats) *d_stats = s->mc_stats ? s->mc_stats + 4 * slot : nullptr;
+    return OFX_OK;
+}
+
+extern "C" int ofx_session_stream_displacement(ofx_session *s, int level, float scale, float *d_ring, size_t slot_stride_bytes, int n_slots)
+{
+    const char *who = "ofx_session_stream_displacement";
+    OFX_REQUIRE(s, "%s: null session", who);
+    if (s->stream_n > 0 || s->n_held > 0) {
+        ofx_set_error("%s: the stream has frames already; set the output before the first frame of a stream", who);
+        return OFX_E_STATE;
+    }
+    if (!d_ring) {
+        s->disp_ring = nullptr;
+        s->displaced = 0;
+        return OFX_OK;
+    }
+    if (s->p.sharded || s->p.frames_partial) {
+        ofx_set_error("%s: not on a sharded session or with partial frames", who);
+        return OFX_E_UNSUPPORTED;
+    }
+    const int B = stream_batch_of(s);
+    OFX_REQUIRE(level >= 0 && level < s->p.levels, "%s: level %d out of range (0 .. %d)", who, level, s->p.levels - 1);
+    OFX_REQUIRE(__builtin_isfinite(scale), "%s: the scale must be finite", who);
+    OFX_REQUIRE(n_slots >= B, "%s: %d slots, the ring needs at least stream_batch = %d (the pairs one call completes)", who, n_slots, B);
+    const size_t slot_bytes = (size_t)s->h[level] * (size_t)s->w[level] * 8;
+    OFX_REQUIRE(((uintptr_t)d_ring & 15) == 0, "%s: the ring must be 16-byte aligned", who);
+    OFX_REQUIRE(slot_stride_bytes % 16 == 0 && slot_stride_bytes >= slot_bytes,
+                "%s: slot stride %zu bytes must be a multiple of 16 and at least the slot's %zu bytes", who, slot_stride_bytes, slot_bytes);
+    s->disp_ring = d_ring;
+    s->disp_stride = slot_stride_bytes;
+    s->disp_slots = n_slots;
+    s->disp_level = level;
+    s->disp_scale = scale;
+    s->displaced = 0;
+    return OFX_OK;
+}
+
+extern "C" int ofx_session_displacement_of(ofx_session *s, int pair, float **d_ptr)
+{
+    OFX_REQUIRE(s, "ofx_session_displacement_of: null session");
+    if (!s->disp_ring) {
+        ofx_set_error("ofx_session_displacement_of: the stage is off (ofx_session_stream_displacement)");
+        return OFX_E_STATE;
+    }
+    OFX_REQUIRE(pair >= 1 && pair <= s->displaced && pair > s->displaced - s->disp_slots,
+                "ofx_session_displacement_of: pair %d is not among the newest %d pairs of the stage (newest: %ld)", pair, s->disp_slots, s->displaced);
+    if (d_ptr) *d_ptr = reinterpret_cast<float *>(reinterpret_cast<char *>(s->disp_ring) + (size_t)((pair - 1) % s->disp_slots) * s->disp_stride);
     return OFX_OK;
 }

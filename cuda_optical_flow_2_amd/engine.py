@@ -111,7 +111,7 @@ class Session:
         check(self.L.ofx_session_create(C.byref(p), C.byref(self._h)), "ofx_session_create")
         self._keep = []
         self._ring, self._ring_level = None, 0
-        self._arrows = self._tracks = self._motion = None
+        self._arrows = self._tracks = self._motion = self._disp = None
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -451,6 +451,35 @@ class Session:
         w, rows = self.width >> level, self.height >> level
         img = DeviceView(ptr.value, (rows, pitch.value), "|u1").tensor()[:, :w] if ptr.value else None
         return img, (DeviceView(st.value, (4,), "<i8").tensor() if st.value else None)
+
+    def stream_displacement(self, ring, level: int = 0, scale: float = None):
+        """The stream pipeline's displacement stage (ofx_session_stream_displacement; the definition: "pixel displacement" in
+        include/ofx.h): for every pair it completes, the motion IN PIXELS the pipeline applied at `level` -- floor(the level's shift)
+        + scale * the level's flow -- into slot (p - 1) mod n_slots of `ring`, by one more launch per completing call.  ring:
+        float32 CUDA tensor [n_slots, rows, width >> level, 2], rows tightly packed, 16-byte aligned, the slot stride a multiple
+        of 16 bytes; n_slots >= stream_batch.  scale: ITER_SCALE when None.  None for ring turns the stage off.  Only before the
+        first frame of a stream; stays in effect for later streams."""
+        if ring is None:
+            check(self.L.ofx_session_stream_displacement(self._h, 0, 0.0, None, 0, 0), "stream_displacement")
+            self._disp = None
+            return
+        import torch
+
+        w, rows = self.width >> level, self.height >> level
+        assert ring.is_cuda and ring.dtype == torch.float32 and ring.dim() == 4, "ring: float32 CUDA tensor [n_slots, rows, w, 2]"
+        assert tuple(ring.shape[1:]) == (rows, w, 2), f"ring slots must be [{rows}, {w}, 2], got {tuple(ring.shape[1:])}"
+        assert ring.stride()[1:] == (2 * w, 2, 1), "ring: the rows of a slot must be tightly packed"
+        check(self.L.ofx_session_stream_displacement(self._h, level, ITER_SCALE if scale is None else float(scale), ring.data_ptr(),
+                                                     4 * int(ring.stride(0)), int(ring.shape[0])), "stream_displacement")
+        self._disp = (ring, level)   # (kept alive while the pipeline may write it)
+
+    def displacement_of(self, pair: int):
+        """torch float32 view [rows, width >> level, 2] of `pair`'s slot in the displacement ring (ofx_session_displacement_of),
+        while it is one of the newest n_slots pairs; valid once the launch of the call that reported the pair has run."""
+        ptr = _vp()
+        check(self.L.ofx_session_displacement_of(self._h, pair, C.byref(ptr)), "session_displacement_of")
+        level = self._disp[1]
+        return DeviceView(ptr.value, (self.height >> level, self.width >> level, 2), "<f4").tensor()
 
     def uv(self, level: int):
         """Shift vector of `level` for the pair in progress (the slot alternates per pair: query after every swap)."""
@@ -896,3 +925,122 @@ def video_consistency(frames, levels: int, window: int, mode: str = "lk_float", 
     if both:
         out += _consistency_pairs(bp, fp, hl, wl, frames.device, ITER_SCALE, float(alpha), beta)
     return out + (fwd, bwd) if return_flows else out
+
+
+# ---- pixel displacement and frame interpolation ---------------------------------------------------------------------------------
+
+INTERP_MAX_TIMES = 8    # OFX_INTERP_MAX_TIMES
+
+
+def flow_displacement(flow: np.ndarray, uv=None, scale: float = ITER_SCALE) -> np.ndarray:
+    """ofx_flow_displacement on a host array [h, w, 2]: D of "pixel displacement" in include/ofx.h -- (floor(uv[0]) + scale * u,
+    floor(uv[1]) + scale * v), the motion in pixels the pipeline applies at a level whose shift is uv (None: none) and whose flow
+    is `flow`.  (compose_flow is the reference's display quantity, not a displacement.)"""
+    import torch
+
+    L = _lib.load()
+    h, w, _ = flow.shape
+    assert tuple(flow.shape) == (h, w, 2)
+    tf = torch.from_numpy(np.array(flow, dtype=np.float32, order="C")).cuda()
+    tuv = None if uv is None else torch.tensor([float(uv[0]), float(uv[1])], dtype=torch.float32, device="cuda")
+    td = torch.empty_like(tf)
+    check(L.ofx_flow_displacement(tf.data_ptr(), w, h, None if tuv is None else tuv.data_ptr(), float(scale), td.data_ptr(), _stream_ptr()),
+          "ofx_flow_displacement")
+    torch.cuda.synchronize()
+    return td.cpu().numpy()
+
+
+def _times(times):
+    t = np.ascontiguousarray(times, dtype=np.float32).reshape(-1)
+    assert 1 <= t.size <= INTERP_MAX_TIMES, f"times: 1 to {INTERP_MAX_TIMES} of them"
+    return t, t.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def interpolate_frames(a: np.ndarray, b: np.ndarray, disp_ab: np.ndarray, disp_ba: np.ndarray, times):
+    """ofx_interpolate_frames on host arrays: the in-between frames of the pair (a, b) at `times` (each in (0, 1), at most 8) of
+    "frame interpolation" in include/ofx.h, from the two displacement fields in pixels, disp_ab (a -> b) and disp_ba (b -> a),
+    both [h, w, 2].  Returns (frames uint8 [T, h, w], stats int64 [T, 4]): stats[k] = (w*h, pixels taken from a only, from b
+    only, with neither source inside its frame)."""
+    import torch
+
+    L = _lib.load()
+    h, w = a.shape
+    assert b.shape == (h, w) and tuple(disp_ab.shape) == (h, w, 2) and tuple(disp_ba.shape) == (h, w, 2)
+    t, tp = _times(times)
+    ta, pa = _u8_plane(np.array(a, dtype=np.uint8))    # (copies: the caller's arrays may be read-only)
+    tb, pb = _u8_plane(np.array(b, dtype=np.uint8))
+    tab = torch.from_numpy(np.array(disp_ab, dtype=np.float32, order="C")).cuda()
+    tba = torch.from_numpy(np.array(disp_ba, dtype=np.float32, order="C")).cuda()
+    td = torch.zeros((t.size, h, w), dtype=torch.uint8, device="cuda")
+    ts = torch.zeros((t.size, 4), dtype=torch.int64, device="cuda")
+    check(L.ofx_interpolate_frames(ta.data_ptr(), pa, tb.data_ptr(), pb, w, h, tab.data_ptr(), tba.data_ptr(), tp, int(t.size), td.data_ptr(), w,
+                                   h * w, ts.data_ptr(), _stream_ptr()), "ofx_interpolate_frames")
+    torch.cuda.synchronize()
+    return td.cpu().numpy(), ts.cpu().numpy()
+
+
+def video_displacement(frames, levels: int, window: int, mode: str = "lk_float", level: int = 0, iters: int = 1, min_det: float = 0.0,
+                       batch: Optional[int] = None, frontend: Optional[str] = None, bilateral=(9, 2.0, 10.0), fast: bool = False, out=None):
+    """The motion in pixels of every consecutive pair of a clip at `level`: D of "pixel displacement" in include/ofx.h -- the
+    level's global shift, floored, plus OFX_ITER_SCALE times the level's flow -- by the pipeline's displacement stage
+    (Session.stream_displacement).  This is what the pipeline applied to frame p to match frame p-1; video_flow's composed field is
+    the reference's display quantity and is no displacement.  frames and the other arguments as video_flow.  Returns float32
+    [N-1, H >> level, W >> level, 2]: out[p-1] is the displacement frame p-1 -> frame p; `out` may supply the tensor."""
+    N, H, W = _clip_shape(frames)
+    assert 0 <= level < levels
+    out = _ring_for(N, H, W, level, frames.device, out)
+    _run_clip(frames, levels, window, mode, iters, min_det, batch, frontend, bilateral, fast, lambda s: s.stream_displacement(out, level))
+    return out
+
+
+def video_interpolate(frames, levels: int, window: int, mode: str = "lk_float", factor: int = 2, iters: int = 1, min_det: float = 0.0,
+                      batch: Optional[int] = None, return_stats: bool = False, return_displacements: bool = False):
+    """Frame-rate up-conversion of a grey clip: the factor - 1 in-between frames of every consecutive pair, at the times
+    float32(k / factor), k = 1 .. factor - 1, by "frame interpolation" of include/ofx.h.  The clip goes through the stream pipeline
+    twice with a level-0 displacement ring -- once as it is, once in reverse frame order (the frames are not copied) -- and the
+    pairs then go through ofx_interpolate_frames_batch, up to 16 per launch, frames read in place and fields straight out of the
+    two rings: one launch writes all in-between frames of its pairs.
+
+    frames: uint8 CUDA tensor [N, H, W], N >= 2, unit column stride (a colour clip is refused); factor: 2 .. 9.  Returns uint8
+    [N-1, factor-1, H, W]: out[p, k-1] lies between frame p and frame p+1 at time k / factor.  return_stats=True appends int64
+    [N-1, factor-1, 4]: (pixels, pixels taken from frame p only, from frame p+1 only, with neither source inside its frame).
+    return_displacements=True appends the two rings, float32 [N-1, H, W, 2]: fwd[p] is the displacement frame p -> p+1, and bwd,
+    in the REVERSED run's order, holds frame p+1 -> p in bwd[N-2-p].
+
+    Memory: the two rings take 2 * (N-1) * H * W * 8 bytes whether they are returned or not."""
+    import torch
+
+    assert frames.dim() == 3, "video_interpolate: grey clips only, uint8 [N, H, W] (colour output is not implemented: convert the clip to grey first)"
+    N, H, W = _clip_shape(frames)
+    assert isinstance(factor, int) and 2 <= factor <= INTERP_MAX_TIMES + 1, f"factor: an integer 2 .. {INTERP_MAX_TIMES + 1}, not {factor!r}"
+    assert frames.stride(2) == 1, "frames: unit column stride"
+    if frames.stride(1) < W or frames.stride(0) < 0:
+        frames = frames.contiguous()
+    T = factor - 1
+    t, tp = _times([np.float32(k / factor) for k in range(1, factor)])
+    rings = []
+    for order in (None, range(N - 1, -1, -1)):
+        ring = _ring_for(N, H, W, 0, frames.device, None)
+        _run_clip(frames, levels, window, mode, iters, min_det, batch, None, None, False,
+                  lambda s, ring=ring: s.stream_displacement(ring, 0), order=order)
+        rings.append(ring)
+    fwd, bwd = rings
+    L = _lib.load()
+    out = torch.empty((N - 1, T, H, W), dtype=torch.uint8, device=frames.device)
+    stats = torch.empty((N - 1, T, 4), dtype=torch.int64, device=frames.device) if return_stats else None
+    pitch = int(frames.stride(1))
+    ap = [frames.data_ptr() + p * int(frames.stride(0)) for p in range(N)]
+    fp, bp = _slot_ptrs(fwd), _slot_ptrs(bwd)[::-1]    # the backward field of forward pair p is slot N-2-p of the reversed run's ring
+    op, sp = _slot_ptrs(out), _slot_ptrs(stats) if return_stats else []
+    for p0 in range(0, N - 1, 16):
+        n = min(16, N - 1 - p0)
+        ptrs = [(_vp * n)(*v[p0:p0 + n]) for v in (ap, ap[1:], fp, bp, op, sp)]
+        pitches = (C.c_int * n)(*([pitch] * n))
+        check(L.ofx_interpolate_frames_batch(ptrs[0], pitches, ptrs[1], pitches, n, W, H, ptrs[2], ptrs[3], tp, T, ptrs[4], W, H * W,
+                                             ptrs[5] if return_stats else None, _stream_ptr()), "ofx_interpolate_frames_batch")
+    res = (out,)
+    if return_stats:
+        res += (stats,)
+    if return_displacements:
+        res += (fwd, bwd)
+    return res[0] if len(res) == 1 else res

@@ -374,6 +374,68 @@ int ofx_flow_consistency_batch(const float *const *d_fwd, const float *const *d_
                                float alpha, float beta, uint8_t *const *d_mask, int mask_pitch, float *const *d_err,
                                int64_t *const *d_stats, void *stream);
 
+/* ---- pixel displacement ------------------------------------------------------
+ * ofx_compose_flow above is the reference's DISPLAY quantity (main.cu:138-147: sum_k 2^k flow_k in raw Sobel / Dt units); it is
+ * not what the pipeline applies to the next image, and scaled by OFX_ITER_SCALE it is not a displacement either.  What the
+ * pipeline applies at a level is the level's global shift uv (integer steps, per pair) and then the level's own flow times
+ * OFX_ITER_SCALE.  That sum, in pixels, is the "pixel displacement".  THE definition (everything else quotes it), for one level
+ * of w x h pixels:
+ *   inputs  flow: interleaved (u, v) float32, w x h, tightly packed; uv: two floats on the device, the level's shift (NULL =
+ *           none, as at the coarsest level); scale.
+ *   D(y,x) = (floorf(uv[0]) + scale*u, floorf(uv[1]) + scale*v): the product rounded, then the sum.  With uv == NULL the first
+ *           term is 0.0f and the add is still performed.  Every float32 operation is rounded once, nothing is fused, denormals
+ *           are kept.  Nothing is tested or clamped: a NaN or Inf in uv or flow goes through.
+ * Why floor: ofx_shift_1ch reads next((int)(x + u)) at integer x; away from the borders that is a translation by floor(u), and
+ * a translation commutes with the bilinear warp that follows.  So away from the image borders the motion-compensated image is
+ * mc(x) = bilinear(next, x + D(x)).
+ *
+ * ofx_flow_displacement: one level, stateless, one launch.  d_flow and d_dst 8-byte aligned, w*h < 2^28, scale finite;
+ * otherwise OFX_E_INVALID, before anything is enqueued. */
+int ofx_flow_displacement(const float *d_flow, int w, int h, const float *d_uv /* NULL = none */, float scale,
+                          float *d_dst, void *stream);
+
+/* ---- frame interpolation -----------------------------------------------------
+ * In-between frames of a pair from its two displacement fields.  THE definition (everything else quotes it), for one pair of
+ * u8 planes a and b of w x h pixels, each with its own row pitch:
+ *   inputs  Dab (a -> b) and Dba (b -> a): displacement fields IN PIXELS, both on the pixel grid, interleaved float32, w x h,
+ *           tightly packed; a time t, float32, finite, 0 < t < 1.
+ *   host    in float32: omt = 1.0f - t; c00 = -(omt*t); c01 = t*t; c10 = omt*omt.  (The usual gather approximation of the
+ *           intermediate flows, F(t->a) = -(1-t)t Dab + t^2 Dba and F(t->b) = (1-t)^2 Dab - t(1-t) Dba: exact for a translation.)
+ * Every float32 operation is rounded once, nothing is fused, denormals are kept.  For pixel (x, y):
+ *   1. Ta = c00*Dab(y,x) + c01*Dba(y,x) and Tb = c10*Dab(y,x) + c00*Dba(y,x), per component: both products rounded, then the sum.
+ *   2. pa = ((float)x + Ta.x, (float)y + Ta.y), one add each; pb the same from Tb.
+ *   3. a side is FINITE when |p.x| <= 1e9 && |p.y| <= 1e9 (a NaN fails), and USABLE when it is finite and
+ *      0 <= p.x <= (float)(w-1) && 0 <= p.y <= (float)(h-1).
+ *   4. its sampling position (sx, sy): finite -- p with each coordinate clamped to [0, w-1] / [0, h-1] (replicate border); not
+ *      finite -- ((float)x, (float)y).
+ *   5. x0 = (int)sx, y0 = (int)sy, fx = sx - (float)x0, fy = sy - (float)y0, x1 = min(x0+1, w-1), y1 = min(y0+1, h-1), and
+ *      ofx_warp_levels' blend on floats: r0 = p00 + fx*(p01 - p00); r1 = p10 + fx*(p11 - p10); V = r0 + fy*(r1 - r0).  V is NOT
+ *      rounded here.  This gives A from plane a and B from plane b.
+ *   6. class 0: both sides usable; 1: only a; 2: only b; 3: neither.  v = A + t*(B - A) for classes 0 and 3, A for class 1, B
+ *      for class 2; out = (uint8_t)(int)(v + 0.5f).
+ *   7. stats = four int64 per (pair, time):  [0] w*h   [1] pixels of class 1   [2] of class 2   [3] of class 3.  Integers: they
+ *      depend on no order, tile or batch.
+ * The rule is geometric on purpose: a pixel whose source in one frame lies outside that frame is taken from the other frame,
+ * which is what happens at the borders of a pan.  No tap reads outside the (h-1)*pitch + w bytes of a plane or the w*h*8 bytes
+ * of a field, whatever the fields hold.
+ *
+ * ofx_interpolate_frames: n_times in-between frames of one pair in ONE launch; frame k at d_dst + k*time_stride_bytes (rows
+ * dst_pitch apart, bytes beyond column w-1 untouched), its stats at d_stats + 4*k (d_stats may be NULL).
+ * ofx_interpolate_frames_batch: the same for 1 <= n <= OFX_STREAM_MAX_BATCH pairs of one size and one set of times, ONE launch.
+ * Null inputs, w, h <= 0 or w*h >= 2^28, a pitch below w, fields or stats not 8-byte aligned, n_times outside
+ * 1 .. OFX_INTERP_MAX_TIMES, a time that is not finite or not in (0, 1), time_stride_bytes < h*dst_pitch when n_times > 1, a
+ * NULL entry in a non-NULL array, n outside 1 .. OFX_STREAM_MAX_BATCH: OFX_E_INVALID, before anything is enqueued.  The host
+ * arrays are read before the call returns. */
+#define OFX_INTERP_MAX_TIMES 8
+int ofx_interpolate_frames(const uint8_t *d_a, int a_pitch, const uint8_t *d_b, int b_pitch, int w, int h,
+                           const float *d_disp_ab, const float *d_disp_ba, const float *h_times, int n_times,
+                           uint8_t *d_dst, int dst_pitch, size_t time_stride_bytes, int64_t *d_stats /* may be NULL */, void *stream);
+int ofx_interpolate_frames_batch(const uint8_t *const *d_a, const int *a_pitches, const uint8_t *const *d_b,
+                                 const int *b_pitches, int n, int w, int h, const float *const *d_disp_ab,
+                                 const float *const *d_disp_ba, const float *h_times, int n_times,
+                                 uint8_t *const *d_dst, int dst_pitch, size_t time_stride_bytes,
+                                 int64_t *const *d_stats /* may be NULL */, void *stream);
+
 /* ---- layout helpers ------------------------------------------------------ */
 int ofx_extract_ch0(const uint8_t *d_src3, uint8_t *d_dst1, int w, int h, int dst_pitch, void *stream);
 int ofx_replicate_3ch(const uint8_t *d_src1, int src_pitch, uint8_t *d_dst3, int w, int h, void *stream);
@@ -677,6 +739,24 @@ int ofx_session_stream_motion(ofx_session *s, int level, float scale, uint8_t *d
  * row pitch, and its four sums (NULL without a stats ring).  OFX_E_STATE without the stage, OFX_E_INVALID for a pair not (or no
  * longer) in the ring. */
 int ofx_session_motion_of(ofx_session *s, int pair, uint8_t **d_ptr, int *row_pitch, int64_t **d_stats);
+/* The stream pipeline's displacement stage: D of "pixel displacement" above, at `level` with `scale` (OFX_ITER_SCALE for the
+ * session's own flows), for every pair the pipeline completes.  Pair p's field (rows x w x 2 floats, tightly packed) goes to slot
+ * (p - 1) mod n_slots at d_ring + slot * slot_stride_bytes.  Every call that completes pairs enqueues ONE more kernel launch
+ * on its `stream` for all those pairs, after the motion stage's (no timing kind records it).
+ *   d_ring 16-byte aligned, slot_stride_bytes a multiple of 16 and at least rows * w * 8, n_slots >= stream_batch,
+ *   0 <= level < levels; otherwise OFX_E_INVALID.  d_ring == NULL turns the stage off (the default: nothing is launched or
+ *   allocated).
+ * Only before the first frame of a stream (OFX_E_STATE once a stream has frames); stays in effect for later streams, whose
+ * pairs count from 1 again.  Sharded sessions and frames_partial: OFX_E_UNSUPPORTED.
+ * Sources: the pair's shift vector of that level (none at the coarsest) and the flow ofx_session_flow_of points to.  As written
+ * at ofx_session_stream_motion: "All of them are intact in the call that completes the pair: that call's own LK stage reads both
+ * image sets and the pair's shift-vector slot, a set is rewritten 3B + 2 (two stages: 2B + 2) frames later and a slot by the
+ * corner stage of a later tick, and the last launch of a tick always leaves the final flow in the set flow_of reports."  The
+ * stage reads no frame: the lifetime of borrowed frames is unchanged.  Lifetime of a slot: as the compose ring's. */
+int ofx_session_stream_displacement(ofx_session *s, int level, float scale, float *d_ring, size_t slot_stride_bytes, int n_slots);
+/* Slot of `pair` while it is one of the newest n_slots pairs of the displacement stage.  OFX_E_STATE without the stage,
+ * OFX_E_INVALID for a pair not (or no longer) in the ring. */
+int ofx_session_displacement_of(ofx_session *s, int pair, float **d_ptr);
 /* Colour frames into the stream pipeline (main.cu:222-272 as one device-resident pipeline): with the front end set, every call
  * that launches a tick first enqueues ONE launch of the front end (ofx_frontend_1ch) for that tick's colour frames on its `stream`,
  * writing the filtered one-channel planes the tick then reads as its frames:

@@ -1,0 +1,162 @@
+"""CPU: the displacement and interpolation calls (ofx_flow_displacement, ofx_session_stream_displacement,
+ofx_session_displacement_of, ofx_interpolate_frames, ofx_interpolate_frames_batch) are declared in include/ofx.h, exported by the
+library and bound in lib.py; bad sizes, pitches, alignments, times, strides and batch arrays are refused with OFX_E_INVALID before
+anything is enqueued; the ABI version and the timing kinds did not move.  No compute calls."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CALLS = ["ofx_flow_displacement", "ofx_session_stream_displacement", "ofx_session_displacement_of", "ofx_interpolate_frames",
+         "ofx_interpolate_frames_batch"]
+OFX_E_INVALID = 1
+NAN, INF = float("nan"), float("inf")
+
+
+def test_declared_exported_and_bound():
+    from cuda_optical_flow_2_amd import build, lib
+
+    build.build()
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ofx.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\b(ofx_[a-z0-9_]+)\s*\(", text))
+    nm = subprocess.run(["nm", "-D", "--defined-only", lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {line.split()[-1] for line in nm.splitlines() if line.strip()}
+    L = lib.load()
+    for name in CALLS:
+        assert name in declared, f"{name} is not declared in include/ofx.h"
+        assert name in exported, f"{name} is not exported by the library"
+        assert name in lib.EXPORTS and name in lib._SIGS, f"{name} is not in lib.EXPORTS / lib._SIGS"
+        assert getattr(L, name).argtypes == lib._SIGS[name]
+    # the bound argument lists are the header's: as many arguments, floats, ints and sizes where it has them
+    for name in CALLS:
+        args = re.search(name + r"\s*\(([^;]*)\)\s*;", text).group(1).split(",")
+        assert len(args) == len(lib._SIGS[name]), name
+        for decl, bound in zip(args, lib._SIGS[name]):
+            assert (bound is C.c_float) == bool(re.match(r"float\s+\w", decl.strip())), (name, decl)
+            assert (bound is C.c_int) == bool(re.match(r"int\s+\w", decl.strip())), (name, decl)
+            assert (bound is C.c_size_t) == bool(re.match(r"size_t\s+\w", decl.strip())), (name, decl)
+
+
+def test_python_surface_and_the_constant():
+    from cuda_optical_flow_2_amd import engine
+
+    for name in ("flow_displacement", "interpolate_frames", "video_displacement", "video_interpolate"):
+        assert callable(getattr(engine, name))
+    assert callable(engine.Session.stream_displacement) and callable(engine.Session.displacement_of)
+    text = open(os.path.join(ROOT, "include", "ofx.h")).read()
+    assert int(re.search(r"#define\s+OFX_INTERP_MAX_TIMES\s+(\d+)\b", text).group(1)) == 8 == engine.INTERP_MAX_TIMES
+
+
+def _times(*values):
+    return (C.c_float * len(values))(*values)
+
+
+def test_the_displacement_call_refuses_bad_arguments_before_it_enqueues_anything():
+    """The addresses are never dereferenced: every case below fails a check on the host."""
+    from cuda_optical_flow_2_amd import lib
+
+    L = lib.load()
+    F, U, D = 0x10000, 0x20000, 0x30000    # made-up, suitably aligned addresses
+
+    def call(flow=F, w=64, h=8, uv=U, scale=0.5, dst=D):
+        return L.ofx_flow_displacement(flow, w, h, uv, scale, dst, None)
+
+    for kw, word in ((dict(flow=None), b"d_flow"), (dict(dst=None), b"d_dst")):
+        assert call(**kw) == OFX_E_INVALID, kw
+        assert word in L.ofx_last_error(), kw
+    assert call(w=0) == OFX_E_INVALID and call(h=0) == OFX_E_INVALID and call(w=-4) == OFX_E_INVALID and call(h=-1) == OFX_E_INVALID
+    assert call(w=1 << 14, h=1 << 14) == OFX_E_INVALID and call(w=1 << 16, h=1 << 16) == OFX_E_INVALID     # 2^28 pixels and beyond
+    assert b"w * h" in L.ofx_last_error()
+    for kw in (dict(flow=F + 4), dict(dst=D + 4)):
+        assert call(**kw) == OFX_E_INVALID, kw
+        assert b"aligned" in L.ofx_last_error(), kw
+    for bad in (NAN, INF, -INF):
+        assert call(scale=bad) == OFX_E_INVALID, bad
+        assert b"scale" in L.ofx_last_error()
+
+
+def test_the_interpolation_call_refuses_bad_arguments_before_it_enqueues_anything():
+    from cuda_optical_flow_2_amd import lib
+
+    L = lib.load()
+    A, B, AB, BA, D, S = 0x10000, 0x20000, 0x30000, 0x40000, 0x50000, 0x60000
+    w, h = 64, 8
+    T3 = _times(0.25, 0.5, 0.75)
+
+    def call(a=A, ap=64, b=B, bp=72, w=w, h=h, ab=AB, ba=BA, times=T3, nt=3, dst=D, dp=64, ts=64 * 8, stats=S):
+        return L.ofx_interpolate_frames(a, ap, b, bp, w, h, ab, ba, times, nt, dst, dp, ts, stats, None)
+
+    for kw, word in ((dict(a=None), b"d_a"), (dict(b=None), b"d_b"), (dict(ab=None), b"d_disp_ab"), (dict(ba=None), b"d_disp_ba"),
+                     (dict(dst=None), b"d_dst"), (dict(times=None), b"h_times")):
+        assert call(**kw) == OFX_E_INVALID, kw
+        assert word in L.ofx_last_error(), kw
+    assert call(w=0) == OFX_E_INVALID and call(h=0) == OFX_E_INVALID and call(w=-4) == OFX_E_INVALID and call(h=-1) == OFX_E_INVALID
+    big = dict(ap=1 << 14, bp=1 << 14, dp=1 << 14, ts=1 << 28)
+    assert call(w=1 << 14, h=1 << 14, **big) == OFX_E_INVALID                 # 2^28 pixels
+    assert b"w * h" in L.ofx_last_error()
+    for kw in (dict(ap=63), dict(bp=63), dict(dp=63)):                          # a pitch below the width
+        assert call(**kw) == OFX_E_INVALID, kw
+        assert b"pitch" in L.ofx_last_error(), kw
+    for kw in (dict(ab=AB + 4), dict(ba=BA + 4), dict(stats=S + 4)):
+        assert call(**kw) == OFX_E_INVALID, kw
+        assert b"aligned" in L.ofx_last_error(), kw
+    for nt in (0, 9, -1):
+        assert call(times=_times(*[0.5] * 9), nt=nt) == OFX_E_INVALID, nt
+        assert b"n_times" in L.ofx_last_error()
+    for bad in (NAN, INF, -INF, 0.0, 1.0, -0.25, 1.5):
+        assert call(times=_times(0.25, bad, 0.75)) == OFX_E_INVALID, bad
+        assert b"h_times" in L.ofx_last_error()
+    assert call(ts=64 * 8 - 1) == OFX_E_INVALID                                # frames would overlap
+    assert b"time_stride_bytes" in L.ofx_last_error()
+    assert call(dp=80, ts=64 * 8) == OFX_E_INVALID
+
+
+def test_the_batch_call_refuses_bad_arguments_before_it_enqueues_anything():
+    from cuda_optical_flow_2_amd import lib
+
+    L = lib.load()
+    vp = C.c_void_p
+
+    def arr(base, n=17, hole=None, step=0x100000):
+        return (vp * n)(*[None if i == hole else base + i * step for i in range(n)])
+
+    def ints(v, n=17):
+        return (C.c_int * n)(*[v] * n)
+
+    A, B, AB, BA, D, S = arr(0x10000000), arr(0x20000000), arr(0x30000000), arr(0x40000000), arr(0x50000000), arr(0x60000000)
+    w, h = 64, 8
+    T3 = _times(0.25, 0.5, 0.75)
+
+    def call(a=A, ap=ints(64), b=B, bp=ints(72), n=3, w=w, h=h, ab=AB, ba=BA, times=T3, nt=3, dst=D, dp=64, ts=64 * 8, stats=S):
+        return L.ofx_interpolate_frames_batch(a, ap, b, bp, n, w, h, ab, ba, times, nt, dst, dp, ts, stats, None)
+
+    assert call(n=0) == OFX_E_INVALID and call(n=17) == OFX_E_INVALID and call(n=-1) == OFX_E_INVALID
+    for kw in ("a", "ap", "b", "bp", "ab", "ba", "dst", "times"):             # a null array
+        assert call(**{kw: None}) == OFX_E_INVALID, kw
+    for kw in ("a", "b", "ab", "ba", "dst", "stats"):                           # a NULL entry in a non-NULL array
+        assert call(**{kw: arr(0x70000000, hole=2)}) == OFX_E_INVALID, kw
+    bad_pitch = ints(64)
+    bad_pitch[1] = 63
+    assert call(ap=bad_pitch) == OFX_E_INVALID and call(bp=bad_pitch) == OFX_E_INVALID and call(dp=63) == OFX_E_INVALID
+    assert b"pitch" in L.ofx_last_error()
+    for kw in ("ab", "ba", "stats"):                                            # one misaligned entry, not the first
+        a = arr(0x70000000)
+        a[1] = 0x70000000 + 0x100000 + 4
+        assert call(**{kw: a}) == OFX_E_INVALID, kw
+        assert b"aligned" in L.ofx_last_error(), kw
+    assert call(w=1 << 14, h=1 << 14, ap=ints(1 << 14), bp=ints(1 << 14), dp=1 << 14, ts=1 << 28) == OFX_E_INVALID
+    assert call(nt=0) == OFX_E_INVALID and call(times=_times(*[0.5] * 9), nt=9) == OFX_E_INVALID
+    assert call(times=_times(0.25, NAN, 0.75)) == OFX_E_INVALID and call(times=_times(0.0, 0.5, 0.75)) == OFX_E_INVALID
+    assert call(times=_times(0.25, 0.5, 1.0)) == OFX_E_INVALID
+    assert call(ts=64 * 8 - 8) == OFX_E_INVALID
+    assert b"time_stride_bytes" in L.ofx_last_error()
+
+
+def test_abi_version_and_timing_kinds_did_not_move():
+    from cuda_optical_flow_2_amd import engine, lib
+
+    assert lib.load().ofx_abi_version() == 10
+    text = open(os.path.join(ROOT, "include", "ofx.h")).read()
+    assert re.search(r"#define\s+OFX_TIME_KINDS\s+9\b", text)
+    assert len(engine.Session.TIME_KINDS) == 9
