@@ -3,11 +3,8 @@
 // the frame, undefined -- the squared round-trip error e, and the pair's three counts.  Every float32 operation below is the
 // definition's, in its order; the build compiles with -ffp-contract=off, so nothing is fused.
 //
-// A thread owns four adjacent pixels of a row (a quad) and takes kQuads quads, one after the other, as motion_ring.hip does: a
-// quad's fwd comes as two 16-byte loads, the NEXT quad's fwd goes out before this quad's taps so that its latency runs under
-// them, and all tap loads of a quad are issued before the first is used.  Every load goes through a buffer resource of exactly
-// the field's w * h * 8 bytes.  A pixel of class 2 or 3 -- and a pixel past the row's ragged end -- gets tap offsets beyond
-// the resource: the unit returns zeros nobody looks at, and no coordinate, however wild, reads outside a field.
+// The march is quad_stage.h's, over fwd; the taps come from bwd.  A pixel of class 2 or 3 -- and a pixel past the row's ragged
+// end -- gets tap offsets beyond the resource: the unit returns zeros nobody looks at.
 //
 // The two taps of a tap row are the 16 adjacent bytes at 8 * (y * w + x0), 8-byte aligned only: one 16-byte load -- EXCEPT in
 // the last column.  At x0 == w - 1 the definition's right tap is the pixel itself (x1 == x0); the 8 bytes behind it belong to
@@ -18,34 +15,16 @@
 //
 // The classes of a quad leave as one dword where the mask and its pitch are 4-byte aligned and the quad is whole, else as
 // bytes; e as four floats where err is 16-byte aligned and w a multiple of 4, else one by one.  The counts: per-thread
-// counters, a wave reduction by __shfl_xor, the block's four waves through LDS, then one 64-bit atomicAdd per non-zero count
-// per block; block 0 adds w * h.  ofx_consistency_batch_launch zeroes the four words of every slot on the stream first.
+// counters, then the block reduction described in quad_stage.h into the pair's slot.
 #include <string.h>
 
-#include "ofx_internal.h"
+#include "quad_stage.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kQuads = 4;                      // quads (four pixels) per thread, kThreads apart in row-major order
-constexpr uint32_t kNowhere = 0x80000000u;     // a buffer offset beyond every field (fields are < 2^31 bytes): loads 0
+using namespace quad;
+
 constexpr uint32_t kInfBits = 0x7f800000u;
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t field_rsrc(const void *base, int bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, bytes, 0x00027000);
-}
-
-// the definition's step 5 for one component
-__device__ __forceinline__ float blend(float b00, float b01, float b10, float b11, float fx, float fy)
-{
-    const float a = b00 + fx * (b01 - b00);
-    const float c = b10 + fx * (b11 - b10);
-    return a + fy * (c - a);
-}
 
 __global__ __launch_bounds__(kThreads) void consistency_kernel(const ofx_consistency_batch A, const int mask_dwords, const int err_quads)
 {
@@ -53,39 +32,24 @@ __global__ __launch_bounds__(kThreads) void consistency_kernel(const ofx_consist
     const int b = blockIdx.y;
     const int w = A.w, h = A.h, wmax = w - 1, hmax = h - 1;
     const int bytes = w * h * 8;
-    const __amdgpu_buffer_rsrc_t rs_fwd = field_rsrc(A.fwd[b], bytes), rs_bwd = field_rsrc(A.bwd[b], bytes);
+    const __amdgpu_buffer_rsrc_t rs_fwd = rsrc(A.fwd[b], bytes), rs_bwd = rsrc(A.bwd[b], bytes);
     uint8_t *mask = A.mask[b];
     float *err = A.err[b];
     unsigned long long *stats = A.stats[b];
     const float wmaxf = (float)wmax, hmaxf = (float)hmax, scale = A.scale, alpha = A.alpha, beta = A.beta;
-    const uint32_t qrow = (uint32_t)(w + 3) >> 2, n_quads = qrow * (uint32_t)h;
-
-    // a quad's place, and its fwd by two 16-byte loads: no branch for the row's ragged end (its last pixels get the next row's
-    // vectors, or zeros past the field: they take no taps and are never looked at) nor for a quad past the end
-    auto place = [&](int g, int &y, int &x0) -> bool {
-        const uint32_t q = (blockIdx.x * kQuads + g) * kThreads + threadIdx.x;
-        y = (int)(q / qrow), x0 = 4 * (int)(q - (uint32_t)y * qrow);
-        return q < n_quads;
-    };
-    auto load_fwd = [&](bool in, int y, int x0, float (&f)[8]) {
-        const uint32_t o = in ? 8u * ((uint32_t)y * (uint32_t)w + (uint32_t)x0) : kNowhere;
-        const f32x4 a = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_fwd, o, 0, 0));
-        const f32x4 c = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_fwd, o, 16, 0));
-#pragma unroll
-        for (int k = 0; k < 4; ++k) f[k] = a[k], f[4 + k] = c[k];
-    };
+    const uint32_t qrow = quads_per_row(w), n_quads = qrow * (uint32_t)h;
 
     uint32_t n1 = 0, n2 = 0, n3 = 0;
     int y, x0, y_next, x0_next;
     float f[8], f_next[8];
-    bool have = place(0, y, x0), have_next = false;
-    load_fwd(have, y, x0, f);
+    bool have = place(qrow, n_quads, 0, y, x0), have_next = false;
+    load_field(rs_fwd, w, have, y, x0, f);
 #pragma unroll
     for (int g = 0; g < kQuads; ++g) {
         if (!have) break;
         // the next quad's fwd goes out before this quad's taps: its latency runs under them
-        have_next = g + 1 < kQuads && place(g + 1, y_next, x0_next);
-        load_fwd(have_next, y_next, x0_next, f_next);
+        have_next = g + 1 < kQuads && place(qrow, n_quads, g + 1, y_next, x0_next);
+        load_field(rs_fwd, w, have_next, y_next, x0_next, f_next);
         const int npx = w - x0 < 4 ? w - x0 : 4;
         const float yf = (float)y;
         // steps 1 to 4
@@ -130,7 +94,7 @@ __global__ __launch_bounds__(kThreads) void consistency_kernel(const ofx_consist
                 tb[k][0] = l1[k][0], tb[k][1] = l1[k][1], tb[k][2] = r1[k][0], tb[k][3] = r1[k][1];
             }
         }
-        // the taps have arrived: steps 5 to 7
+        // the taps have arrived: steps 5 (the blend, per component) to 7
         uint32_t out = 0;
         float e4[4];
 #pragma unroll
@@ -148,16 +112,7 @@ __global__ __launch_bounds__(kThreads) void consistency_kernel(const ofx_consist
             out |= c << (8 * k);
             if (k < npx) n1 += c == OFX_FB_INCONSISTENT, n2 += c == OFX_FB_LEAVES, n3 += c == OFX_FB_UNDEFINED;
         }
-        if (mask) {
-            uint8_t *d = mask + (size_t)y * (size_t)A.mask_pitch + (size_t)x0;
-            if (npx == 4 && mask_dwords) {
-                *reinterpret_cast<uint32_t *>(d) = out;
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (k < npx) d[k] = (uint8_t)(out >> (8 * k));
-            }
-        }
+        if (mask) store_quad_u8(mask + (size_t)y * (size_t)A.mask_pitch + (size_t)x0, out, npx, mask_dwords);
         if (err) {
             float *d = err + (size_t)y * (size_t)w + (size_t)x0;
             if (err_quads) { // (w is a multiple of 4: every quad is whole)
@@ -175,6 +130,7 @@ __global__ __launch_bounds__(kThreads) void consistency_kernel(const ofx_consist
         for (int k = 0; k < 8; ++k) f[k] = f_next[k];
     }
     if (!stats) return; // (block-uniform)
+    // the block reduction (the rule: quad_stage.h), written out: behind a function the kernel's other instructions come out in another order
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         n1 += __shfl_xor(n1, o);
@@ -198,37 +154,21 @@ __global__ __launch_bounds__(kThreads) void consistency_kernel(const ofx_consist
 int ofx_consistency_batch_launch(const ofx_consistency_batch *a, void *stream)
 {
     const char *who = "ofx_consistency_batch_launch";
-    OFX_REQUIRE(a && a->n >= 1 && a->n <= OFX_STREAM_MAX_BATCH && a->w > 0 && a->h > 0, "%s: bad arguments", who);
-    // (the fields are read through buffer resources: 8 bytes per pixel, below 2^31 bytes)
-    OFX_REQUIRE((size_t)a->w * (size_t)a->h < ((size_t)1 << 28), "%s: %d x %d is more than this build checks (2^28 pixels)", who, a->w, a->h);
+    OFX_REQUIRE(a, "%s: bad arguments", who);
+    OFX_TRY(check_batch(who, a->n, a->w, a->h, {}, {a->fwd, a->bwd}, a->stats));
     OFX_REQUIRE(__builtin_isfinite(a->scale), "%s: the scale must be finite", who);
     OFX_REQUIRE(__builtin_isfinite(a->alpha) && a->alpha >= 0.0f && __builtin_isfinite(a->beta) && a->beta >= 0.0f,
                 "%s: alpha and beta must be finite and >= 0", who);
     bool mask_dwords = (a->mask_pitch & 3) == 0, err_quads = (a->w & 3) == 0;
     for (int i = 0; i < a->n; ++i) {
-        OFX_REQUIRE(a->fwd[i] && a->bwd[i], "%s: pair %d: null field", who, i);
         OFX_REQUIRE(a->mask[i] || a->err[i] || a->stats[i], "%s: pair %d has no output", who, i);
-        OFX_REQUIRE((((uintptr_t)a->fwd[i] | (uintptr_t)a->bwd[i]) & 7) == 0, "%s: pair %d: the fields must be 8-byte aligned", who, i);
         OFX_REQUIRE(((uintptr_t)a->err[i] & 3) == 0, "%s: pair %d: err must be 4-byte aligned", who, i);
-        OFX_REQUIRE(((uintptr_t)a->stats[i] & 7) == 0, "%s: pair %d: the stats must be 8-byte aligned", who, i);
         OFX_REQUIRE(!a->mask[i] || a->mask_pitch >= a->w, "%s: the mask's row pitch %d is below the width %d", who, a->mask_pitch, a->w);
         mask_dwords = mask_dwords && ((uintptr_t)a->mask[i] & 3) == 0;
         err_quads = err_quads && ((uintptr_t)a->err[i] & 15) == 0;
     }
-    // everything is checked: zero the stats slots, one memset per run of consecutive slots
-    for (int i = 0; i < a->n;) {
-        int e = i + 1;
-        if (!a->stats[i]) {
-            i = e;
-            continue;
-        }
-        while (e < a->n && a->stats[e] == a->stats[i] + 4 * (e - i)) ++e;
-        OFX_HIP(hipMemsetAsync(a->stats[i], 0, (size_t)(e - i) * 4 * sizeof(unsigned long long), ofx_stream(stream)));
-        i = e;
-    }
-    const unsigned quads = (unsigned)((a->w + 3) >> 2) * (unsigned)a->h, per_block = kThreads * kQuads;
-    dim3 grid((quads + per_block - 1) / per_block, a->n);
-    hipLaunchKernelGGL(consistency_kernel, grid, dim3(kThreads), 0, ofx_stream(stream), *a, (int)mask_dwords, (int)err_quads);
+    OFX_TRY(zero_stats(a->stats, a->n, 4, stream)); // (everything is checked)
+    hipLaunchKernelGGL(consistency_kernel, grid(a->w, a->h, a->n), dim3(kThreads), 0, ofx_stream(stream), *a, (int)mask_dwords, (int)err_quads);
     OFX_HIP(hipGetLastError());
     return OFX_OK;
 }

@@ -7,14 +7,11 @@
 // 16-byte aligned a thread moves two pixels per 16-byte load and store, and an odd last pixel goes by 8 bytes; otherwise every
 // pixel goes by 8 bytes (the fields are 8-byte aligned by contract).
 //
-// Interpolation: a thread owns four adjacent pixels of a row (a quad) and takes kQuads quads, one after the other, as
-// consistency.hip and motion_ring.hip do.  A quad's Dab and Dba arrive as four 16-byte buffer loads ONCE -- the NEXT quad's go
-// out before this quad's taps -- and the thread then loops over the launch's times with the fields in registers: per pair the
-// launch reads 16 B/px of fields whatever the number of frames it writes, and the tap bytes come from two planes that stay
-// cache-resident across the passes.  Every load goes through a buffer resource of exactly the plane's (h - 1) * pitch + w bytes
-// or the field's w * h * 8 bytes; a pixel past the row's ragged end gets offsets beyond the resource and loads zeros nobody looks
-// at, and the sampling position is clamped (or the pixel's own) before it becomes an offset, so no field value, however wild,
-// reads outside a plane.
+// Interpolation: the march is quad_stage.h's, over two fields.  A quad's Dab and Dba arrive as four 16-byte buffer loads ONCE and
+// the thread then loops over the launch's times with the fields in registers: per pair the launch reads 16 B/px of fields whatever
+// the number of frames it writes, and the tap bytes come from two planes that stay cache-resident across the passes.  A pixel past
+// the row's ragged end gets offsets beyond the resource and loads zeros nobody looks at, and the sampling position is clamped (or
+// the pixel's own) before it becomes an offset, so no field value, however wild, reads outside a plane.
 //
 // The two taps of a tap row are the 2 adjacent bytes at y * pitch + x0: one 16-bit load -- EXCEPT in the last column, where the
 // definition's right tap is the pixel itself (x1 == x0) and the byte behind it belongs to the row's padding, the next row, or
@@ -25,27 +22,17 @@
 //
 // A quad of a frame leaves as one dword where the quad is whole and every destination, dst_pitch and the time stride are 4-byte
 // aligned, else as bytes.  The counts: a thread keeps one packed counter per time (8 bits per class: at most 16 pixels a thread)
-// in its own LDS word, touched only for a quad that has a pixel of class 1, 2 or 3; at the end each time's counters go through a
-// wave reduction by __shfl_xor, the block's four waves through LDS, then one 64-bit atomicAdd per non-zero count per block;
-// block 0 adds w * h.  ofx_interp_batch_launch zeroes the words of every slot on the stream first.
+// in its own LDS word, touched only for a quad that has a pixel of class 1, 2 or 3; at the end each time's counters go through
+// the block reduction described in quad_stage.h into the time's slot, all times under one barrier.
 #include <string.h>
 
-#include "ofx_internal.h"
+#include "quad_stage.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kQuads = 4;                      // quads (four pixels) per thread, kThreads apart in row-major order
-constexpr int kVecs = 4;                       // displacement: 16-byte (or 8-byte) items per thread, kThreads apart
-constexpr uint32_t kNowhere = 0x80000000u;     // a buffer offset beyond every plane and field (both are < 2^31 bytes): loads 0
+using namespace quad;
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base, int bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, bytes, 0x00027000);
-}
+constexpr int kVecs = 4; // displacement: 16-byte (or 8-byte) items per thread, kThreads apart
 
 __global__ __launch_bounds__(kThreads) void displacement_kernel(const ofx_displacement_batch A, const int vec16)
 {
@@ -93,30 +80,19 @@ __global__ __launch_bounds__(kThreads) void interp_kernel(const ofx_interp_batch
     const int b = blockIdx.y;
     const int w = A.w, h = A.h, wmax = w - 1, hmax = h - 1, nt = A.n_times;
     const int ap = A.a_pitch[b], bp = A.b_pitch[b];
-    const __amdgpu_buffer_rsrc_t rs_a = make_rsrc(A.a[b], hmax * ap + w), rs_b = make_rsrc(A.b[b], hmax * bp + w);
-    const __amdgpu_buffer_rsrc_t rs_ab = make_rsrc(A.dab[b], w * h * 8), rs_ba = make_rsrc(A.dba[b], w * h * 8);
+    const __amdgpu_buffer_rsrc_t rs_a = rsrc(A.a[b], hmax * ap + w), rs_b = rsrc(A.b[b], hmax * bp + w);
+    const __amdgpu_buffer_rsrc_t rs_ab = rsrc(A.dab[b], w * h * 8), rs_ba = rsrc(A.dba[b], w * h * 8);
     uint8_t *dst = A.dst[b];
     unsigned long long *stats = A.stats[b];
     const float wmaxf = (float)wmax, hmaxf = (float)hmax;
-    const uint32_t qrow = (uint32_t)(w + 3) >> 2, n_quads = qrow * (uint32_t)h;
+    const uint32_t qrow = quads_per_row(w), n_quads = qrow * (uint32_t)h;
     if (stats)
         for (int ti = 0; ti < nt; ++ti) cnt[ti][threadIdx.x] = 0; // (a thread's own words: no barrier needed)
 
-    // a quad's place, and its two fields by four 16-byte loads: no branch for the row's ragged end (its last pixels get the next
-    // row's vectors, or zeros past the field: they take no taps and are never looked at) nor for a quad past the end
-    auto place = [&](int g, int &y, int &x0) -> bool {
-        const uint32_t q = (blockIdx.x * kQuads + g) * kThreads + threadIdx.x;
-        y = (int)(q / qrow), x0 = 4 * (int)(q - (uint32_t)y * qrow);
-        return q < n_quads;
-    };
-    auto load_fields = [&](bool in, int y, int x0, float (&f)[16]) {
-        const uint32_t o = in ? 8u * ((uint32_t)y * (uint32_t)w + (uint32_t)x0) : kNowhere;
-        const f32x4 a0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_ab, o, 0, 0));
-        const f32x4 a1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_ab, o, 16, 0));
-        const f32x4 b0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_ba, o, 0, 0));
-        const f32x4 b1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_ba, o, 16, 0));
-#pragma unroll
-        for (int k = 0; k < 4; ++k) f[k] = a0[k], f[4 + k] = a1[k], f[8 + k] = b0[k], f[12 + k] = b1[k];
+    // a quad's two fields, Dab in f[0 .. 7] and Dba in f[8 .. 15]
+    auto load_fields = [&](bool in, int y, int x0, float *f) {
+        load_field(rs_ab, w, in, y, x0, f);
+        load_field(rs_ba, w, in, y, x0, f + 8);
     };
     // steps 3 to 5 of one side of one pixel, up to the taps: the offsets of the left taps of its two tap rows, whether the right
     // taps are one byte further (x0 < w - 1) or the same byte, and the fractions.  Returns "usable".
@@ -136,13 +112,13 @@ __global__ __launch_bounds__(kThreads) void interp_kernel(const ofx_interp_batch
 
     int y, x0, y_next = 0, x0_next = 0;
     float f[16], f_next[16];
-    bool have = place(0, y, x0), have_next = false;
+    bool have = place(qrow, n_quads, 0, y, x0), have_next = false;
     load_fields(have, y, x0, f);
 #pragma nounroll
     for (int g = 0; g < kQuads; ++g) {
         if (!have) break;
         // the next quad's fields go out before this quad's taps: their latency runs under them
-        have_next = g + 1 < kQuads && place(g + 1, y_next, x0_next);
+        have_next = g + 1 < kQuads && place(qrow, n_quads, g + 1, y_next, x0_next);
         load_fields(have_next, y_next, x0_next, f_next);
         const int npx = w - x0 < 4 ? w - x0 : 4;
         const float yf = (float)y;
@@ -200,19 +176,13 @@ __global__ __launch_bounds__(kThreads) void interp_kernel(const ofx_interp_batch
             for (int k = 0; k < 4; ++k) {
                 float V[2];
 #pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    const float p00 = (float)(r0[s][k] & 0xffu), p01 = (float)((r0[s][k] >> 8) & 0xffu);
-                    const float p10 = (float)(r1[s][k] & 0xffu), p11 = (float)((r1[s][k] >> 8) & 0xffu);
-                    const float q0 = p00 + fx[s][k] * (p01 - p00);
-                    const float q1 = p10 + fx[s][k] * (p11 - p10);
-                    V[s] = q0 + fy[s][k] * (q1 - q0);
-                }
+                for (int s = 0; s < 2; ++s) V[s] = blend_u8(r0[s][k], r1[s][k], fx[s][k], fy[s][k]);
                 const float mix = V[0] + t * (V[1] - V[0]);
                 const float v = cls[k] == 1u ? V[0] : cls[k] == 2u ? V[1] : mix;
-                out |= ((uint32_t)(int)(v + 0.5f) & 0xffu) << (8 * k);
+                out |= round_u8(v) << (8 * k);
                 if (k < npx && cls[k]) pk += 1u << (8 * (cls[k] - 1u));
             }
-            uint8_t *d = row + (size_t)ti * A.time_stride;
+            uint8_t *d = row + (size_t)ti * A.time_stride; // (store_quad_u8, written out: behind the function the time loop is scheduled otherwise)
             if (npx == 4 && dwords) {
                 *reinterpret_cast<uint32_t *>(d) = out;
             } else {
@@ -227,6 +197,7 @@ __global__ __launch_bounds__(kThreads) void interp_kernel(const ofx_interp_batch
         for (int k = 0; k < 16; ++k) f[k] = f_next[k];
     }
     if (!stats) return; // (block-uniform)
+    // the block reduction (the rule: quad_stage.h), per time and written out as in the other two kernels
     for (int ti = 0; ti < nt; ++ti) {
         const uint32_t pk = cnt[ti][threadIdx.x];
         uint32_t n1 = pk & 0xffu, n2 = (pk >> 8) & 0xffu, n3 = (pk >> 16) & 0xffu;
@@ -288,10 +259,8 @@ extern "C" int ofx_flow_displacement(const float *d_flow, int w, int h, const fl
 int ofx_interp_batch_launch(const ofx_interp_batch *a, void *stream)
 {
     const char *who = "ofx_interp_batch_launch";
-    OFX_REQUIRE(a && a->n >= 1 && a->n <= OFX_STREAM_MAX_BATCH, "%s: bad arguments", who);
-    OFX_REQUIRE(a->w > 0 && a->h > 0, "%s: w = %d, h = %d must be positive", who, a->w, a->h);
-    // (the fields are read through buffer resources: 8 bytes per pixel, below 2^31 bytes)
-    OFX_REQUIRE((size_t)a->w * (size_t)a->h < ((size_t)1 << 28), "%s: w * h = %d x %d is more than this build takes (2^28 pixels)", who, a->w, a->h);
+    OFX_REQUIRE(a, "%s: bad arguments", who);
+    OFX_TRY(check_batch(who, a->n, a->w, a->h, {a->a_pitch, a->b_pitch}, {a->dab, a->dba}, a->stats));
     OFX_REQUIRE(a->n_times >= 1 && a->n_times <= OFX_INTERP_MAX_TIMES, "%s: n_times = %d is not in 1 .. %d", who, a->n_times, OFX_INTERP_MAX_TIMES);
     for (int k = 0; k < a->n_times; ++k)
         OFX_REQUIRE(__builtin_isfinite(a->t[k]) && a->t[k] > 0.0f && a->t[k] < 1.0f, "%s: h_times[%d] = %g is not in (0, 1)", who, k, (double)a->t[k]);
@@ -301,30 +270,11 @@ int ofx_interp_batch_launch(const ofx_interp_batch *a, void *stream)
     bool dwords = (a->dst_pitch & 3) == 0 && (a->n_times == 1 || (a->time_stride & 3) == 0);
     for (int i = 0; i < a->n; ++i) {
         OFX_REQUIRE(a->a[i] && a->b[i], "%s: pair %d: a null plane (d_a, d_b)", who, i);
-        OFX_REQUIRE(a->dab[i] && a->dba[i], "%s: pair %d: a null field (d_disp_ab, d_disp_ba)", who, i);
         OFX_REQUIRE(a->dst[i], "%s: pair %d: d_dst is null", who, i);
-        OFX_REQUIRE(a->a_pitch[i] >= a->w && a->b_pitch[i] >= a->w, "%s: pair %d: a row pitch (a_pitch, b_pitch) below the width %d", who, i, a->w);
-        OFX_REQUIRE((size_t)a->h * (size_t)a->a_pitch[i] < ((size_t)1 << 31) && (size_t)a->h * (size_t)a->b_pitch[i] < ((size_t)1 << 31),
-                    "%s: pair %d: a plane of 2^31 bytes or more", who, i);
-        OFX_REQUIRE((((uintptr_t)a->dab[i] | (uintptr_t)a->dba[i]) & 7) == 0, "%s: pair %d: the fields (d_disp_ab, d_disp_ba) must be 8-byte aligned", who, i);
-        OFX_REQUIRE(((uintptr_t)a->stats[i] & 7) == 0, "%s: pair %d: d_stats must be 8-byte aligned", who, i);
         dwords = dwords && ((uintptr_t)a->dst[i] & 3) == 0;
     }
-    // everything is checked: zero the stats slots (4 * n_times words a pair), one memset per run of consecutive slots
-    const size_t words = 4 * (size_t)a->n_times;
-    for (int i = 0; i < a->n;) {
-        int e = i + 1;
-        if (!a->stats[i]) {
-            i = e;
-            continue;
-        }
-        while (e < a->n && a->stats[e] == a->stats[i] + words * (size_t)(e - i)) ++e;
-        OFX_HIP(hipMemsetAsync(a->stats[i], 0, (size_t)(e - i) * words * sizeof(unsigned long long), ofx_stream(stream)));
-        i = e;
-    }
-    const unsigned quads = (unsigned)((a->w + 3) >> 2) * (unsigned)a->h, per_block = kThreads * kQuads;
-    dim3 grid((quads + per_block - 1) / per_block, a->n);
-    hipLaunchKernelGGL(interp_kernel, grid, dim3(kThreads), 0, ofx_stream(stream), *a, (int)dwords);
+    OFX_TRY(zero_stats(a->stats, a->n, 4 * (size_t)a->n_times, stream)); // (everything is checked; a slot: four words per time)
+    hipLaunchKernelGGL(interp_kernel, grid(a->w, a->h, a->n), dim3(kThreads), 0, ofx_stream(stream), *a, (int)dwords);
     OFX_HIP(hipGetLastError());
     return OFX_OK;
 }

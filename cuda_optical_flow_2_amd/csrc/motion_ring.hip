@@ -15,26 +15,17 @@
 // goes through a buffer resource of exactly the plane's (h - 1) * pitch + w bytes, and a tap that the rule sets to 0 is given
 // an offset beyond it: the unit returns 0, and no coordinate, however wild, reads outside the plane.
 //
-// A thread takes kQuads quads, one after the other.  All tap loads of a quad are issued before the first is used; prev's
-// dword and the unshifted next's (for the sums) go out with them, and so did the NEXT quad's flow before them.  The sums are
-// integers: per-thread v_sad_u8 partial sums, a wave reduction by __shfl_xor, the block's four waves through LDS, then one
-// 64-bit atomicAdd per sum per block (a zero sum is not sent).  ofx_motion_batch_launch zeroes the four words of every slot
-// on the stream before the launch.  (A lane on the byte path waits for its sixteen taps inside that branch, before prev's and
-// next's dwords go out: a wave with a border lane runs both branches in turn.  Only waves at the image's borders have one.)
+// The march is quad_stage.h's.  prev's dword and the unshifted next's (for the sums) go out with a quad's taps.  The sums are
+// integers: per-thread v_sad_u8 partial sums, then the block reduction described in quad_stage.h into the pair's slot.  (A lane on the byte
+// path waits for its sixteen taps inside that branch, before prev's and next's dwords go out: a wave with a border lane runs both
+// branches in turn.  Only waves at the image's borders have one.)
 #include <string.h>
 
-#include "ofx_internal.h"
+#include "quad_stage.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kQuads = 4;                      // quads (four pixels) per thread, kThreads apart in row-major order
-constexpr uint32_t kNowhere = 0x80000000u;     // a buffer offset beyond every plane (planes are < 2^31 bytes): loads 0
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t plane_rsrc(const void *base, int bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, bytes, 0x00027000);
-}
+using namespace quad;
 
 // four bytes at `off` of a plane of `bytes` bytes: one dword where it lies inside, else its first n bytes one by one
 __device__ __forceinline__ uint32_t load_quad(const __amdgpu_buffer_rsrc_t &rs, uint32_t off, int bytes, int n)
@@ -54,7 +45,7 @@ __global__ __launch_bounds__(kThreads) void motion_ring_kernel(const ofx_motion_
     const int w = A.w, h = A.h, wmax = w - 1, hmax = h - 1;
     const int pp = A.prev_pitch[b], np = A.next_pitch[b];
     const int prev_bytes = hmax * pp + w, next_bytes = hmax * np + w;
-    const __amdgpu_buffer_rsrc_t rs_prev = plane_rsrc(A.prev[b], prev_bytes), rs_next = plane_rsrc(A.next[b], next_bytes);
+    const __amdgpu_buffer_rsrc_t rs_prev = rsrc(A.prev[b], prev_bytes), rs_next = rsrc(A.next[b], next_bytes);
     const float *flow = A.flow[b];
     uint8_t *dst = A.dst[b];
     unsigned long long *stats = A.stats[b];
@@ -62,7 +53,7 @@ __global__ __launch_bounds__(kThreads) void motion_ring_kernel(const ofx_motion_
     if (A.uv[b]) u = A.uv[b][0], v = A.uv[b][1];
     const float wf = (float)w, hf = (float)h, wmaxf = (float)wmax, hmaxf = (float)hmax, scale = A.scale;
     const uint32_t third = ((uint32_t)w * (uint32_t)h + 2u) / 3u; // 3 * pos < w * h  <=>  pos < ceil(w * h / 3)
-    const uint32_t qrow = (uint32_t)(w + 3) >> 2, n_quads = qrow * (uint32_t)h;
+    const uint32_t qrow = quads_per_row(w), n_quads = qrow * (uint32_t)h;
 
     // the shift's map of one coordinate: in range?  and where to
     auto map_col = [&](int x, int &nx) -> bool {
@@ -78,35 +69,20 @@ __global__ __launch_bounds__(kThreads) void motion_ring_kernel(const ofx_motion_
         return in;
     };
 
-    // a quad's place, and its flow by one 32-byte load through a resource of the field's size: no branch for the row's ragged end
-    // (its last pixels get the next row's flow, or zeros past the field: they are computed like the others and never looked at)
-    // nor for a quad past the end
-    const __amdgpu_buffer_rsrc_t rs_flow = plane_rsrc(flow, w * h * 8);
-    auto place = [&](int g, int &y, int &x0) -> bool {
-        const uint32_t q = (blockIdx.x * kQuads + g) * kThreads + threadIdx.x;
-        y = (int)(q / qrow), x0 = 4 * (int)(q - (uint32_t)y * qrow);
-        return q < n_quads;
-    };
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    auto load_flow = [&](bool in, int y, int x0, float (&f)[8]) {
-        const uint32_t o = in ? 8u * ((uint32_t)y * (uint32_t)w + (uint32_t)x0) : kNowhere;
-        const f32x4 a = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_flow, o, 0, 0));
-        const f32x4 c = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_flow, o, 16, 0));
-#pragma unroll
-        for (int k = 0; k < 4; ++k) f[k] = a[k], f[4 + k] = c[k];
-    };
+    // (the ragged end's pixels are computed like the others)
+    const __amdgpu_buffer_rsrc_t rs_flow = rsrc(flow, w * h * 8);
 
     uint32_t sad_raw = 0, sad_mc = 0, unwarped = 0;
     int y, x0, y_next, x0_next;
     float f[8], f_next[8];
-    bool have = place(0, y, x0), have_next = false;
-    load_flow(have, y, x0, f);
+    bool have = place(qrow, n_quads, 0, y, x0), have_next = false;
+    load_field(rs_flow, w, have, y, x0, f);
 #pragma unroll
     for (int g = 0; g < kQuads; ++g) {
         if (!have) break;
         // the next quad's flow goes out before this quad's taps: its latency runs under them
-        have_next = g + 1 < kQuads && place(g + 1, y_next, x0_next);
-        load_flow(have_next, y_next, x0_next, f_next);
+        have_next = g + 1 < kQuads && place(qrow, n_quads, g + 1, y_next, x0_next);
+        load_field(rs_flow, w, have_next, y_next, x0_next, f_next);
         const int npx = w - x0 < 4 ? w - x0 : 4;
         float fu[4], fv[4];
 #pragma unroll
@@ -176,24 +152,8 @@ __global__ __launch_bounds__(kThreads) void motion_ring_kernel(const ofx_motion_
         // the taps have arrived: the blend of warp_row_finish
         uint32_t out = 0;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float p00 = (float)(ra[k] & 0xffu), p01 = (float)((ra[k] >> 8) & 0xffu);
-            const float p10 = (float)(rb[k] & 0xffu), p11 = (float)((rb[k] >> 8) & 0xffu);
-            const float a = p00 + fx[k] * (p01 - p00);
-            const float c = p10 + fx[k] * (p11 - p10);
-            const float r = a + fy[k] * (c - a);
-            out |= ((uint32_t)(int)(r + 0.5f) & 0xffu) << (8 * k);
-        }
-        if (dst) {
-            uint8_t *d = dst + (size_t)y * (size_t)A.dst_pitch + (size_t)x0;
-            if (npx == 4 && A.dst_dwords) {
-                *reinterpret_cast<uint32_t *>(d) = out;
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (k < npx) d[k] = (uint8_t)(out >> (8 * k));
-            }
-        }
+        for (int k = 0; k < 4; ++k) out |= round_u8(blend_u8(ra[k], rb[k], fx[k], fy[k])) << (8 * k);
+        if (dst) store_quad_u8(dst + (size_t)y * (size_t)A.dst_pitch + (size_t)x0, out, npx, A.dst_dwords);
         if (stats) {
             const uint32_t m = npx == 4 ? 0xffffffffu : (1u << (8 * npx)) - 1u;
             sad_raw = __builtin_amdgcn_sad_u8(pv & m, nv & m, sad_raw);
@@ -205,6 +165,7 @@ __global__ __launch_bounds__(kThreads) void motion_ring_kernel(const ofx_motion_
         for (int k = 0; k < 8; ++k) f[k] = f_next[k];
     }
     if (!stats) return; // (block-uniform)
+    // the block reduction (the rule: quad_stage.h), written out: behind a function the kernel's other instructions come out in another order
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         sad_raw += __shfl_xor(sad_raw, o);
@@ -228,36 +189,18 @@ __global__ __launch_bounds__(kThreads) void motion_ring_kernel(const ofx_motion_
 int ofx_motion_batch_launch(const ofx_motion_batch *a, void *stream)
 {
     const char *who = "ofx_motion_batch_launch";
-    OFX_REQUIRE(a && a->n >= 1 && a->n <= OFX_STREAM_MAX_BATCH && a->w > 0 && a->h > 0, "%s: bad arguments", who);
-    // (the flow is read through a buffer resource: 8 bytes per pixel, below 2^31 bytes)
-    OFX_REQUIRE((size_t)a->w * (size_t)a->h < ((size_t)1 << 28), "%s: %d x %d is more than this build warps (2^28 pixels)", who, a->w, a->h);
+    OFX_REQUIRE(a, "%s: bad arguments", who);
+    OFX_TRY(check_batch(who, a->n, a->w, a->h, {a->prev_pitch, a->next_pitch}, {a->flow}, a->stats));
     for (int i = 0; i < a->n; ++i) {
-        OFX_REQUIRE(a->prev[i] && a->next[i] && a->flow[i], "%s: pair %d: null pointer", who, i);
+        OFX_REQUIRE(a->prev[i] && a->next[i], "%s: pair %d: null pointer", who, i);
         OFX_REQUIRE(a->dst[i] || a->stats[i], "%s: pair %d has neither an image nor a stats slot", who, i);
-        OFX_REQUIRE(a->prev_pitch[i] >= a->w && a->next_pitch[i] >= a->w, "%s: pair %d: a row pitch below the width %d", who, i, a->w);
-        OFX_REQUIRE((size_t)a->h * (size_t)a->prev_pitch[i] < ((size_t)1 << 31) && (size_t)a->h * (size_t)a->next_pitch[i] < ((size_t)1 << 31),
-                    "%s: pair %d: a plane of 2^31 bytes or more", who, i);
-        OFX_REQUIRE(((uintptr_t)a->flow[i] & 7) == 0, "%s: pair %d: the flow must be 8-byte aligned", who, i);
         OFX_REQUIRE(((uintptr_t)a->uv[i] & 3) == 0, "%s: pair %d: the shift vector must be 4-byte aligned", who, i);
-        OFX_REQUIRE(((uintptr_t)a->stats[i] & 7) == 0, "%s: pair %d: the stats must be 8-byte aligned", who, i);
         OFX_REQUIRE(!a->dst[i] || a->dst_pitch >= a->w, "%s: the image's row pitch %d is below the width %d", who, a->dst_pitch, a->w);
         OFX_REQUIRE(!a->dst_dwords || !a->dst[i] || (((uintptr_t)a->dst[i] | (uintptr_t)a->dst_pitch) & 3) == 0,
                     "%s: pair %d: dword stores need a 4-byte aligned image and pitch", who, i);
     }
-    // everything is checked: zero the stats slots, one memset per run of consecutive slots (a ring that wraps: two)
-    for (int i = 0; i < a->n;) {
-        int e = i + 1;
-        if (!a->stats[i]) {
-            i = e;
-            continue;
-        }
-        while (e < a->n && a->stats[e] == a->stats[i] + 4 * (e - i)) ++e;
-        OFX_HIP(hipMemsetAsync(a->stats[i], 0, (size_t)(e - i) * 4 * sizeof(unsigned long long), ofx_stream(stream)));
-        i = e;
-    }
-    const unsigned quads = (unsigned)((a->w + 3) >> 2) * (unsigned)a->h, per_block = kThreads * kQuads;
-    dim3 grid((quads + per_block - 1) / per_block, a->n);
-    hipLaunchKernelGGL(motion_ring_kernel, grid, dim3(kThreads), 0, ofx_stream(stream), *a);
+    OFX_TRY(zero_stats(a->stats, a->n, 4, stream)); // (everything is checked)
+    hipLaunchKernelGGL(motion_ring_kernel, grid(a->w, a->h, a->n), dim3(kThreads), 0, ofx_stream(stream), *a);
     OFX_HIP(hipGetLastError());
     return OFX_OK;
 }

@@ -12,6 +12,7 @@
 
 #include "iter_plan.h"
 #include "ofx_internal.h"
+#include "out_ring.h"
 
 // The stream pipeline with B frames per tick uses 3B + 2 image sets and 2B shift-vector slots (see stream_tick); the
 // pair-at-a-time paths rotate 3 sets and alternate 2 slots.
@@ -106,36 +107,27 @@ struct ofx_session {
     size_t ev_used = 0;
     hipEvent_t ev_frame = nullptr; // staged path: the caller's frame is complete (caller's stream -> aux)
     int n_sets = 0;                // image sets allocated (3B + 2; the pair-at-a-time paths rotate the first three)
-    // ofx_session_stream_compose: the caller's ring of composed fields (nullptr: off), and the newest pair composed into it
-    float *ring = nullptr;
-    size_t ring_stride = 0; // bytes from slot to slot
-    int ring_slots = 0, ring_level = 0;
-    long composed = 0;
-    // ofx_session_stream_arrows / _stream_tracks (sample_ring.hip): the caller's arrow ring, points, statuses and history ring
-    // (nullptr: off), and the newest pair sampled
-    int32_t *arrow_ring = nullptr;
-    size_t arrow_stride = 0;
-    int arrow_slots = 0, arrow_level = 0, arrow_offset = 0, arrow_ny = 0, arrow_nx = 0;
-    float *trk_points = nullptr, *trk_hist = nullptr;
+    // The output stages of the stream pipeline: each writes the pairs a call completes into a ring of the caller's (out_ring.h).  All
+    // rings are in `out`, so that ofx_session_stream_begin resets every one; a stage's level, scale, pitch and grid stay next to it.
+    enum { RING_COMPOSE, RING_ARROWS, RING_TRACKS, RING_MOTION, RING_DISP, N_RINGS };
+    ofx_ring::OutRing out[N_RINGS];
+    int ring_level = 0; // ofx_session_stream_compose: out[RING_COMPOSE] holds composed fields
+    // ofx_session_stream_arrows / _stream_tracks (sample_ring.hip): out[RING_ARROWS] holds arrow fields and its `newest` is the one
+    // counter of both (only the arrows have an accessor); the points and statuses (trk_points nullptr: tracks off) and, optional,
+    // out[RING_TRACKS], the history of the points' positions
+    int arrow_level = 0, arrow_offset = 0, arrow_ny = 0, arrow_nx = 0;
+    float *trk_points = nullptr;
     int32_t *trk_status = nullptr;
-    size_t trk_stride = 0;
-    int trk_n = 0, trk_slots = 0, trk_level = 0;
-    long sampled = 0;
-    // ofx_session_stream_motion (motion_ring.hip): the caller's image ring and stats ring (either may be nullptr; both: off), and
-    // the newest pair written
-    uint8_t *mc_ring = nullptr;
+    int trk_n = 0, trk_level = 0;
+    // ofx_session_stream_motion (motion_ring.hip): out[RING_MOTION] holds images (its base may be nullptr) and gives the slot count
+    // and the newest pair of the stats ring as well: pair p's four words are at mc_stats + 4 * index(p).  Both nullptr: off
     int64_t *mc_stats = nullptr;
-    size_t mc_stride = 0;
-    int mc_pitch = 0, mc_slots = 0, mc_level = 0;
+    int mc_pitch = 0, mc_level = 0;
     float mc_scale = 0.0f;
-    long motioned = 0;
-    // ofx_session_stream_displacement (interp.hip): the caller's ring of displacement fields (nullptr: off), and the newest pair
-    // written
-    float *disp_ring = nullptr;
-    size_t disp_stride = 0; // bytes from slot to slot
-    int disp_slots = 0, disp_level = 0;
+    bool motion_on() const { return out[RING_MOTION].on() || mc_stats; }
+    // ofx_session_stream_displacement (interp.hip): out[RING_DISP] holds displacement fields
+    int disp_level = 0;
     float disp_scale = 0.0f;
-    long displaced = 0;
     // ofx_session_stream_frontend: colour frames through the front end (frontend.hip).  fe_mode: what a frame gets
     // (OFX_FRONTEND_GREY / _BILATERAL / _BILATERAL_FAST), 0 = off; frame 0 of a stream gets OFX_FRONTEND_GREY with
     // OFX_FRONTEND_FLAG_FIRST_GREY.  borrow_frames: the filtered plane of image set i (fplane[i], at pitch[0]) stands in for the

@@ -17,6 +17,7 @@
 static int compose_ring(ofx_session *s, long first, long last, void *stream)
 {
     const int B = stream_batch_of(s), lv = s->ring_level;
+    ofx_ring::OutRing &ring = s->out[ofx_session::RING_COMPOSE];
     static thread_local ofx_compose_batch cb; // (1.7 KB)
     memset(&cb, 0, sizeof cb);
     cb.w = s->w[lv];
@@ -27,9 +28,9 @@ static int compose_ring(ofx_session *s, long first, long last, void *stream)
     for (int k = 0; k < s->p.levels; ++k) cb.own0[k] = s->own0[k];
     for (long p = first; p <= last; ++p, ++cb.n) {
         for (int k = lv; k < s->p.levels; ++k) cb.lv[cb.n][k] = s->flowset[p % B][k] + s->flow_own_offset(k);
-        cb.dst[cb.n] = reinterpret_cast<float *>(reinterpret_cast<char *>(s->ring) + (size_t)((p - 1) % s->ring_slots) * s->ring_stride);
+        cb.dst[cb.n] = reinterpret_cast<float *>(ring.slot(p));
     }
-    s->composed = last;
+    ring.newest = last;
     return timed_launch(s, OFX_TIME_COMPOSE, stream, [&] { return ofx_compose_batch_launch(&cb, stream); });
 }
 
@@ -37,11 +38,12 @@ static int compose_ring(ofx_session *s, long first, long last, void *stream)
 static int sample_ring(ofx_session *s, long first, long last, void *stream)
 {
     const int B = stream_batch_of(s);
+    ofx_ring::OutRing &arrows = s->out[ofx_session::RING_ARROWS], &hist = s->out[ofx_session::RING_TRACKS];
     static thread_local ofx_sample_batch sb; // (2 KB)
     memset(&sb, 0, sizeof sb);
     sb.levels = s->p.levels;
     for (int k = 0; k < s->p.levels; ++k) sb.own0[k] = s->own0[k];
-    if (s->arrow_ring) {
+    if (arrows.on()) {
         sb.a_level = s->arrow_level, sb.a_w = s->w[s->arrow_level], sb.a_h = s->h[s->arrow_level];
         sb.a_offset = s->arrow_offset, sb.a_ny = s->arrow_ny, sb.a_nx = s->arrow_nx;
     }
@@ -52,12 +54,10 @@ static int sample_ring(ofx_session *s, long first, long last, void *stream)
     }
     for (long p = first; p <= last; ++p, ++sb.n) {
         for (int k = 0; k < s->p.levels; ++k) sb.lv[sb.n][k] = s->flowset[p % B][k] + s->flow_own_offset(k);
-        if (s->arrow_ring)
-            sb.arrows[sb.n] = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(s->arrow_ring) + (size_t)((p - 1) % s->arrow_slots) * s->arrow_stride);
-        if (s->trk_points && s->trk_hist)
-            sb.hist[sb.n] = reinterpret_cast<float *>(reinterpret_cast<char *>(s->trk_hist) + (size_t)((p - 1) % s->trk_slots) * s->trk_stride);
+        if (arrows.on()) sb.arrows[sb.n] = reinterpret_cast<int32_t *>(arrows.slot(p));
+        if (s->trk_points && hist.on()) sb.hist[sb.n] = reinterpret_cast<float *>(hist.slot(p));
     }
-    s->sampled = last;
+    arrows.newest = hist.newest = last; // (the stage's one counter, whichever of the two is on)
     OfxRange range("ofx.sample_ring");
     return ofx_sample_batch_launch(&sb, stream);
 }
@@ -107,24 +107,24 @@ static int motion_ring(const Tick &t, long first, long last, void *stream)
 {
     ofx_session *s = t.s;
     const int lv = s->mc_level;
+    ofx_ring::OutRing &ring = s->out[ofx_session::RING_MOTION];
     static thread_local ofx_motion_batch mb; // (1 KB)
     memset(&mb, 0, sizeof mb);
     mb.w = s->w[lv], mb.h = s->h[lv], mb.scale = s->mc_scale;
     mb.dst_pitch = s->mc_pitch, mb.dst_dwords = 1; // (ofx_session_stream_motion checked the alignment)
     for (long p = first; p <= last; ++p, ++mb.n) {
-        const long slot = (p - 1) % s->mc_slots;
         mb.prev[mb.n] = t.plane_of(p - 1, lv), mb.prev_pitch[mb.n] = t.pitch_of(p - 1, lv, false);
         mb.next[mb.n] = t.plane_of(p, lv), mb.next_pitch[mb.n] = t.pitch_of(p, lv, false);
         mb.flow[mb.n] = s->flowset[p % t.B][lv];
         mb.uv[mb.n] = lv == t.L - 1 ? nullptr : t.uvslot(p) + 2 * lv; // (the coarsest level is not shifted)
-        if (s->mc_ring) mb.dst[mb.n] = s->mc_ring + (size_t)slot * s->mc_stride;
-        if (s->mc_stats) mb.stats[mb.n] = reinterpret_cast<unsigned long long *>(s->mc_stats + 4 * slot);
+        if (ring.on()) mb.dst[mb.n] = reinterpret_cast<uint8_t *>(ring.slot(p));
+        if (s->mc_stats) mb.stats[mb.n] = reinterpret_cast<unsigned long long *>(s->mc_stats + 4 * ring.index(p));
     }
     {
         OfxRange range("ofx.motion_ring");
         OFX_TRY(ofx_motion_batch_launch(&mb, stream)); // (zeroes the pairs' stats slots, then the one kernel launch)
     }
-    s->motioned = last;
+    ring.newest = last;
     return OFX_OK;
 }
 
@@ -140,13 +140,13 @@ static int displacement_ring(const Tick &t, long first, long last, void *stream)
     for (long p = first; p <= last; ++p, ++db.n) {
         db.flow[db.n] = s->flowset[p % t.B][lv];
         db.uv[db.n] = lv == t.L - 1 ? nullptr : t.uvslot(p) + 2 * lv; // (the coarsest level is not shifted)
-        db.dst[db.n] = reinterpret_cast<float *>(reinterpret_cast<char *>(s->disp_ring) + (size_t)((p - 1) % s->disp_slots) * s->disp_stride);
+        db.dst[db.n] = reinterpret_cast<float *>(s->out[ofx_session::RING_DISP].slot(p));
     }
     {
         OfxRange range("ofx.displacement_ring");
         OFX_TRY(ofx_displacement_batch_launch(&db, stream));
     }
-    s->displaced = last;
+    s->out[ofx_session::RING_DISP].newest = last;
     return OFX_OK;
 }
 
@@ -411,13 +411,13 @@ static int stream_tick(ofx_session *s, const uint8_t *const *frames, const int *
     if (newest >= 1) OFX_TRY(iter_passes(t, oldest, newest, stream));
     // the output stage (ofx_session_stream_compose): behind the tick's last launch on the same stream, before the next tick
     // rewrites flow set p mod B
-    if (s->ring && newest >= 1) OFX_TRY(compose_ring(s, oldest, newest, stream));
+    if (s->out[ofx_session::RING_COMPOSE].on() && newest >= 1) OFX_TRY(compose_ring(s, oldest, newest, stream));
     // the sampled output stage (ofx_session_stream_arrows / _stream_tracks): one launch, under the same rule
-    if ((s->arrow_ring || s->trk_points) && newest >= 1) OFX_TRY(sample_ring(s, oldest, newest, stream));
+    if ((s->out[ofx_session::RING_ARROWS].on() || s->trk_points) && newest >= 1) OFX_TRY(sample_ring(s, oldest, newest, stream));
     // the motion-compensation stage (ofx_session_stream_motion): one launch, under the same rule
-    if ((s->mc_ring || s->mc_stats) && newest >= 1) OFX_TRY(motion_ring(t, oldest, newest, stream));
+    if (s->motion_on() && newest >= 1) OFX_TRY(motion_ring(t, oldest, newest, stream));
     // the displacement stage (ofx_session_stream_displacement): one launch, under the same rule
-    if (s->disp_ring && newest >= 1) OFX_TRY(displacement_ring(t, oldest, newest, stream));
+    if (s->out[ofx_session::RING_DISP].on() && newest >= 1) OFX_TRY(displacement_ring(t, oldest, newest, stream));
     s->stream_n = t.f0 + t.B;
     return OFX_OK;
 }
@@ -438,10 +438,7 @@ extern "C" int ofx_session_stream_begin(ofx_session *s)
     s->n_held = 0;
     s->reported = 0;
     s->corner_newest = 0;
-    s->composed = 0;
-    s->sampled = 0;
-    s->motioned = 0;
-    s->displaced = 0;
+    for (ofx_ring::OutRing &r : s->out) r.reset();
     s->stream_input = 0;
     s->have_prev = s->have_next = s->staged = false;
     s->corner_done = false;
@@ -638,27 +635,41 @@ extern "C" int ofx_session_flow_of(ofx_session *s, int pair, int level, float **
     return OFX_OK;
 }
 
-extern "C" int ofx_session_stream_compose(ofx_session *s, int level, float *d_ring, size_t slot_stride_bytes, int n_slots)
+// ---- the ring outputs (out_ring.h) ---------------------------------------------------------------------------------------------
+// What every setter of an output stage asks first: an output is set before the first frame of a stream.
+static int output_settable(const ofx_session *s, const char *who)
 {
-    OFX_REQUIRE(s, "ofx_session_stream_compose: null session");
     if (s->stream_n > 0 || s->n_held > 0) {
-        ofx_set_error("ofx_session_stream_compose: the stream has frames already; set the ring before the first frame of a stream");
+        ofx_set_error("%s: the stream has frames already; set the output before the first frame of a stream", who);
         return OFX_E_STATE;
     }
+    return OFX_OK;
+}
+
+// ... and of the caller's ring: a slot for each pair one call completes, 16-byte aligned, slots a multiple of 16 bytes apart that hold
+// slot_bytes each
+static int ring_fits(const ofx_session *s, const void *ring, size_t stride, size_t slot_bytes, int n_slots, const char *who)
+{
+    const int B = stream_batch_of(s);
+    OFX_REQUIRE(n_slots >= B, "%s: %d slots, the ring needs at least stream_batch = %d (the pairs one call completes)", who, n_slots, B);
+    OFX_REQUIRE(((uintptr_t)ring & 15) == 0, "%s: the ring must be 16-byte aligned", who);
+    OFX_REQUIRE(stride % 16 == 0 && stride >= slot_bytes, "%s: slot stride %zu bytes must be a multiple of 16 and at least the slot's %zu bytes", who,
+                stride, slot_bytes);
+    return OFX_OK;
+}
+
+extern "C" int ofx_session_stream_compose(ofx_session *s, int level, float *d_ring, size_t slot_stride_bytes, int n_slots)
+{
+    const char *who = "ofx_session_stream_compose";
+    OFX_REQUIRE(s, "%s: null session", who);
+    OFX_TRY(output_settable(s, who));
     if (!d_ring) {
-        s->ring = nullptr;
-        s->composed = 0;
+        s->out[ofx_session::RING_COMPOSE].set(nullptr, 0, 0);
         return OFX_OK;
     }
-    const int B = stream_batch_of(s);
-    OFX_REQUIRE(level >= 0 && level < s->p.levels, "ofx_session_stream_compose: level %d out of range (0 .. %d)", level, s->p.levels - 1);
-    OFX_REQUIRE(n_slots >= B, "ofx_session_stream_compose: %d slots, the ring needs at least stream_batch = %d (the pairs one call completes)",
-                n_slots, B);
+    OFX_REQUIRE(level >= 0 && level < s->p.levels, "%s: level %d out of range (0 .. %d)", who, level, s->p.levels - 1);
     const size_t slot_bytes = (size_t)(s->own1[level] - s->own0[level]) * (size_t)s->w[level] * 2 * sizeof(float);
-    OFX_REQUIRE(((uintptr_t)d_ring & 15) == 0, "ofx_session_stream_compose: the ring must be 16-byte aligned");
-    OFX_REQUIRE(slot_stride_bytes % 16 == 0 && slot_stride_bytes >= slot_bytes,
-                "ofx_session_stream_compose: slot stride %zu bytes must be a multiple of 16 and at least the slot's %zu bytes", slot_stride_bytes,
-                slot_bytes);
+    OFX_TRY(ring_fits(s, d_ring, slot_stride_bytes, slot_bytes, n_slots, who));
     if (slot_bytes / 8 >= ((size_t)1 << 31)) {
         ofx_set_error("ofx_session_stream_compose: a slot of %zu pixels is more than this build composes (2^31)", slot_bytes / 8);
         return OFX_E_UNSUPPORTED;
@@ -673,51 +684,36 @@ extern "C" int ofx_session_stream_compose(ofx_session *s, int level, float *d_ri
             return OFX_E_UNSUPPORTED;
         }
     }
-    s->ring = d_ring;
-    s->ring_stride = slot_stride_bytes;
-    s->ring_slots = n_slots;
+    s->out[ofx_session::RING_COMPOSE].set(d_ring, slot_stride_bytes, n_slots);
     s->ring_level = level;
-    s->composed = 0;
     return OFX_OK;
 }
 
 extern "C" int ofx_session_composed_of(ofx_session *s, int pair, float **d_ptr, int *row0, int *rows)
 {
     OFX_REQUIRE(s, "ofx_session_composed_of: null session");
-    if (!s->ring) {
+    const ofx_ring::OutRing &ring = s->out[ofx_session::RING_COMPOSE];
+    if (!ring.on()) {
         ofx_set_error("ofx_session_composed_of: no ring set (ofx_session_stream_compose)");
         return OFX_E_STATE;
     }
-    OFX_REQUIRE(pair >= 1 && pair <= s->composed && pair > s->composed - s->ring_slots,
-                "ofx_session_composed_of: pair %d is not among the newest %d composed pairs (newest: %ld)", pair, s->ring_slots, s->composed);
+    OFX_REQUIRE(ring.holds(pair), "ofx_session_composed_of: pair %d is not among the newest %d composed pairs (newest: %ld)", pair, ring.slots,
+                ring.newest);
     const int lv = s->ring_level;
-    if (d_ptr) *d_ptr = reinterpret_cast<float *>(reinterpret_cast<char *>(s->ring) + (size_t)((pair - 1) % s->ring_slots) * s->ring_stride);
+    if (d_ptr) *d_ptr = reinterpret_cast<float *>(ring.slot(pair));
     if (row0) *row0 = s->own0[lv];
     if (rows) *rows = s->own1[lv] - s->own0[lv];
     return OFX_OK;
 }
 
-// what ofx_session_stream_arrows / _stream_tracks share: the session may take a new output setting, and the ring fits
+// what ofx_session_stream_arrows / _stream_tracks share: the session may take a new output setting
 static int sampled_settable(ofx_session *s, const char *who)
 {
-    if (s->stream_n > 0 || s->n_held > 0) {
-        ofx_set_error("%s: the stream has frames already; set the output before the first frame of a stream", who);
-        return OFX_E_STATE;
-    }
+    OFX_TRY(output_settable(s, who));
     if (s->p.sharded) {
         ofx_set_error("%s: not on a sharded session (sampled positions cross shard boundaries)", who);
         return OFX_E_UNSUPPORTED;
     }
-    return OFX_OK;
-}
-
-static int sampled_ring_ok(const ofx_session *s, const void *ring, size_t stride, size_t slot_bytes, int n_slots, const char *who)
-{
-    const int B = stream_batch_of(s);
-    OFX_REQUIRE(n_slots >= B, "%s: %d slots, the ring needs at least stream_batch = %d (the pairs one call completes)", who, n_slots, B);
-    OFX_REQUIRE(((uintptr_t)ring & 15) == 0, "%s: the ring must be 16-byte aligned", who);
-    OFX_REQUIRE(stride % 16 == 0 && stride >= slot_bytes, "%s: slot stride %zu bytes must be a multiple of 16 and at least the slot's %zu bytes", who,
-                stride, slot_bytes);
     return OFX_OK;
 }
 
@@ -727,34 +723,30 @@ extern "C" int ofx_session_stream_arrows(ofx_session *s, int level, int arrow_re
     OFX_REQUIRE(s, "%s: null session", who);
     OFX_TRY(sampled_settable(s, who));
     if (!d_ring) {
-        s->arrow_ring = nullptr;
-        s->sampled = 0;
+        s->out[ofx_session::RING_ARROWS].set(nullptr, 0, 0);
         return OFX_OK;
     }
     OFX_REQUIRE(level >= 0 && level < s->p.levels, "%s: level %d out of range (0 .. %d)", who, level, s->p.levels - 1);
     int offset, ny, nx;
     OFX_TRY(ofx_arrow_grid(s->w[level], s->h[level], arrow_res, &offset, &ny, &nx, who));
     OFX_TRY(ofx_check_sample_pyramid(s->w[level], s->h[level], s->p.levels, level, who));
-    OFX_TRY(sampled_ring_ok(s, d_ring, slot_stride_bytes, (size_t)ny * (size_t)nx * 16, n_slots, who));
-    s->arrow_ring = d_ring;
-    s->arrow_stride = slot_stride_bytes;
-    s->arrow_slots = n_slots;
+    OFX_TRY(ring_fits(s, d_ring, slot_stride_bytes, (size_t)ny * (size_t)nx * 16, n_slots, who));
+    s->out[ofx_session::RING_ARROWS].set(d_ring, slot_stride_bytes, n_slots);
     s->arrow_level = level;
     s->arrow_offset = offset, s->arrow_ny = ny, s->arrow_nx = nx;
-    s->sampled = 0;
     return OFX_OK;
 }
 
 extern "C" int ofx_session_arrows_of(ofx_session *s, int pair, int32_t **d_ptr, int *ny, int *nx)
 {
     OFX_REQUIRE(s, "ofx_session_arrows_of: null session");
-    if (!s->arrow_ring) {
+    const ofx_ring::OutRing &ring = s->out[ofx_session::RING_ARROWS];
+    if (!ring.on()) {
         ofx_set_error("ofx_session_arrows_of: no ring set (ofx_session_stream_arrows)");
         return OFX_E_STATE;
     }
-    OFX_REQUIRE(pair >= 1 && pair <= s->sampled && pair > s->sampled - s->arrow_slots,
-                "ofx_session_arrows_of: pair %d is not among the newest %d sampled pairs (newest: %ld)", pair, s->arrow_slots, s->sampled);
-    if (d_ptr) *d_ptr = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(s->arrow_ring) + (size_t)((pair - 1) % s->arrow_slots) * s->arrow_stride);
+    OFX_REQUIRE(ring.holds(pair), "ofx_session_arrows_of: pair %d is not among the newest %d sampled pairs (newest: %ld)", pair, ring.slots, ring.newest);
+    if (d_ptr) *d_ptr = reinterpret_cast<int32_t *>(ring.slot(pair));
     if (ny) *ny = s->arrow_ny;
     if (nx) *nx = s->arrow_nx;
     return OFX_OK;
@@ -766,23 +758,22 @@ extern "C" int ofx_session_stream_tracks(ofx_session *s, int level, float *d_poi
     const char *who = "ofx_session_stream_tracks";
     OFX_REQUIRE(s, "%s: null session", who);
     OFX_TRY(sampled_settable(s, who));
-    if (!d_points) {
-        s->trk_points = s->trk_hist = nullptr;
-        s->trk_status = nullptr;
+    ofx_ring::OutRing &hist = s->out[ofx_session::RING_TRACKS];
+    if (!d_points) { // (the arrows keep their counter)
+        s->trk_points = nullptr, s->trk_status = nullptr;
+        hist.set(nullptr, 0, 0);
         return OFX_OK;
     }
     OFX_REQUIRE(level >= 0 && level < s->p.levels, "%s: level %d out of range (0 .. %d)", who, level, s->p.levels - 1);
     OFX_REQUIRE(d_status && n_points >= 1, "%s: %d points need a status word each", who, n_points);
     OFX_REQUIRE(((uintptr_t)d_points & 7) == 0 && ((uintptr_t)d_status & 3) == 0, "%s: points must be 8-byte, statuses 4-byte aligned", who);
     OFX_TRY(ofx_check_sample_pyramid(s->w[level], s->h[level], s->p.levels, level, who));
-    if (d_history) OFX_TRY(sampled_ring_ok(s, d_history, slot_stride_bytes, (size_t)n_points * 8, n_slots, who));
+    if (d_history) OFX_TRY(ring_fits(s, d_history, slot_stride_bytes, (size_t)n_points * 8, n_slots, who));
     s->trk_points = d_points;
     s->trk_status = d_status;
     s->trk_n = n_points;
     s->trk_level = level;
-    s->trk_hist = d_history;
-    s->trk_stride = d_history ? slot_stride_bytes : 0;
-    s->trk_slots = d_history ? n_slots : 0;
+    hist.set(d_history, d_history ? slot_stride_bytes : 0, d_history ? n_slots : 0); // (optional)
     return OFX_OK;
 }
 
@@ -791,56 +782,44 @@ extern "C" int ofx_session_stream_motion(ofx_session *s, int level, float scale,
 {
     const char *who = "ofx_session_stream_motion";
     OFX_REQUIRE(s, "%s: null session", who);
-    if (s->stream_n > 0 || s->n_held > 0) {
-        ofx_set_error("%s: the stream has frames already; set the output before the first frame of a stream", who);
-        return OFX_E_STATE;
-    }
+    OFX_TRY(output_settable(s, who));
     if (!d_ring && !d_stats_ring) {
-        s->mc_ring = nullptr;
+        s->out[ofx_session::RING_MOTION].set(nullptr, 0, 0);
         s->mc_stats = nullptr;
-        s->motioned = 0;
         return OFX_OK;
     }
     if (s->p.sharded || s->p.frames_partial) {
         ofx_set_error("%s: not on a sharded session or with partial frames (a warp crosses shard rows)", who);
         return OFX_E_UNSUPPORTED;
     }
-    const int B = stream_batch_of(s);
     OFX_REQUIRE(level >= 0 && level < s->p.levels, "%s: level %d out of range (0 .. %d)", who, level, s->p.levels - 1);
-    OFX_REQUIRE(n_slots >= B, "%s: %d slots, the rings need at least stream_batch = %d (the pairs one call completes)", who, n_slots, B);
-    if (d_ring) {
-        const size_t slot_bytes = (size_t)s->h[level] * (size_t)row_pitch;
+    if (d_ring)
         OFX_REQUIRE(row_pitch >= s->w[level] && (row_pitch & 3) == 0, "%s: row pitch %d must be a multiple of 4 and at least the level's width %d", who,
                     row_pitch, s->w[level]);
-        OFX_REQUIRE(((uintptr_t)d_ring & 15) == 0, "%s: the ring must be 16-byte aligned", who);
-        OFX_REQUIRE(slot_stride_bytes % 16 == 0 && slot_stride_bytes >= slot_bytes,
-                    "%s: slot stride %zu bytes must be a multiple of 16 and at least the slot's %zu bytes", who, slot_stride_bytes, slot_bytes);
-    }
+    // (both rings have n_slots slots; without an image ring there is no stride to check)
+    OFX_TRY(ring_fits(s, d_ring, d_ring ? slot_stride_bytes : 0, d_ring ? (size_t)s->h[level] * (size_t)row_pitch : 0, n_slots, who));
     OFX_REQUIRE(((uintptr_t)d_stats_ring & 7) == 0, "%s: the stats ring must be 8-byte aligned", who);
-    s->mc_ring = d_ring;
+    s->out[ofx_session::RING_MOTION].set(d_ring, d_ring ? slot_stride_bytes : 0, n_slots);
     s->mc_stats = d_stats_ring;
     s->mc_pitch = d_ring ? row_pitch : 0;
-    s->mc_stride = d_ring ? slot_stride_bytes : 0;
-    s->mc_slots = n_slots;
     s->mc_level = level;
     s->mc_scale = scale;
-    s->motioned = 0;
     return OFX_OK;
 }
 
 extern "C" int ofx_session_motion_of(ofx_session *s, int pair, uint8_t **d_ptr, int *row_pitch, int64_t **d_stats)
 {
     OFX_REQUIRE(s, "ofx_session_motion_of: null session");
-    if (!s->mc_ring && !s->mc_stats) {
+    const ofx_ring::OutRing &ring = s->out[ofx_session::RING_MOTION];
+    if (!s->motion_on()) {
         ofx_set_error("ofx_session_motion_of: the stage is off (ofx_session_stream_motion)");
         return OFX_E_STATE;
     }
-    OFX_REQUIRE(pair >= 1 && pair <= s->motioned && pair > s->motioned - s->mc_slots,
-                "ofx_session_motion_of: pair %d is not among the newest %d pairs of the stage (newest: %ld)", pair, s->mc_slots, s->motioned);
-    const size_t slot = (size_t)((pair - 1) % s->mc_slots);
-    if (d_ptr) *d_ptr = s->mc_ring ? s->mc_ring + slot * s->mc_stride : nullptr;
+    OFX_REQUIRE(ring.holds(pair), "ofx_session_motion_of: pair %d is not among the newest %d pairs of the stage (newest: %ld)", pair, ring.slots,
+                ring.newest);
+    if (d_ptr) *d_ptr = ring.on() ? reinterpret_cast<uint8_t *>(ring.slot(pair)) : nullptr;
     if (row_pitch) *row_pitch = s->mc_pitch;
-    if (d_stats) *d_stats = s->mc_stats ? s->mc_stats + 4 * slot : nullptr;
+    if (d_stats) *d_stats = s->mc_stats ? s->mc_stats + 4 * ring.index(pair) : nullptr;
     return OFX_OK;
 }
 
@@ -848,45 +827,34 @@ extern "C" int ofx_session_stream_displacement(ofx_session *s, int level, float 
 {
     const char *who = "ofx_session_stream_displacement";
     OFX_REQUIRE(s, "%s: null session", who);
-    if (s->stream_n > 0 || s->n_held > 0) {
-        ofx_set_error("%s: the stream has frames already; set the output before the first frame of a stream", who);
-        return OFX_E_STATE;
-    }
+    OFX_TRY(output_settable(s, who));
     if (!d_ring) {
-        s->disp_ring = nullptr;
-        s->displaced = 0;
+        s->out[ofx_session::RING_DISP].set(nullptr, 0, 0);
         return OFX_OK;
     }
     if (s->p.sharded || s->p.frames_partial) {
         ofx_set_error("%s: not on a sharded session or with partial frames", who);
         return OFX_E_UNSUPPORTED;
     }
-    const int B = stream_batch_of(s);
     OFX_REQUIRE(level >= 0 && level < s->p.levels, "%s: level %d out of range (0 .. %d)", who, level, s->p.levels - 1);
     OFX_REQUIRE(__builtin_isfinite(scale), "%s: the scale must be finite", who);
-    OFX_REQUIRE(n_slots >= B, "%s: %d slots, the ring needs at least stream_batch = %d (the pairs one call completes)", who, n_slots, B);
-    const size_t slot_bytes = (size_t)s->h[level] * (size_t)s->w[level] * 8;
-    OFX_REQUIRE(((uintptr_t)d_ring & 15) == 0, "%s: the ring must be 16-byte aligned", who);
-    OFX_REQUIRE(slot_stride_bytes % 16 == 0 && slot_stride_bytes >= slot_bytes,
-                "%s: slot stride %zu bytes must be a multiple of 16 and at least the slot's %zu bytes", who, slot_stride_bytes, slot_bytes);
-    s->disp_ring = d_ring;
-    s->disp_stride = slot_stride_bytes;
-    s->disp_slots = n_slots;
+    OFX_TRY(ring_fits(s, d_ring, slot_stride_bytes, (size_t)s->h[level] * (size_t)s->w[level] * 8, n_slots, who));
+    s->out[ofx_session::RING_DISP].set(d_ring, slot_stride_bytes, n_slots);
     s->disp_level = level;
     s->disp_scale = scale;
-    s->displaced = 0;
     return OFX_OK;
 }
 
 extern "C" int ofx_session_displacement_of(ofx_session *s, int pair, float **d_ptr)
 {
     OFX_REQUIRE(s, "ofx_session_displacement_of: null session");
-    if (!s->disp_ring) {
+    const ofx_ring::OutRing &ring = s->out[ofx_session::RING_DISP];
+    if (!ring.on()) {
         ofx_set_error("ofx_session_displacement_of: the stage is off (ofx_session_stream_displacement)");
         return OFX_E_STATE;
     }
-    OFX_REQUIRE(pair >= 1 && pair <= s->displaced && pair > s->displaced - s->disp_slots,
-                "ofx_session_displacement_of: pair %d is not among the newest %d pairs of the stage (newest: %ld)", pair, s->disp_slots, s->displaced);
-    if (d_ptr) *d_ptr = reinterpret_cast<float *>(reinterpret_cast<char *>(s->disp_ring) + (size_t)((pair - 1) % s->disp_slots) * s->disp_stride);
+    OFX_REQUIRE(ring.holds(pair), "ofx_session_displacement_of: pair %d is not among the newest %d pairs of the stage (newest: %ld)", pair, ring.slots,
+                ring.newest);
+    if (d_ptr) *d_ptr = reinterpret_cast<float *>(ring.slot(pair));
     return OFX_OK;
 }
