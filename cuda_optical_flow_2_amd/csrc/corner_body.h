@@ -52,7 +52,7 @@ struct PatchBuild {
     int pw[OFX_MAX_LEVELS], ph[OFX_MAX_LEVELS], pitch[OFX_MAX_LEVELS]; // [0]: the patch of the frame itself (pitch: per slot)
     int off[OFX_MAX_LEVELS];                 // byte offset of level k inside a frame's patch planes
     int frame_stride;                        // bytes between the planes of the slot's two frames
-    int first;                               // 0: build both frames' planes; 1: only the second's (pyr_corner.hip: the first's are at hand)
+    int first;                               // always 0 (both frames' planes are built); kept because the struct is a kernel argument of every stream_kernel
 };
 struct PatchBuildSlot {
     const uint8_t *src[2]; // the frames (level 0, whole rows from column 0)

@@ -957,7 +957,6 @@ __device__ __forceinline__ void lk_wave_impl(const LkTable &T, int wave, int lan
 } // namespace ofx_dev
 #include "lk_body_warp.h" // the warp of lk_iter in two stages (ITER == 2 below)
 #include "lk_body_buf.h" // lk_wave_buf: the same march on buffer resources (a fifth of the scalar instructions)
-#include "lk_body_wide.h" // lk_wave_wide: eight columns per lane (round 4)
 #include "lk_body_pair.h" // lk_wave_pair: two refinement iterations in one march, the flow between them kept in LDS
 #undef OFX_LK_PRIO_STEP
 namespace ofx_dev {

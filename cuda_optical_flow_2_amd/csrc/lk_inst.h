@@ -23,18 +23,12 @@ int levels(int radius, const LkLevelIn *lv, int n, bool sums, hipStream_t st)
     return rc;
 }
 
-template <int MODE, bool FAST, int ITER, int NC>
+template <int MODE, bool FAST, int ITER>
 int iter(int radius, const LkLevelIn *lv, int n, hipStream_t st)
 {
     int rc = OFX_E_UNSUPPORTED;
-    const bool known = dispatch_radius<lk_max_radius(MODE, NC)>(radius, [&](auto R) {
-        if constexpr (NC == 8) rc = launch_iter_rd<decltype(R)::value, MODE, FAST, ITER, false, 8>(lv, n, st);
-        else rc = launch_iter_r<decltype(R)::value, MODE, FAST, ITER>(lv, n, st);
-    });
-    if (!known) {
-        if constexpr (NC == 8) ofx_set_error("ofx_lk_levels: window %d not supported with eight columns per lane", 2 * radius + 1);
-        else ofx_set_error("ofx_lk_level: window %d not supported in mode %d", 2 * radius + 1, MODE);
-    }
+    const bool known = dispatch_radius<lk_max_radius(MODE)>(radius, [&](auto R) { rc = launch_iter_r<decltype(R)::value, MODE, FAST, ITER>(lv, n, st); });
+    if (!known) ofx_set_error("ofx_lk_level: window %d not supported in mode %d", 2 * radius + 1, MODE);
     return rc;
 }
 
@@ -47,18 +41,12 @@ int iter_pair(int radius, const LkLevelIn *lv, int n, const ofx_pair_opts *opts,
     return rc;
 }
 
-template <int MODE, bool FAST, int WOUT, int NC>
+template <int MODE, bool FAST, int WOUT>
 int stream(int radius, const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st)
 {
     int rc = OFX_E_UNSUPPORTED;
-    const bool known = dispatch_radius<lk_max_radius(MODE, NC)>(radius, [&](auto R) {
-        if constexpr (NC == 8) rc = launch_stream_rd<decltype(R)::value, MODE, FAST, false, WOUT, 8>(lv, n, S, stage_blocks, lds, st);
-        else rc = launch_stream_r<decltype(R)::value, MODE, FAST, WOUT>(lv, n, S, stage_blocks, lds, st);
-    });
-    if (!known) {
-        if constexpr (NC == 8) ofx_set_error("ofx_stream_launch: window %d not supported with eight columns per lane", 2 * radius + 1);
-        else ofx_set_error("ofx_stream_launch: window %d not supported in mode %d", 2 * radius + 1, MODE);
-    }
+    const bool known = dispatch_radius<lk_max_radius(MODE)>(radius, [&](auto R) { rc = launch_stream_r<decltype(R)::value, MODE, FAST, WOUT>(lv, n, S, stage_blocks, lds, st); });
+    if (!known) ofx_set_error("ofx_stream_launch: window %d not supported in mode %d", 2 * radius + 1, MODE);
     return rc;
 }
 

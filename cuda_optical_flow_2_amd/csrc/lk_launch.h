@@ -70,17 +70,13 @@ __global__ __launch_bounds__(64, kLkMinWaves) void lk_level_kernel(const LkTable
 // SIMD, three for the other windows).  Capping it at 128 everywhere spills 2-8 registers and measured 1-3 % slower at 1080p, 4K
 // and 8K (profiles/r03_ablation.txt), so the cap stays at three waves.
 // DMA: the rows are fetched two steps ahead through LDS (lk_body_buf.h; chosen per launch as for the stream kernel)
-// NC = 8: the march with eight columns per lane (lk_body_wide.h; no deep fetch): two waves per SIMD
-template <int R, int MODE, bool FAST, int ITER, bool DMA = false, int NC = 4>
-__global__ __launch_bounds__(64, NC == 8 ? 2 : 3) void lk_iter_kernel(const LkTable T)
+// The body is lk_wave's !SUMS && !MAY_ACC branch (lk_body.h), written out: with a call of lk_wave in its place hipcc allocates the
+// scalar registers of the level search differently, and every lk_iter_kernel's code object changes.
+template <int R, int MODE, bool FAST, int ITER, bool DMA = false>
+__global__ __launch_bounds__(64, 3) void lk_iter_kernel(const LkTable T)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t xlds[NC == 8 ? kLkWaveLdsW : (DMA ? kLkWaveLdsDma : kLkWaveLdsX)];
+    __shared__ __attribute__((aligned(16))) uint8_t xlds[DMA ? kLkWaveLdsDma : kLkWaveLdsX];
     const int wave = (int)blockIdx.x, lane = (int)threadIdx.x;
-    if constexpr (NC == 8) {
-        static_assert(!DMA, "the wide march has no deep fetch");
-        lk_wave_w<R, MODE, FAST, ITER, 8>(T, wave, lane, xlds);
-        return;
-    }
     if (wave >= T.first_block[T.n]) return;
     int level = 0, hi = T.n;
     while (hi - level > 1) {
@@ -180,14 +176,13 @@ constexpr int kPyrPrio = 3; // priority of the marching-pyramid waves next to th
 // DMA: the LK stage fetches its rows two steps ahead through LDS (lk_body_buf.h); chosen per launch by launch_stream_r
 // WOUT: the LK stage is iteration 1 of pairs that have more (lk_iter): it also writes the warped images of their second iteration
 // (lk_body_buf.h, ITER = WOUT = 3, or 5 on the row windows of a shard; ~128 VGPRs: three blocks per CU at least); 0: it does not
-// NC = 8: the LK stage marches with eight columns per lane (lk_body_wide.h): ~170 VGPRs, three blocks per CU (two with WOUT)
 // blocks per CU: lk_float fits 5 (<= 96 VGPRs) without scratch for every radius; compat_cpu needs ~120: 4 blocks (<= 128)
-constexpr int stream_min_blocks(int mode, int wout, int nc)
+constexpr int stream_min_blocks(int mode, int wout)
 {
-    return nc == 8 ? (wout ? 2 : 3) : (wout ? 3 : (mode == OFX_MODE_LK_FLOAT ? 5 : 4));
+    return wout ? 3 : (mode == OFX_MODE_LK_FLOAT ? 5 : 4);
 }
-template <int R, int MODE, bool FAST, bool DMA, int WOUT = 0, int NC = 4>
-__global__ __launch_bounds__(256, stream_min_blocks(MODE, WOUT, NC)) void stream_kernel(const StreamArgs S)
+template <int R, int MODE, bool FAST, bool DMA, int WOUT = 0>
+__global__ __launch_bounds__(256, stream_min_blocks(MODE, WOUT)) void stream_kernel(const StreamArgs S)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
@@ -209,8 +204,7 @@ __global__ __launch_bounds__(256, stream_min_blocks(MODE, WOUT, NC)) void stream
                                      reinterpret_cast<int *>(lds + kCornerScratch - 32));
         }
     } else if (b < S.first[0]) {
-        if constexpr (NC == 8) lk_wave_w<R, MODE, FAST, WOUT, 8>(S.lk, 4 * (b - OFX_STREAM_MAX_BATCH) + wv, tid & 63, lds + wv * kLkWaveLdsW);
-        else lk_wave<R, MODE, false, false, FAST, DMA, WOUT>(S.lk, 4 * (b - OFX_STREAM_MAX_BATCH) + wv, tid & 63, lds + wv * (DMA ? kLkWaveLdsDma : kLkWaveLdsX));
+        lk_wave<R, MODE, false, false, FAST, DMA, WOUT>(S.lk, 4 * (b - OFX_STREAM_MAX_BATCH) + wv, tid & 63, lds + wv * (DMA ? kLkWaveLdsDma : kLkWaveLdsX));
     } else {
         int i = 0;
         while (i + 1 < kPyrStages && b >= S.first[i + 1]) ++i;
@@ -240,7 +234,7 @@ int env_int(const char *name, int dflt)
 // `capacity` (lk_wave_target), but at least `min_h` so the 2R priming rows of a strip stay a minor cost.
 // The grid is sized to fit in ONE residency round: every wave runs for the whole kernel, so a second, partly filled
 // round would nearly double the run time.
-// G: the tile's geometry (its OUT_W; TileGeomW<R, NC> -- NC = 4: TileGeom<R> -- or TileGeomP<R>)
+// G: the tile's geometry (its OUT_W; TileGeom<R> or TileGeomP<R>)
 template <typename G>
 int plan_table_g(const LkLevelIn *lv, int n, int capacity, LkTable *out)
 {
@@ -273,10 +267,10 @@ int plan_table_g(const LkLevelIn *lv, int n, int capacity, LkTable *out)
     return blocks;
 }
 
-template <int R, int NC = 4>
+template <int R>
 int plan_table(const LkLevelIn *lv, int n, int capacity, LkTable *out)
 {
-    return plan_table_g<TileGeomW<R, NC>>(lv, n, capacity, out);
+    return plan_table_g<TileGeom<R>>(lv, n, capacity, out);
 }
 
 // Number of LK waves a launch is planned for.  Every LK wave runs for the whole launch, so what matters is how many of
@@ -315,13 +309,13 @@ int launch_r(const LkLevelIn *lv, int n, hipStream_t st)
     return OFX_OK;
 }
 
-template <int R, int MODE, bool FAST, int ITER, bool DMA, int NC = 4>
+template <int R, int MODE, bool FAST, int ITER, bool DMA>
 int launch_iter_rd(const LkLevelIn *lv, int n, hipStream_t st)
 {
-    static const int capacity = lk_wave_target(lk_iter_kernel<R, MODE, FAST, ITER, DMA, NC>, 64, 0, 0, NC == 8 ? env_int("OFX_WIDE_WAVES_PER_SIMD", 2) : 4);
+    static const int capacity = lk_wave_target(lk_iter_kernel<R, MODE, FAST, ITER, DMA>, 64, 0, 0, 4);
     LkTable t{};
-    const int blocks = plan_table<R, NC>(lv, n, capacity, &t);
-    hipLaunchKernelGGL((lk_iter_kernel<R, MODE, FAST, ITER, DMA, NC>), dim3((unsigned)blocks), dim3(64), 0, st, t);
+    const int blocks = plan_table<R>(lv, n, capacity, &t);
+    hipLaunchKernelGGL((lk_iter_kernel<R, MODE, FAST, ITER, DMA>), dim3((unsigned)blocks), dim3(64), 0, st, t);
     OFX_HIP(hipGetLastError());
     return OFX_OK;
 }
@@ -365,20 +359,19 @@ int launch_pair_r(const LkLevelIn *lv, int n, const ofx_pair_opts *opts, hipStre
 // two frames per launch: 279 vs 295 us (-5 %); 4K with its frames in the Infinity Cache: 247 vs 237 us (+4 %: the form costs
 // ~60 more scalar instructions per step, and the loads are short there) -- so it is chosen by the size of the largest level:
 // planes of 16 Mpx and more do not stay cached between their two uses.  OFX_LK_DMA=0 / 1 overrides.
-template <int R, int MODE, bool FAST, bool DMA, int WOUT, int NC = 4>
+template <int R, int MODE, bool FAST, bool DMA, int WOUT>
 int launch_stream_rd(const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st)
 {
-    constexpr size_t wave_lds = NC == 8 ? kLkWaveLdsW : (DMA ? kLkWaveLdsDma : kLkWaveLdsX);
+    constexpr size_t wave_lds = DMA ? kLkWaveLdsDma : kLkWaveLdsX;
     // Next to the staging blocks the LK stage does best with 2 waves per SIMD when the tick carries one pair and 4 when it
     // carries more (measured, 4K: one pair 58.2 / 59.8 us per frame at 2 / 3; two pairs 59.7 / 57.2 / 56.5 at 2 / 3 / 4)
-    // (eight columns per lane: a wave carries twice the pixels, and three blocks fit a CU: 1 / 2 waves per SIMD)
-    static const int capacity1 = lk_wave_target(stream_kernel<R, MODE, FAST, DMA, WOUT, NC>, 256, 4 * wave_lds, 1, NC == 8 ? 1 : 2);
-    static const int capacity2 = lk_wave_target(stream_kernel<R, MODE, FAST, DMA, WOUT, NC>, 256, 4 * wave_lds, 1, NC == 8 ? env_int("OFX_WIDE_WAVES_PER_SIMD", 2) : 4);
+    static const int capacity1 = lk_wave_target(stream_kernel<R, MODE, FAST, DMA, WOUT>, 256, 4 * wave_lds, 1, 2);
+    static const int capacity2 = lk_wave_target(stream_kernel<R, MODE, FAST, DMA, WOUT>, 256, 4 * wave_lds, 1, 4);
     int pairs = 0;
     for (int i = 0; i < n; ++i) pairs += (lv[i].a.w == lv[0].a.w && lv[i].a.h == lv[0].a.h) ? 1 : 0;
     const int capacity = pairs >= 2 ? capacity2 : capacity1;
     int lk_blocks = 0;
-    if (n > 0) lk_blocks = ofx_div_up(plan_table<R, NC>(lv, n, capacity, &S.lk), 4);
+    if (n > 0) lk_blocks = ofx_div_up(plan_table<R>(lv, n, capacity, &S.lk), 4);
     S.first[0] = OFX_STREAM_MAX_BATCH + lk_blocks;
     for (int i = 0; i < kPyrStages; ++i) S.first[i + 1] = S.first[i] + stage_blocks[i];
     const int blocks = S.first[kPyrStages];
@@ -393,7 +386,7 @@ int launch_stream_rd(const LkLevelIn *lv, int n, StreamArgs &S, const int *stage
     }
     if (lds < corner_lds) lds = corner_lds;
     if (lds < 4 * wave_lds) lds = 4 * wave_lds; // an LK block: four waves, each with its exchange row (and its fetched rows)
-    hipLaunchKernelGGL((stream_kernel<R, MODE, FAST, DMA, WOUT, NC>), dim3((unsigned)blocks), dim3(256), lds, st, S);
+    hipLaunchKernelGGL((stream_kernel<R, MODE, FAST, DMA, WOUT>), dim3((unsigned)blocks), dim3(256), lds, st, S);
     OFX_HIP(hipGetLastError());
     return OFX_OK;
 }
@@ -429,7 +422,7 @@ bool dispatch_radius(int radius, F &&f)
         return false;
     }
 }
-constexpr int lk_max_radius(int mode, int nc = 4) { return mode == OFX_MODE_COMPAT_CPU && nc == 4 ? 12 : 11; } // windows up to 23x23 / 25x25
+constexpr int lk_max_radius(int mode) { return mode == OFX_MODE_COMPAT_CPU ? 12 : 11; } // windows up to 23x23 / 25x25
 
 } // namespace
 
@@ -441,15 +434,14 @@ template <int MODE, bool FAST>
 int levels(int radius, const LkLevelIn *lv, int n, bool sums, hipStream_t st);
 // refinement iterations on the buffer march (lk_wave_buf's ITER): 1 flow += result; 2 the launch also writes the next iteration's
 // warped images; 3 iteration 1 of pairs that have more: flow = result and the warped images of iteration 2; 4: 2 on the row
-// windows of a shard.  NC = 8, ITER = 0: all levels of one pair with eight columns per lane (the pair-at-a-time path)
-template <int MODE, bool FAST, int ITER, int NC = 4>
+// windows of a shard
+template <int MODE, bool FAST, int ITER>
 int iter(int radius, const LkLevelIn *lv, int n, hipStream_t st);
 // two refinement iterations per launch (lk_body_pair.h; radii 1..kLkPairMaxR, lk_float solves, whole levels): lv[i].a.flow_in is
 // the flow set read, .flow the one written; WOUT: the launch also writes the warped images of the iteration after its second
 template <bool FAST, bool WOUT>
 int iter_pair(int radius, const LkLevelIn *lv, int n, const ofx_pair_opts *opts, hipStream_t st);
-// one stream tick.  WOUT = 3: its LK stage also writes the warped images of its pairs' second iteration (5: on row windows);
-// NC = 8: eight columns per lane (lk_body_wide.h)
-template <int MODE, bool FAST, int WOUT = 0, int NC = 4>
+// one stream tick.  WOUT = 3: its LK stage also writes the warped images of its pairs' second iteration (5: on row windows)
+template <int MODE, bool FAST, int WOUT = 0>
 int stream(int radius, const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st);
 } // namespace ofx_launch

@@ -162,24 +162,6 @@ bool fit_buffer_offsets(const LkLevelIn *lv, int m)
     return true;
 }
 
-// Columns per lane of the LK march of a launch: 8 (lk_body_wide.h) or 4.  The wide march has no deep fetch, so launches that would
-// choose that (levels of 16 Mpx and more, launch_stream_r) keep four columns.  OFX_LK_COLS=4 / 8 overrides.
-#ifndef OFX_LK_COLS_DEFAULT
-#define OFX_LK_COLS_DEFAULT 4 // (measured, profiles/r04_ablation.txt: eight columns lose at 4K -- two LK waves per SIMD next to the pyramid stage)
-#endif
-int lk_cols(const LkLevelIn *lv, int m, int radius)
-{
-    static const int forced = [] { const char *e = getenv("OFX_LK_COLS"); return e ? atoi(e) : 0; }();
-    static const int dma_forced = [] { const char *e = getenv("OFX_LK_DMA"); return e ? atoi(e) : -1; }();
-    if (radius < 1 || radius > 11 || m <= 0) return 4;
-    if (dma_forced < 0 && ofx_launch::g_stream_deep_fetch > 0) return 4;
-    if (forced == 4 || forced == 8) return forced;
-    long max_px = 0;
-    for (int i = 0; i < m; ++i) max_px = (long)lv[i].a.w * lv[i].a.h > max_px ? (long)lv[i].a.w * lv[i].a.h : max_px;
-    if (dma_forced > 0 || (dma_forced < 0 && max_px >= 16l * 1000 * 1000)) return 4;
-    return OFX_LK_COLS_DEFAULT;
-}
-
 int lk_dispatch(const ofx_lk_desc *d, int n, int window, int mode, int32_t *d_sums, void *stream)
 {
     LkLevelIn lv[OFX_MAX_LK_ITEMS];
@@ -211,11 +193,6 @@ int lk_dispatch(const ofx_lk_desc *d, int n, int window, int mode, int32_t *d_su
             return mode == OFX_MODE_LK_FLOAT_FAST ? run(std::true_type{}) : run(std::false_type{});
         }
     }
-    // (experiment, OFX_LK_PLAIN_COLS=8: the pair-at-a-time launch on the march with eight columns per lane)
-    static const bool plain_wide = [] { const char *e = getenv("OFX_LK_PLAIN_COLS"); return e && atoi(e) == 8; }();
-    if (plain_wide && !d_sums && mode == OFX_MODE_LK_FLOAT && !lv[0].a.accumulate && !lv[0].a.warp_out && radius >= 1 && radius <= 11 &&
-        fit_buffer_offsets(lv, m))
-        return ofx_launch::iter<OFX_MODE_LK_FLOAT, false, 0, 8>(radius, lv, m, st);
     const bool sums = d_sums != nullptr; // (the sums do not depend on the solve)
     if (mode == OFX_MODE_COMPAT_CPU) return ofx_launch::levels<OFX_MODE_COMPAT_CPU, false>(radius, lv, m, sums, st);
     if (mode == OFX_MODE_LK_FLOAT_FAST && !sums) return ofx_launch::levels<OFX_MODE_LK_FLOAT, true>(radius, lv, m, false, st);
@@ -352,7 +329,6 @@ extern "C" int ofx_stream_launch(const ofx_stream_stages *g, int window, int mod
             return rw ? ofx_launch::stream<OFX_MODE_LK_FLOAT, F, 5>(radius, lv, m, S, stage_blocks, lds, st)
                       : ofx_launch::stream<OFX_MODE_LK_FLOAT, F, 3>(radius, lv, m, S, stage_blocks, lds, st);
         }
-        if (lk_cols(lv, m, radius) == 8) return ofx_launch::stream<OFX_MODE_LK_FLOAT, F, 0, 8>(radius, lv, m, S, stage_blocks, lds, st);
         return ofx_launch::stream<OFX_MODE_LK_FLOAT, F>(radius, lv, m, S, stage_blocks, lds, st);
     };
     return mode == OFX_MODE_LK_FLOAT_FAST ? tick(std::true_type{}) : tick(std::false_type{});

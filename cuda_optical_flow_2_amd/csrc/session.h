@@ -75,13 +75,6 @@ struct ofx_session {
     // (borrow_frames) and the chain reads a patch (stream_two_stage, local_corner).
     uint8_t *preloc[kMaxBatch][OFX_MAX_LEVELS]{};
     bool repair = false;
-    // pair-at-a-time sessions (neither local_corner nor stream_two_stage, whole frames): ofx_session_build_pyramid also walks the
-    // pair's corner chain in one more block of its launch (pyr_corner.hip) on patch planes that block builds: pscr[0][0 / 1] hold the
-    // patch pyramids of two image sets in turn (pset_img / pset_gen: which set's, and of which load), preloc[0] the repair's planes
-    bool plain_fuse = false;
-    bool corner_done = false; // the shift vectors of the pair (prev, next) are in uv_cur() already
-    int pset_img[2] = {-1, -1};
-    long pset_gen[2] = {0, 0}, img_gen[3] = {0, 0, 0};
     int debug_extent = 0; // test hook (OFX_DEBUG_CORNER_EXTENT): the chain may only read this many level-0 columns / rows of its patch planes
     int *corner_status = nullptr;
     int *pair_status = nullptr; // one word per shift-vector slot (pair p -> slot p mod 2B)

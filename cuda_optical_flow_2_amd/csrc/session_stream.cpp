@@ -441,8 +441,6 @@ extern "C" int ofx_session_stream_begin(ofx_session *s)
     for (ofx_ring::OutRing &r : s->out) r.reset();
     s->stream_input = 0;
     s->have_prev = s->have_next = s->staged = false;
-    s->corner_done = false;
-    s->pset_img[0] = s->pset_img[1] = -1;
     for (int k = 0; k < s->p.levels; ++k) s->flow[k] = s->flowset[0][k];
     return OFX_OK;
 }

@@ -4,11 +4,14 @@
     python tools/isa_digest.py --out before.txt        (on the old tree)
     python tools/isa_digest.py --out after.txt         (on the new tree)
     python tools/isa_digest.py --compare before.txt after.txt
+    python tools/isa_digest.py --compare before.txt after.txt --rename REGEX REPL     (a kernel template lost or gained a parameter)
 
 Every .hip unit of build.SOURCES is compiled with build.FLAGS plus --cuda-device-only -S.  A kernel's digest is the SHA-256 of its
 assembly body, its .amdhsa_kernel block (registers, static LDS, occupancy attributes) and its metadata entry (arguments, limits),
 with what depends on the compilation unit rather than on the kernel normalised away: the __hip_cuid_* symbol and the function index
-inside local labels and block names, so that the order in which the kernels are emitted does not matter.  Digests only: nothing is searched for.
+inside local labels and block names, so that the order in which the kernels are emitted does not matter, and the kernel's own mangled
+name (in its labels, its metadata and the symbols of its static LDS), so that a change of its template's parameter list alone leaves
+the digest as it was; --rename then maps the old names to the new ones.  Digests only: nothing is searched for.
 """
 import argparse
 import hashlib
@@ -44,7 +47,7 @@ def unit_digests(unit, tmp):
     for m in re.finditer(r"^\t\.amdhsa_kernel (\S+)\n.*?^\t\.end_amdhsa_kernel$", text, re.S | re.M):
         name = m.group(1)
         body = re.search(r"^%s:.*?^\.Lfunc_end:" % re.escape(name), text, re.S | re.M).group(0)
-        h = hashlib.sha256("\n".join([body, m.group(0), entries[name]]).encode()).hexdigest()
+        h = hashlib.sha256("\n".join([body, m.group(0), entries[name]]).replace(name[2:], "KERNEL").encode()).hexdigest()
         out.append(f"{unit} {name} {h}")
     return out
 
@@ -54,8 +57,10 @@ def read(path):
         return {tuple(l.split()[:2]): l.split()[2] for l in f if l.strip()}
 
 
-def compare(a, b):
+def compare(a, b, rename=None):
     da, db = read(a), read(b)
+    if rename:
+        da = {(u, re.sub(rename[0], rename[1], k)): h for (u, k), h in da.items()}
     differ = sorted(k for k in da if k in db and da[k] != db[k])
     missing, extra = sorted(set(da) - set(db)), sorted(set(db) - set(da))
     for tag, ks in (("differs", differ), ("missing", missing), ("extra", extra)):
@@ -69,9 +74,10 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--out", help="write the sorted 'unit kernel digest' lines here (default: stdout)")
     ap.add_argument("--compare", nargs=2, metavar=("BEFORE", "AFTER"), help="compare two such files")
+    ap.add_argument("--rename", nargs=2, metavar=("REGEX", "REPL"), help="with --compare: re.sub applied to the kernel names of BEFORE")
     args = ap.parse_args()
     if args.compare:
-        return compare(*args.compare)
+        return compare(*args.compare, rename=args.rename)
     units = [s for s in build.SOURCES if s.endswith(".hip")]
     with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(max_workers=min(os.cpu_count() or 4, 8)) as ex:
         lines = sorted(l for ls in ex.map(lambda u: unit_digests(u, tmp), units) for l in ls)
