@@ -255,15 +255,17 @@ class Oracle:
         self.lib.orc_warp_bilinear_u8(_p(src1, _u8p), w, h, _p(flow, _f32p), C.c_float(self.ITER_SCALE if scale is None else scale), _p(d, _u8p))
         return d
 
-    def lk_iter_level(self, prev1, next1_shifted, window, iters):
+    def lk_iter_level(self, prev1, next1_shifted, window, iters, min_det=0.0):
+        """min_det > 0: the determinant guard of include/ofx.h after every iteration's solve (orc_lk_iter_level_guard)"""
         prev1, next1_shifted = _c(prev1, np.uint8), _c(next1_shifted, np.uint8)
         h, w = prev1.shape
         flow = np.empty((h, w, 2), np.float32)
         first = np.empty((h, w, 2), np.float32)
-        self.lib.orc_lk_iter_level(_p(prev1, _u8p), _p(next1_shifted, _u8p), w, h, window, iters, _p(flow, _f32p), _p(first, _f32p))
+        self.lib.orc_lk_iter_level_guard(_p(prev1, _u8p), _p(next1_shifted, _u8p), w, h, window, iters, C.c_float(min_det),
+                                         _p(flow, _f32p), _p(first, _f32p))
         return flow, first
 
-    def flow_pair_iter(self, prev1, next1, levels, window, iters):
+    def flow_pair_iter(self, prev1, next1, levels, window, iters, min_det=0.0):
         """lk_float pyramid with `iters` refinement iterations per level.  Returns the flow pyramid (accumulated)."""
         pp = self.gauss_pyramid(np.repeat(prev1[:, :, None], 3, 2), levels)
         npyr = self.gauss_pyramid(np.repeat(next1[:, :, None], 3, 2), levels)
@@ -272,7 +274,7 @@ class Oracle:
         out = [None] * levels
         for k in range(levels - 1, -1, -1):
             nxt3 = npyr[k] if k == levels - 1 else self.shift_back_pyramid(npyr[k], k, levels, first)
-            out[k], first[k] = self.lk_iter_level(pp[k][:, :, 0], nxt3[:, :, 0], window, iters)
+            out[k], first[k] = self.lk_iter_level(pp[k][:, :, 0], nxt3[:, :, 0], window, iters, min_det)
         return out
 
     # ---- bilateral

@@ -568,14 +568,36 @@ void orc_warp_bilinear_u8(const uint8_t *src1, int w, int h, const float *flow_u
         }
 }
 
-void orc_lk_iter_level(const uint8_t *prev1, const uint8_t *next1_shifted, int w, int h, int window, int iters,
-                       float *flow_uv, float *flow_first)
+void orc_lk_iter_level_guard(const uint8_t *prev1, const uint8_t *next1_shifted, int w, int h, int window, int iters,
+                             float min_det, float *flow_uv, float *flow_first)
 {
     const size_t n = (size_t)w * (size_t)h;
     uint8_t *p3 = (uint8_t *)malloc(3 * n), *n3 = (uint8_t *)malloc(3 * n), *warped = (uint8_t *)malloc(n);
     float *delta = (float *)malloc(2 * n * sizeof(float));
     float *levels[1] = {delta};
+    uint8_t *low = NULL; /* the determinant guard (include/ofx.h, ofx_lk_desc.min_det): 1 where the pixel's result is (0, 0) */
     orc_replicate_1ch_to_3ch(prev1, p3, (int)n);
+    if (min_det > 0.0f) {
+        /* Sxx, Syy, Sxy are window sums of prev's derivatives alone: the same floats in every iteration, so the mask is made
+         * once.  The sums are the float planes the solve reads (exact integer sums rounded once, orc_srm_1ch_f32_exact); their
+         * products are exact in double (24-bit factors), so det is the exact difference rounded once, then once more to float. */
+        float *ix = (float *)malloc(n * sizeof(float)), *iy = (float *)malloc(n * sizeof(float));
+        float *s = (float *)malloc(3 * n * sizeof(float));
+        orc_conv_3ch_to_1ch_f32(p3, w, h, ix, orc_Dx_3x3, 3, 3);
+        orc_conv_3ch_to_1ch_f32(p3, w, h, iy, orc_Dy_3x3, 3, 3);
+        orc_srm_1ch_f32_exact(ix, ix, w, h, window, window, s);
+        orc_srm_1ch_f32_exact(iy, iy, w, h, window, window, s + n);
+        orc_srm_1ch_f32_exact(ix, iy, w, h, window, window, s + 2 * n);
+        low = (uint8_t *)malloc(n);
+        for (size_t p = 0; p < n; ++p) {
+            const double a = (double)s[p], d = (double)s[n + p], b = (double)s[2 * n + p];
+            const double det = a * d - b * b;
+            low[p] = !((float)det >= min_det);
+        }
+        free(s);
+        free(iy);
+        free(ix);
+    }
     for (int it = 0; it < iters; ++it) {
         if (it == 0) {
             orc_replicate_1ch_to_3ch(next1_shifted, n3, (int)n);
@@ -585,6 +607,9 @@ void orc_lk_iter_level(const uint8_t *prev1, const uint8_t *next1_shifted, int w
         }
         /* one level, already shifted: level == max_level - 1 skips the shift inside */
         orc_calc_opt_flow_gpu(p3, n3, w, h, levels, 0, 1, window, 1);
+        if (low)
+            for (size_t p = 0; p < n; ++p)
+                if (low[p]) delta[2 * p] = delta[2 * p + 1] = 0.0f;
         if (it == 0) {
             memcpy(flow_uv, delta, 2 * n * sizeof(float));
             if (flow_first) memcpy(flow_first, delta, 2 * n * sizeof(float));
@@ -592,10 +617,17 @@ void orc_lk_iter_level(const uint8_t *prev1, const uint8_t *next1_shifted, int w
             for (size_t i = 0; i < 2 * n; ++i) flow_uv[i] = flow_uv[i] + delta[i];
         }
     }
+    free(low);
     free(delta);
     free(warped);
     free(n3);
     free(p3);
+}
+
+void orc_lk_iter_level(const uint8_t *prev1, const uint8_t *next1_shifted, int w, int h, int window, int iters,
+                       float *flow_uv, float *flow_first)
+{
+    orc_lk_iter_level_guard(prev1, next1_shifted, w, h, window, iters, 0.0f, flow_uv, flow_first);
 }
 
 /* ------------------------------------------------------------------------ */

@@ -128,6 +128,13 @@ void orc_bilateral_3ch(const uint8_t *src3, const uint8_t *gray3, uint8_t *dst3,
 void orc_warp_bilinear_u8(const uint8_t *src1, int w, int h, const float *flow_uv, float scale, uint8_t *dst1);
 void orc_lk_iter_level(const uint8_t *prev1, const uint8_t *next1_shifted, int w, int h, int window, int iters,
                        float *flow_uv /* out: accumulated */, float *flow_first /* out, may be NULL: iteration 1 only */);
+/* ... with the determinant guard of include/ofx.h (ofx_lk_desc.min_det; csrc/lk_solve.h, solve_guard) after the solve of EVERY
+ * iteration, the first included: with a, d, b the float planes Sxx, Syy, Sxy the solve reads and det = a*d - b*b in double
+ * (rounded once), a pixel with !((float)det >= min_det) gets (0, 0) as that iteration's result -- an accumulating iteration leaves
+ * its flow as it was, and the guarded first-iteration flow is the flow_first that feeds the shift vectors.  min_det <= 0: no guard
+ * (orc_lk_iter_level). */
+void orc_lk_iter_level_guard(const uint8_t *prev1, const uint8_t *next1_shifted, int w, int h, int window, int iters,
+                             float min_det, float *flow_uv, float *flow_first);
 
 /* ---- helpers for 1-channel pipelines (layout only, no arithmetic) ------- */
 void orc_replicate_1ch_to_3ch(const uint8_t *src1, uint8_t *dst3, int n);

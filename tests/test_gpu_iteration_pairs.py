@@ -4,8 +4,8 @@ j + 1, the second trailing the first by R + 2 rows; the flow and the warped imag
 for bit.
 
 The stream pipeline takes pyramids of two levels and more whose downsampled levels have even dimensions, so the level sizes
-that matter to the fused tile (224 output columns at 9x9, 240 below) are those of LEVEL 1 of a frame twice as large; level 0
-runs through the same launch and is compared too."""
+that matter to the fused tile (232 output columns at 9x9, 240 at 7x7 and 5x5, 248 at 3x3) are those of LEVEL 1 of a frame twice
+as large; level 0 runs through the same launch and is compared too."""
 import numpy as np
 import pytest
 
@@ -78,8 +78,8 @@ def _stream(eng, frames, w, h, L, win, mode, iters, B, ptrs=None, launches=None,
     return {p: [t.cpu().numpy() for t in v] for p, v in got.items()}
 
 
-# level-1 widths 223 / 224 / 225 (around the 9x9 tile), 449, 517 (odd, a ragged last chunk), 100 (less than one tile; with level 2
-# at 100x5); level-1 heights 130, 259, 8 and -- three levels -- 10 and 5 (around and below the lag R + 2)
+# level-1 widths 223 / 224 / 225 (inside the 232 columns of the 9x9 tile; around the 224 it had once), 449, 517 (odd, a ragged last
+# chunk), 100 (less than one tile; with level 2 at 100x5); level-1 heights 130, 259, 8 and -- three levels -- 10 and 5 (around and below the lag R + 2)
 S223, S224, S225, S449, S517, S100 = (446, 260, 2), (448, 518, 2), (450, 16, 2), (898, 260, 2), (1034, 518, 2), (400, 20, 3)
 CASES = [
     (S223, 9, 5, "lk_float", 1), (S223, 3, 3, "lk_float_fast", 2), (S224, 9, 4, "lk_float_fast", 2), (S224, 5, 6, "lk_float", 1),

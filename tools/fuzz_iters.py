@@ -2,7 +2,9 @@
 (csrc/lk_body_warp.h; the default) against one warp launch per iteration (OFX_ITER_FUSED=0), pair at a time and through the
 stream pipeline -- random size, levels, window, iterations, solve, frames per tick, borrowed frames, deep row fetch, row sharding
 (logical ranks on one device; a result that differs must come with a non-zero status word), and frames with flat blocks and
-noise (non-finite and huge flows).  tests/test_gpu_parity.py pins the two-launch form against the oracle.
+noise (non-finite and huge flows).  Against the oracle, tests/test_gpu_parity.py pins the two-launch form on smooth pairs, and
+tests/test_gpu_iter_hard.py the default form on such frames: every window 3x3 .. 23x23 pair at a time, the stream pipeline with two
+iterations per launch, min_det against the guarded restatement, lk_float_fast step by step.
     python tools/fuzz_iters.py [n_configs] [seed]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
