@@ -60,6 +60,11 @@ static_assert(TileGeomP<1>::LO_LANE == 1 && TileGeomP<1>::HI_LANE == 62 && TileG
 // per instance, should one not fit its registers (profiles/pair_rcp_budget.txt: all sixteen do)
 constexpr bool pair_share_rcp(int r, bool fast) { return OFX_PAIR_SHARE_RCP != 0; }
 
+// A comment in the listing, no instruction: marks the paths of the joint step that a segment takes a bounded number of times (its
+// priming, B's start, A's drain: 3R + 4 steps however many rows it has).  tools/isa_waits.py leaves paths through a marked block out
+// when it measures how long the warp's tap loads stay in flight on the steps in between, where both marches emit.
+#define OFX_COLD_PATH() asm volatile("; ofx-cold")
+
 constexpr int kLkPairMaxR = 4;
 constexpr int pair_warp_rows(int r) { return 2 * r + 4; } // rows [yyB - 2R, yyB + 1] are live in a step: 2R + 2, and slack
 constexpr int pair_flow_rows(int r) { return r + 3; }     // LAG + 1
@@ -181,6 +186,12 @@ __device__ __forceinline__ void lk_wave_pair(const LkTable &T, int level, int ti
     }
     int axx[4] = {0, 0, 0, 0}, ayy[4] = {0, 0, 0, 0}, axy[4] = {0, 0, 0, 0}, axt[4] = {0, 0, 0, 0}, ayt[4] = {0, 0, 0, 0};
 
+    // Loaded values that a path must have waited for before it reaches a join (no instruction but the s_waitcnt the compiler puts
+    // in front).  Loads complete in order and the compiler counts them per path, but where paths join it keeps the worst count
+    // of a register: a value one path still has in flight as its YOUNGEST load costs vmcnt(0) behind the join on every path,
+    // also on the one that has just issued the warp's taps.  Only the cold paths have such values.
+    auto landed = [](uint32_t &a, uint32_t &b) { asm volatile("; ofx-cold" : "+v"(a), "+v"(b)); };
+    auto landed4 = [](uint32_t &a, uint32_t &b, uint32_t &c, uint32_t &d) { asm volatile("; ofx-cold" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)); };
     // a step of A that emits nothing leaves its slot of the line undefined (no copy to keep what it held)
     auto no_rcp = [](double (&q)[4]) {
         if constexpr (SHARE) asm("" : "=v"(q[0]), "=v"(q[1]), "=v"(q[2]), "=v"(q[3])); // (ONE asm: four alike are merged, then copied)
@@ -197,8 +208,8 @@ __device__ __forceinline__ void lk_wave_pair(const LkTable &T, int level, int ti
         const int yh = folded ? y_firstA + s : yo;
         const int ro = (H > 1 && s + 1 < H) ? y_firstA + s + 2 : yo + 2;
         const int po_in = row_offA(yy + 2), po_out = row_off_outA(ro);
-        const uint32_t pf_ip = load_u32(rs_prev, po_in), pf_in = load_u32(rs_next, po_in);
-        const uint32_t pf_op = load_u32(rs_prev, po_out), pf_on = load_u32(rs_next, po_out);
+        uint32_t pf_ip = load_u32(rs_prev, po_in), pf_in = load_u32(rs_next, po_in);
+        uint32_t pf_op = load_u32(rs_prev, po_out), pf_on = load_u32(rs_next, po_out);
         const bool emit = s >= PR;
         const int yw = yy - R; // this step's output row
         f32x4 old_a, old_b;
@@ -246,7 +257,14 @@ __device__ __forceinline__ void lk_wave_pair(const LkTable &T, int level, int ti
             const lds_ptr fr = fring + fslot(yw);
             *(__attribute__((address_space(3))) f32x4 *)(fr) = f32x4{uv[0], uv[1], uv[2], uv[3]};
             *(__attribute__((address_space(3))) f32x4 *)(fr + 16) = f32x4{uv[4], uv[5], uv[6], uv[7]};
-        } else no_rcp(rq[0][k]);
+        } else {
+            no_rcp(rq[0][k]);
+            // The step's rows are unpacked behind the join.  On the emitting path they are older than the old flow, which has
+            // been waited for; on this one they are the youngest loads, and left to the join the compiler waits there for the
+            // worse of the two -- which drained the taps eleven instructions after their issue (profiles/warp_taps_isa.txt).
+            // So this path waits for its rows itself.
+            landed4(pf_ip, pf_in, pf_op, pf_on);
+        }
         unpack_pk(finish_row(pf_ip), finish_row(pf_in), finish_row(pf_op), finish_row(pf_on), wa[k]);
         pin_row(wa[k]);
     };
@@ -265,12 +283,16 @@ __device__ __forceinline__ void lk_wave_pair(const LkTable &T, int level, int ti
         return v;
     };
     RowPk<MODE> wb[3];
-    uint32_t pfb_i = 0u, pfb_o = 0u; // B's rows of prev for the next step, in flight
+    // B's rows of prev for the next step, in flight.  B takes them at the top of its part, behind the join of A's paths.  Where A
+    // emitted, they are older than loads A has waited for; the two paths on which they are not (A finished, B's priming) wait for
+    // them inside the path (`landed`).
+    uint32_t pfb_i = 0u, pfb_o = 0u;
     int bxx[4] = {0, 0, 0, 0}, byy[4] = {0, 0, 0, 0}, bxy[4] = {0, 0, 0, 0}, bxt[4] = {0, 0, 0, 0}, byt[4] = {0, 0, 0, 0};
     const int fso0 = __builtin_amdgcn_readfirstlane((ysB * A.w + x0) * 8);
     // the high stream's bottom row of step s (lk_wave_buf fetches it a step earlier: `ro`, and the third priming row)
     auto high_rowB = [&](int s) -> int { return (H > 0 && (s == 0 || s < H)) ? y_firstB + s + 1 : y_lo0B + s - NS + 1; };
     auto primeB = [&]() {
+        OFX_COLD_PATH();
         uint32_t pi, ni, po = 0u, no = 0u;
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
@@ -284,6 +306,7 @@ __device__ __forceinline__ void lk_wave_pair(const LkTable &T, int level, int ti
         }
         pfb_i = load_u32(rs_prev, row_offB(y_lo0B + 1));
         pfb_o = load_u32(rs_prev, H > 0 ? row_off_outB(high_rowB(0)) : kOob);
+        landed(pfb_i, pfb_o); // (step 0 takes them at once; once per segment)
     };
     auto store_row = [&](int s_row, const f32x4 xlo, const f32x4 xhi) {
         const int fso = __builtin_amdgcn_readfirstlane(fso0 + (s_row - PR) * fstep);
@@ -355,7 +378,7 @@ __device__ __forceinline__ void lk_wave_pair(const LkTable &T, int level, int ti
             const f32x4 xlo = *(__attribute__((address_space(3))) f32x4 *)(xl_r);
             const f32x4 xhi = *(__attribute__((address_space(3))) f32x4 *)(xl_r + 1024);
             store_row(s, xlo, xhi);
-        }
+        } else OFX_COLD_PATH();
     };
 
     // ---- the joint march: step t is A's step t and B's step t - kLagSteps
@@ -379,8 +402,10 @@ __device__ __forceinline__ void lk_wave_pair(const LkTable &T, int level, int ti
         }
         if (t < nstepsA) stepA(K, t);
         else {
+            OFX_COLD_PATH();
             if (t == nstepsA) ring_warped(yeA - 1);
             no_rcp(rq[0][k]);
+            landed(pfb_i, pfb_o); // (on this path B's rows are not behind a wait of A's yet)
         }
         if (t >= kLagSteps) {
             // (what A has just put into the rings is read by other lanes: LDS operations of a wave execute in order)
@@ -390,7 +415,7 @@ __device__ __forceinline__ void lk_wave_pair(const LkTable &T, int level, int ti
                 if (t == kLagSteps) primeB();
             }
             stepB(std::integral_constant<int, kb>{}, t - kLagSteps, rcpB);
-        }
+        } else OFX_COLD_PATH();
     };
     int s = 0;
     while (true) {
