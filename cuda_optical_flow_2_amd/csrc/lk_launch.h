@@ -11,6 +11,7 @@
 #include "lk_body.h"
 #include "pair_plan.h"
 #include "pyr_march.h"
+#include "session_plan.h"
 #include "stages_body.h"
 
 using namespace ofx_dev;
@@ -328,7 +329,7 @@ int launch_iter_r(const LkLevelIn *lv, int n, hipStream_t st)
     static const int forced = [] { const char *e = getenv("OFX_ITER_DMA"); return e ? atoi(e) : -1; }();
     long max_px = 0;
     for (int i = 0; i < n; ++i) max_px = (long)lv[i].a.w * lv[i].a.h > max_px ? (long)lv[i].a.w * lv[i].a.h : max_px;
-    if (forced > 0 || (forced < 0 && max_px >= 16l * 1000 * 1000)) return launch_iter_rd<R, MODE, FAST, ITER, true>(lv, n, st);
+    if (forced > 0 || (forced < 0 && ofx_plan::deep_fetch_by_size(max_px))) return launch_iter_rd<R, MODE, FAST, ITER, true>(lv, n, st);
     return launch_iter_rd<R, MODE, FAST, ITER, false>(lv, n, st);
 }
 
@@ -402,7 +403,7 @@ int launch_stream_r(const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_
         // longer than the Infinity Cache gains 5 % / 3.5 % with the deep fetch, a warm one loses 2 %: the caller can say which,
         // ofx_params.deep_fetch)
         const int want = forced >= 0 ? (forced > 0 ? 1 : -1) : g_stream_deep_fetch;
-        if (want > 0 || (want == 0 && max_px >= 16l * 1000 * 1000)) return launch_stream_rd<R, MODE, FAST, true, WOUT>(lv, n, S, stage_blocks, lds, st);
+        if (want > 0 || (want == 0 && ofx_plan::deep_fetch_by_size(max_px))) return launch_stream_rd<R, MODE, FAST, true, WOUT>(lv, n, S, stage_blocks, lds, st);
     }
     return launch_stream_rd<R, MODE, FAST, false, WOUT>(lv, n, S, stage_blocks, lds, st);
 }

@@ -153,7 +153,7 @@ int lk_build_levels(const ofx_lk_desc *d, int n, int window, int mode, int32_t *
 // The buffer march addresses a level's planes and its flow rows through buffer resources with 32-bit offsets (lk_body_buf.h)
 bool fits_buffer_offsets(const LkArgs &a)
 {
-    return (long long)(a.row_end - a.row0) * a.pitch < (1ll << 31) && (long long)(a.out_y1 - a.flow_row0) * a.w * 8 < (1ll << 31);
+    return ofx_plan::fits_buffer_offsets(a.row_end - a.row0, a.pitch, a.out_y1 - a.flow_row0, a.w);
 }
 bool fit_buffer_offsets(const LkLevelIn *lv, int m)
 {

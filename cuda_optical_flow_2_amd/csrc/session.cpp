@@ -2,15 +2,13 @@
 //
 // One hipMalloc arena holds, per pyramid level: the previous and the next frame's 1-channel planes, a scratch
 // plane for the shifted next frame, the flow field, and the 2-float shift vector.  Nothing is allocated or freed
-// while frames flow (the reference does 58 cudaMalloc/cudaFree calls per level).
+// while frames flow (the reference does 58 cudaMalloc/cudaFree calls per level).  What the arena holds and where is the
+// plan's (session_plan.h); ofx_session_create walks it.
+#include <memory>
 #include <new>
 
 #include "compat_scratch.h"
 #include "session.h"
-
-#ifndef OFX_ITER_PAIRS_DEFAULT
-#define OFX_ITER_PAIRS_DEFAULT 1 // the stream pipeline's iterations two per launch (lk_body_pair.h); OFX_ITER_PAIRS=0 / 1 overrides
-#endif
 
 static void repoint(ofx_session *s)
 {
@@ -25,234 +23,98 @@ static void repoint(ofx_session *s)
     if (s->pframe[(s->cur + 1) % 3]) s->plane[1][0] = const_cast<uint8_t *>(s->pframe[(s->cur + 1) % 3]) + skip;
 }
 
+// The environment of a session (ofx_plan::SessionSwitches says what each switch does), read once per ofx_session_create.
+static ofx_plan::SessionSwitches session_switches_from_env()
+{
+    auto env = [](const char *name, int dflt) {
+        const char *e = getenv(name);
+        return e ? atoi(e) : dflt;
+    };
+    ofx_plan::SessionSwitches sw;
+    sw.iter_fused = env("OFX_ITER_FUSED", 1) != 0;
+    sw.iter_pairs = env("OFX_ITER_PAIRS", sw.iter_pairs) != 0;
+    sw.iter_dma = env("OFX_ITER_DMA", 0) > 0;
+    sw.pair_pack = env("OFX_PAIR_PACK", 1) != 0;
+    const int waves = env("OFX_PAIR_WAVES", 0);
+    sw.pair_waves = waves > 0 ? waves : 0;
+    sw.debug_corner_extent = env("OFX_DEBUG_CORNER_EXTENT", 0);
+    return sw;
+}
+
+// Frees what a session under construction holds: ofx_session_create's one exit for every failure.
+struct SessionDeleter {
+    void operator()(ofx_session *s) const
+    {
+        if (s->arena) (void)hipFree(s->arena);
+        delete s;
+    }
+};
+
 extern "C" int ofx_session_create(const ofx_params *p_in, ofx_session **out)
 {
     OFX_REQUIRE(p_in && out, "ofx_session_create: null argument");
-    // The fused warp of a refinement iteration fetches a tap's dword AT the tap's byte (lk_body_warp.h): its source must be followed by
-    // three readable bytes.  Every plane of a session is (by 64); the one warp source that would be a caller's buffer is level 0 of
-    // a single-level session on borrowed frames (pair at a time: the stream pipeline needs two levels) -- such a session copies its frames.
-    ofx_params eff = *p_in;
-    if (eff.levels == 1 && eff.iters > 1 && eff.borrow_frames) eff.borrow_frames = 0, eff.stream_two_stage = 0;
-    const ofx_params *p = &eff;
-    OFX_REQUIRE(p->width > 0 && p->height > 0, "ofx_session_create: bad size %dx%d", p->width, p->height);
-    OFX_REQUIRE(p->levels >= 1 && p->levels <= OFX_MAX_LEVELS, "ofx_session_create: levels %d out of range", p->levels);
-    OFX_REQUIRE(p->window >= 3 && (p->window & 1), "ofx_session_create: window must be odd and >= 3");
-    OFX_REQUIRE(p->mode == OFX_MODE_COMPAT_CPU || p->mode == OFX_MODE_LK_FLOAT || p->mode == OFX_MODE_LK_FLOAT_FAST,
-                "ofx_session_create: bad mode %d", p->mode);
-    OFX_REQUIRE(p->min_det >= 0.0f, "ofx_session_create: min_det must be >= 0 (0 = the reference's unguarded solve)");
-    OFX_REQUIRE(p->iters >= 0 && p->iters <= 64, "ofx_session_create: iters %d out of range", p->iters);
-    OFX_REQUIRE(p->stream_batch >= 0 && p->stream_batch <= OFX_STREAM_MAX_BATCH, "ofx_session_create: stream_batch %d (0 .. %d)", p->stream_batch,
-                OFX_STREAM_MAX_BATCH);
-    OFX_REQUIRE(p->stream_batch * p->levels <= OFX_MAX_LK_ITEMS, "ofx_session_create: stream_batch %d needs levels <= %d",
-                p->stream_batch, OFX_MAX_LK_ITEMS / (p->stream_batch > 0 ? p->stream_batch : 1));
-    OFX_REQUIRE(!p->stream_two_stage || p->borrow_frames, "ofx_session_create: stream_two_stage needs borrow_frames (the corner stage reads "
-                                                            "both frames of a pair in the tick in which the second one arrives)");
-    OFX_REQUIRE(p->iters <= 1 || p->mode != OFX_MODE_COMPAT_CPU, "ofx_session_create: refinement iterations need mode lk_float");
-    OFX_REQUIRE(p->deep_fetch >= -1 && p->deep_fetch <= 1, "ofx_session_create: deep_fetch must be -1, 0 or +1 (got %d)", p->deep_fetch);
-    OFX_REQUIRE(!p->frames_partial || (p->sharded && p->local_corner && !p->stream_two_stage),
-                "ofx_session_create: frames_partial describes the frames of a sharded local_corner session (not stream_two_stage)");
-    OFX_REQUIRE(p->iters <= 1 || !p->sharded || p->local_corner,
-                "ofx_session_create: refinement iterations on a sharded session run through the stream pipeline, which needs local_corner");
-    OFX_REQUIRE((p->width >> (p->levels - 1)) > 0 && (p->height >> (p->levels - 1)) > 0,
-                "ofx_session_create: %d levels is too many for %dx%d", p->levels, p->width, p->height);
-    for (int k = 0; k + 1 < p->levels; ++k)
-        OFX_REQUIRE(((p->width >> k) & 1) == 0 && ((p->height >> k) & 1) == 0,
-                    "ofx_session_create: level %d is %dx%d; every level that is downsampled must have even dimensions "
-                    "(the reference assumes a source stride of exactly 2*w, OptFlowCPU.cpp:117)",
-                    k, p->width >> k, p->height >> k);
-    OFX_HIP(hipSetDevice(p->device));
-
-    ofx_session *s = new (std::nothrow) ofx_session();
+    ofx_plan::SessionPlan plan;
+    char err[512];
+    if (const int rc = ofx_plan::session_plan_make(p_in, session_switches_from_env(), &plan, err, sizeof err)) {
+        ofx_set_error("%s", err);
+        return rc;
+    }
+    OFX_HIP(hipSetDevice(plan.p.device));
+    std::unique_ptr<ofx_session, SessionDeleter> guard(new (std::nothrow) ofx_session());
+    ofx_session *s = guard.get();
     OFX_REQUIRE(s != nullptr, "ofx_session_create: out of host memory");
-    s->p = *p;
-    // image sets: the stream pipeline cycles through 3B + 2 of them (B = frames per tick; a session created without a
-    // stream_batch may still stream one frame per tick), the pair-at-a-time paths rotate the first three
-    const int B = stream_batch_of(s), n_sets = stream_sets(s);
-    s->n_sets = n_sets;
-    size_t total = 0;
-    // (streamed refinement iterations: two more scratch planes per pair of a tick)
-    const int n_iter_sets = p->iters > 1 ? 3 * B : 0; // per flow set: shifted, warped, warped'
-    std::vector<size_t> off_plane[kSets + 2 + 3 * kMaxBatch], off_flow, off_flow2, off_flow_alt, flow_stride;
-    // Two iterations per launch in the stream pipeline (lk_body_pair.h): unsharded lk_float sessions with three iterations or more,
-    // windows up to 9x9, levels that do not take the deep fetch (below 16 Mpx).  OFX_ITER_PAIRS=0 / 1 overrides the default.
-    const bool want_pairs = p->iters >= 3 && !p->sharded && (p->mode == OFX_MODE_LK_FLOAT || p->mode == OFX_MODE_LK_FLOAT_FAST) &&
-                            (p->window >> 1) >= 1 && (p->window >> 1) <= 4 && (long)p->width * p->height < 16l * 1000 * 1000 &&
-                            [] { const char *e = getenv("OFX_ITER_DMA"); return !e || atoi(e) <= 0; }() &&
-                            [] { const char *e = getenv("OFX_ITER_PAIRS"); return e ? atoi(e) != 0 : OFX_ITER_PAIRS_DEFAULT != 0; }();
-    for (int k = 0; k < p->levels; ++k) {
-        s->w[k] = p->width >> k;
-        s->h[k] = p->height >> k;
-        s->pitch[k] = (int)align_up((size_t)s->w[k], 64);
-        if (p->sharded) {
-            s->own0[k] = p->own_y0[k];
-            s->own1[k] = p->own_y1[k];
-            s->buf0[k] = p->buf_y0[k];
-            s->buf1[k] = p->buf_y1[k];
-            const bool has_comp = p->comp_y1[k] > 0;
-            s->cmp0[k] = has_comp ? p->comp_y0[k] : s->own0[k];
-            s->cmp1[k] = has_comp ? p->comp_y1[k] : s->own1[k];
-            const bool ok = 0 <= s->buf0[k] && s->buf0[k] <= s->own0[k] && s->own0[k] <= s->own1[k] &&
-                            s->own1[k] <= s->buf1[k] && s->buf1[k] <= s->h[k] && s->buf0[k] < s->buf1[k] &&
-                            s->buf0[k] <= s->cmp0[k] && s->cmp0[k] <= s->own0[k] && s->own1[k] <= s->cmp1[k] &&
-                            s->cmp1[k] <= s->buf1[k];
-            if (!ok) {
-                ofx_set_error("ofx_session_create: level %d shard rows own [%d,%d) buf [%d,%d) invalid for height %d", k,
-                              s->own0[k], s->own1[k], s->buf0[k], s->buf1[k], s->h[k]);
-                delete s;
-                return OFX_E_INVALID;
-            }
-        } else {
-            s->own0[k] = s->buf0[k] = s->cmp0[k] = 0;
-            s->own1[k] = s->buf1[k] = s->cmp1[k] = s->h[k];
-        }
-        s->fl0[k] = s->own0[k];
-        s->fl1[k] = s->own1[k];
-        if (p->sharded && p->iters > 1) {
-            const int reach = (p->window >> 1) + 1, ext = reach * (p->iters - 1);
-            s->fl0[k] = s->own0[k] - ext > 0 ? s->own0[k] - ext : 0;
-            s->fl1[k] = s->own1[k] + ext < s->h[k] ? s->own1[k] + ext : s->h[k];
-            const int lo = s->fl0[k] - reach > 0 ? s->fl0[k] - reach : 0, hi = s->fl1[k] + reach < s->h[k] ? s->fl1[k] + reach : s->h[k];
-            if (lo < s->buf0[k] || hi > s->buf1[k]) {
-                ofx_set_error("ofx_session_create: level %d: %d iterations need rows [%d,%d) in the buffers (own rows +- (radius + 1) * iters), "
-                              "they hold [%d,%d): plan the shard with its iterations (ShardPlan(iters=...))", k, p->iters, lo, hi, s->buf0[k], s->buf1[k]);
-                delete s;
-                return OFX_E_INVALID;
-            }
-        }
-        const size_t plane_bytes = align_up((size_t)s->pitch[k] * (size_t)(s->buf1[k] - s->buf0[k]) + 64, kAlign);
-        for (int t = 0; t < n_sets + 2 + n_iter_sets; ++t) { // image sets + 2 shifted sets + the streamed iterations' scratch
-            off_plane[t].push_back(total);
-            total += plane_bytes;
-        }
-        off_flow.push_back(total);
-        const size_t own_rows = (size_t)(s->fl1[k] - s->fl0[k]);
-        const size_t flow_bytes = align_up((own_rows ? own_rows : 1) * (size_t)s->w[k] * 2 * sizeof(float), kAlign);
-        total += flow_bytes;
-        off_flow2.push_back(total); // further flow sets: a B-frame stream tick writes the flows of B pairs
-        total += flow_bytes * (size_t)(B - 1);
-        flow_stride.push_back(flow_bytes);
-    }
-    std::vector<size_t> off_patch[kSets];
-    std::vector<size_t> off_pscr; // (per level; slot i, frame f at + (F i + f) * pscr_frame, F = frames per slot)
-    size_t pscr_frame = 0;
-    size_t patch_bytes[OFX_MAX_LEVELS] = {};
-    if (p->local_corner || p->stream_two_stage) {
-        const int step = 1 << (p->levels - 1);
-        int side = p->patch_size > 0 ? p->patch_size : step * ((p->window >> 1) + 2 + 8);
-        if (p->patch_size <= 0 && side < 256) side = 256;
-        side = (int)align_up((size_t)side, (size_t)step);
-        const int pw0 = side < p->width ? side : p->width, ph0 = side < p->height ? side : p->height;
-        for (int k = 0; k < p->levels; ++k) {
-            s->pw[k] = pw0 >> k;
-            s->ph[k] = ph0 >> k;
-            s->ppitch[k] = (int)align_up((size_t)s->pw[k], 64);
-            patch_bytes[k] = align_up((size_t)s->ppitch[k] * (size_t)s->ph[k] + 64, kAlign);
-        }
-        const int need = (p->window >> 1) + 2;
-        const int lc = p->levels - 1;
-        if (s->pw[lc] < (need < s->w[lc] ? need : s->w[lc]) || s->ph[lc] < (need < s->h[lc] ? need : s->h[lc])) {
-            ofx_set_error("ofx_session_create: patch_size %d leaves %dx%d at the coarsest level, the corner needs %d", side, s->pw[lc],
-                          s->ph[lc], need);
-            delete s;
-            return OFX_E_INVALID;
-        }
-        // With the frames borrowed the whole next frame is at hand when the chain runs: a shift that leaves the patch is repaired
-        // (ofx_corner_stage.d_patch_reloc) -- provided the patch leaves room at the coarsest level to be placed around any
-        // target (radius + 3 pixels of stencils + the plane's first column / row); a smaller patch (patch_size) keeps the
-        // status bit.
-        const int need_r = (p->window >> 1) + 5;
-        const bool room = (s->pw[lc] >= need_r || s->pw[lc] >= s->w[lc]) && (s->ph[lc] >= need_r || s->ph[lc] >= s->h[lc]);
-        s->repair = p->borrow_frames && !p->frames_partial && p->levels >= 3 && room;
-    }
-    if (s->repair) {
-        // Test hook: pretend the top-left patch planes are only this many level-0 pixels wide and high (never less than the
-        // corner itself), so that ordinary frames drive the chain into the relocated planes; the results must not change.
-        const char *e = getenv("OFX_DEBUG_CORNER_EXTENT");
-        s->debug_extent = e ? atoi(e) : 0;
-    }
-    const int frames_per_slot = (p->stream_two_stage ? 2 : 0) + (s->repair ? 1 : 0);
-    if (p->local_corner || p->stream_two_stage) {
-        for (int k = 0; k < p->levels; ++k) {
-            off_pscr.push_back(pscr_frame);
-            if (k >= 1) pscr_frame += patch_bytes[k];
-            if (p->stream_two_stage) continue; // no patch pyramids per image set: the corner blocks build what they read
-            for (int t = 0; t < n_sets; ++t) {
-                off_patch[t].push_back(total);
-                total += patch_bytes[k];
-            }
-        }
-        const size_t off_pscr_base = total;
-        total += pscr_frame * (size_t)frames_per_slot * (size_t)B;
-        for (size_t &o : off_pscr) o += off_pscr_base;
-    }
-    const size_t off_status = total; // the sticky word, then one word per shift-vector slot
-    total += align_up(sizeof(int) * (size_t)(1 + kUvSlots), kAlign);
-    const size_t off_uv = total;
-    total += align_up((size_t)OFX_MAX_LEVELS * 2 * sizeof(float) * kUvSlots, kAlign);
-    const size_t off_staging = total; // one 3-channel frame for ofx_session_set_frame_host_3ch (unsharded sessions only)
-    if (!p->sharded) total += align_up((size_t)p->width * (size_t)p->height * 3, kAlign);
-    // the second flow set of every pair slot, behind everything else: the first sets lie where they do without it
-    for (int k = 0; k < p->levels; ++k) {
-        off_flow_alt.push_back(total);
-        if (want_pairs) total += flow_stride[k] * (size_t)B;
-    }
-
-    hipError_t e = hipMalloc(&s->arena, total);
+    hipError_t e = hipMalloc(&s->arena, plan.total);
     if (e != hipSuccess) {
-        ofx_set_error("ofx_session_create: hipMalloc(%zu bytes): %s", total, hipGetErrorString(e));
-        delete s;
+        s->arena = nullptr;
+        ofx_set_error("ofx_session_create: hipMalloc(%zu bytes): %s", plan.total, hipGetErrorString(e));
         return OFX_E_HIP;
     }
-    s->arena_bytes = total;
-    e = hipMemset(s->arena, 0, total);
+    s->arena_bytes = plan.total;
+    e = hipMemset(s->arena, 0, plan.total);
     if (e != hipSuccess) {
         ofx_set_error("ofx_session_create: hipMemset: %s", hipGetErrorString(e));
-        (void)hipFree(s->arena);
-        delete s;
         return OFX_E_HIP;
     }
-    uint8_t *base = static_cast<uint8_t *>(s->arena);
-    for (int k = 0; k < p->levels; ++k) {
-        for (int t = 0; t < n_sets; ++t) s->img[t][k] = base + off_plane[t][k];
-        for (int t = 0; t < 2; ++t) s->sh[t][k] = base + off_plane[n_sets + t][k];
-        for (int t = 0; t < n_iter_sets; ++t) s->itsh[t / 3][t % 3][k] = base + off_plane[n_sets + 2 + t][k];
-        s->flowset[0][k] = reinterpret_cast<float *>(base + off_flow[k]);
-        for (int t = 1; t < kMaxBatch; ++t)
-            s->flowset[t][k] = reinterpret_cast<float *>(base + (t < p->stream_batch ? off_flow2[k] + (size_t)(t - 1) * flow_stride[k] : off_flow[k]));
-        s->flow[k] = s->flowset[0][k];
-        for (int t = 0; t < B && want_pairs; ++t) s->flowset2[t][k] = reinterpret_cast<float *>(base + off_flow_alt[k] + (size_t)t * flow_stride[k]);
-    }
-    if (p->local_corner && !p->stream_two_stage)
-        for (int k = 0; k < p->levels; ++k)
-            for (int t = 0; t < n_sets; ++t) s->pimg[t][k] = base + off_patch[t][k];
-    for (int i = 0; i < B && frames_per_slot > 0; ++i)
-        for (int k = 1; k < p->levels; ++k) {
-            uint8_t *slot = base + off_pscr[k] + (size_t)(frames_per_slot * i) * pscr_frame;
-            if (p->stream_two_stage) {
-                s->pscr[i][0][k] = slot;
-                s->pscr[i][1][k] = slot + pscr_frame;
-            }
-            if (s->repair) s->preloc[i][k] = slot + (size_t)(frames_per_slot - 1) * pscr_frame;
+    // every pointer of the session: base + its offset in the plan (null where the plan has none)
+    uint8_t *const base = static_cast<uint8_t *>(s->arena);
+    auto at = [base](size_t off) { return off == ofx_plan::kNoOffset ? nullptr : base + off; };
+    auto flt = [&at](size_t off) { return reinterpret_cast<float *>(at(off)); };
+    const ofx_plan::ArenaOffsets &o = plan.off;
+    for (int k = 0; k < plan.p.levels; ++k) {
+        for (int t = 0; t < kSets; ++t) s->img[t][k] = at(o.img[t][k]), s->pimg[t][k] = at(o.pimg[t][k]);
+        for (int t = 0; t < 2; ++t) s->sh[t][k] = at(o.sh[t][k]);
+        for (int t = 0; t < kMaxBatch; ++t) {
+            for (int j = 0; j < 3; ++j) s->itsh[t][j][k] = at(o.itsh[t][j][k]);
+            for (int f = 0; f < 2; ++f) s->pscr[t][f][k] = at(o.pscr[t][f][k]);
+            s->preloc[t][k] = at(o.preloc[t][k]);
+            s->flowset[t][k] = flt(o.flowset[t][k]);
+            s->flowset2[t][k] = flt(o.flowset2[t][k]);
         }
-    s->corner_status = reinterpret_cast<int *>(base + off_status);
+        s->flow[k] = s->flowset[0][k];
+    }
+    s->corner_status = reinterpret_cast<int *>(at(o.status));
     s->pair_status = s->corner_status + 1;
-    s->uv = reinterpret_cast<float *>(base + off_uv);
-    s->staging = p->sharded ? nullptr : base + off_staging;
-    // OFX_ITER_FUSED=0 keeps one ofx_warp_levels launch per refinement iteration
-    s->fused_iters = p->iters > 1 && [] { const char *e = getenv("OFX_ITER_FUSED"); return !e || atoi(e) != 0; }();
-    // the launches that also write the warped image run on 32-bit buffer offsets (lk_body_buf.h): a session whose level 0 reaches
-    // 2 GB of plane or of flow rows keeps the warp launch + the old accumulating march, as before round 3
-    if ((size_t)(s->buf1[0] - s->buf0[0]) * (size_t)s->pitch[0] >= ((size_t)1 << 31) ||
-        (size_t)(s->buf1[0] - s->buf0[0]) * (size_t)s->w[0] * 8 >= ((size_t)1 << 31))
-        s->fused_iters = false;
-    s->iter_pairs = want_pairs && s->fused_iters;
-    s->n_iter_pass = ofx_plan::iter_plan_make(p->iters, s->fused_iters, s->iter_pairs, s->iter_plan);
-    s->n_iter_pass1 = ofx_plan::iter_plan_make(p->iters, s->fused_iters, false, s->iter_plan1);
-    s->pair_opts.pack = [] { const char *e = getenv("OFX_PAIR_PACK"); return !e || atoi(e) != 0; }() ? 1 : 0;
-    s->pair_opts.waves = [] { const char *e = getenv("OFX_PAIR_WAVES"); return e && atoi(e) > 0 ? atoi(e) : 0; }();
-    s->pair_opts.cache = &s->pair_cache;
+    s->uv = flt(o.uv);
+    s->staging = at(o.staging);
+    // geometry and flags
+    s->p = plan.p;
+    s->n_sets = plan.n_sets;
+    for (int k = 0; k < plan.p.levels; ++k) {
+        const ofx_plan::LevelPlan &l = plan.lv[k];
+        s->w[k] = l.w, s->h[k] = l.h, s->pitch[k] = l.pitch;
+        s->own0[k] = l.own0, s->own1[k] = l.own1, s->buf0[k] = l.buf0, s->buf1[k] = l.buf1;
+        s->cmp0[k] = l.cmp0, s->cmp1[k] = l.cmp1, s->fl0[k] = l.fl0, s->fl1[k] = l.fl1;
+        s->pw[k] = l.pw, s->ph[k] = l.ph, s->ppitch[k] = l.ppitch;
+    }
+    s->repair = plan.repair;
+    s->debug_extent = plan.debug_extent;
+    s->fused_iters = plan.fused_iters;
+    s->iter_pairs = plan.iter_pairs;
+    s->n_iter_pass = ofx_plan::iter_plan_make(plan.p.iters, s->fused_iters, s->iter_pairs, s->iter_plan);
+    s->n_iter_pass1 = ofx_plan::iter_plan_make(plan.p.iters, s->fused_iters, false, s->iter_plan1);
+    s->pair_opts = ofx_pair_opts{plan.pair_pack, plan.pair_waves, &s->pair_cache};
     repoint(s);
-    *out = s;
+    *out = guard.release();
     return OFX_OK;
 }
 

@@ -3,7 +3,10 @@
 //
 // One hipMalloc arena holds, per pyramid level: the previous and the next frame's 1-channel planes, a scratch
 // plane for the shifted next frame, the flow field, and the 2-float shift vector.  Nothing is allocated or freed
-// while frames flow (the reference does 58 cudaMalloc/cudaFree calls per level).
+// while frames flow (the reference does 58 cudaMalloc/cudaFree calls per level).  What a session of given
+// ofx_params holds, which paths it takes and where in the arena every buffer lies is decided in session_plan.h (host code
+// without HIP; tools/session_plan_main.cpp prints it): ofx_session_create allocates the plan's total and points the fields
+// below at base + offset.
 #pragma once
 #include <stdlib.h>
 #include <string.h>
@@ -13,14 +16,13 @@
 #include "iter_plan.h"
 #include "ofx_internal.h"
 #include "out_ring.h"
+#include "session_plan.h"
 
-// The stream pipeline with B frames per tick uses 3B + 2 image sets and 2B shift-vector slots (see stream_tick); the
-// pair-at-a-time paths rotate 3 sets and alternate 2 slots.
-constexpr int kMaxBatch = OFX_STREAM_MAX_BATCH;
-constexpr int kSets = 3 * kMaxBatch + 2;
-constexpr int kUvSlots = 2 * kMaxBatch;
-constexpr size_t kAlign = 256; // of every plane and table in the arenas
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+using ofx_plan::align_up;
+using ofx_plan::kAlign;
+using ofx_plan::kMaxBatch;
+using ofx_plan::kSets;
+using ofx_plan::kUvSlots;
 
 struct ofx_session {
     ofx_params p{};
@@ -177,6 +179,5 @@ inline void shard_reach(const ofx_session *s, int (*rows)[4])
     }
 }
 
-inline int stream_batch_of(const ofx_session *s) { return s->p.stream_batch >= 2 ? s->p.stream_batch : 1; }
-// image sets the stream pipeline cycles through: (D + 1) B + 2 (stream_tick)
-inline int stream_sets(const ofx_session *s) { return (s->p.stream_two_stage ? 2 : 3) * stream_batch_of(s) + 2; }
+inline int stream_batch_of(const ofx_session *s) { return ofx_plan::stream_batch_of(s->p); }
+inline int stream_sets(const ofx_session *s) { return ofx_plan::stream_sets(s->p); }

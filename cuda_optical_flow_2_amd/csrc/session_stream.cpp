@@ -566,7 +566,7 @@ extern "C" int ofx_session_stream_frontend(ofx_session *s, int mode, int window,
     OFX_TRY(ofx_frontend_tables_make(mode == OFX_FRONTEND_BILATERAL ? window : 0, sigma_s, sigma_b, &t));
     if (s->p.borrow_frames && !s->fe_arena) {
         // one plane per image set at the level-0 pitch, plus the three readable bytes the fused warp may fetch past level 0
-        const size_t plane = align_up((size_t)s->pitch[0] * (size_t)s->h[0] + 64, kAlign);
+        const size_t plane = ofx_plan::plane_bytes(s->pitch[0], s->h[0]);
         const hipError_t e = hipMalloc(&s->fe_arena, plane * (size_t)s->n_sets);
         if (e != hipSuccess) {
             ofx_frontend_tables_free(t);

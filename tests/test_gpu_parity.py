@@ -12,6 +12,7 @@ import pytest
 
 from conftest import assert_flow_close, assert_same
 from cuda_optical_flow_2_amd import synth
+from stream_helpers import plain_sequence as _plain_sequence, stream_all_pairs as _stream_all_pairs
 
 pytestmark = pytest.mark.gpu
 
@@ -776,47 +777,6 @@ def test_partial_frames_report_a_shift_that_leaves_the_patch_instead_of_repairin
             assert got_bits & ((1 << L) - 1) == want_bits, (d, r, hex(got_bits), hex(want_bits))
         seen_miss = seen_miss or want_bits != 0
     assert seen_miss, "no brightness step drove the corner shift out of the patch: the test lost its subject"
-
-
-def _plain_sequence(eng, frames, w, h, L, win, mode="lk_float"):
-    """flows of every pair of `frames` through the plain pair-at-a-time session (the sequence the oracle tests pin)"""
-    import torch
-
-    plain = eng.Session(w, h, L, win, mode)
-    plain.set_frame_device(frames[0]); plain.build_pyramid(); plain.swap()
-    want = {}
-    for i in range(1, len(frames)):
-        plain.set_frame_device(frames[i]); plain.build_pyramid(); plain.run_flow()
-        torch.cuda.synchronize()
-        want[i] = [plain.flow_host(k) for k in range(L)]
-        plain.swap()
-    plain.close()
-    return want
-
-
-def _stream_all_pairs(s, frames, L, B):
-    """every pair of `frames` through the stream pipeline of session s; returns {pair: [flow per level]} (host copies)"""
-    import torch
-
-    got, seen = {}, 0
-
-    def snap(done):
-        nonlocal seen
-        if done >= 1:
-            for p in range(max(seen + 1, done - B + 1), done + 1):
-                got[p] = [s.flow_of(p, k)[0].cpu().numpy() for k in range(L)]
-            seen = done
-
-    s.stream_begin()
-    for f in frames:
-        snap(s.stream_submit(f))
-    while True:
-        done = s.stream_drain()
-        if done == -2:
-            break
-        snap(done)
-    torch.cuda.synchronize()
-    return got
 
 
 @pytest.mark.parametrize("cfg", [(1280, 720, 4, 9, "lk_float", 4, True), (1000, 564, 3, 7, "lk_float", 2, False), (640, 480, 3, 5, "compat_cpu", 4, True),
