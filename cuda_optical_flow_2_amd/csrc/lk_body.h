@@ -4,6 +4,7 @@
 
 #include <type_traits>
 
+#include "lk_plan.h"
 #include "lk_solve.h"
 #include "ofx_internal.h"
 
@@ -964,8 +965,8 @@ namespace ofx_dev {
 // One wave of the fused level kernel: picks the variant for its tile (wave-uniform: two complete copies of the march, nothing
 // merges after them).
 // LDS_ROWS: xlds holds kLkWaveLdsDma bytes and the march fetches its rows through LDS (lk_body_buf.h, DMA)
-// ITER: lk_wave_buf's (0, or 3 = also write the warped image of the pair's second iteration); buffer march only
-template <int R, int MODE, bool SUMS, bool MAY_ACC = true, bool FAST = false, bool LDS_ROWS = false, int ITER = 0>
+// ITER: lk_wave_buf's (lk_plan.h; the tick's kIterSet, kIterSetWarp or kIterSetWarpRows); buffer march only
+template <int R, int MODE, bool SUMS, bool MAY_ACC = true, bool FAST = false, bool LDS_ROWS = false, int ITER = ofx_plan::kIterSet>
 __device__ __forceinline__ void lk_wave(const LkTable &T, int wave, int lane, uint8_t *xlds)
 {
     if (wave >= T.first_block[T.n]) return;

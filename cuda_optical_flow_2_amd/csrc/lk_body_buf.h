@@ -49,18 +49,13 @@ constexpr int kLkWaveLdsDma = kLkWaveLdsX + 2 * kLkDmaSetBytes; // the exchange 
 // (the host sizes the dynamic LDS and asks for the occupancy with these)
 static_assert(kLkWaveLdsX == 2 * 2176 && kLkWaveLdsDma == 2 * 2176 + 2 * 1536, "LDS per wave of the buffer march");
 
-// ITER (refinement iterations of lk_iter): 0 = flow = result (the reference's level); 1 = flow += result,
-// the row's old flow fetched through the flow's own resource with the step's rows; 2 = the same, and the march also writes the
-// warped image the NEXT iteration reads (lk_body_warp.h): the row's new flow is in registers after the add, the warp's first stage
-// runs there and issues its tap loads, the second stage and the row's store follow one step later (whole levels only: lk_level.hip);
-// 3 = iteration 1 of a pair that has more: flow = result, and the warped image of iteration 2;
-// 4 / 5 = 2 / 3 on the row window of a shard: the planes hold rows [row0, row_end) only, a tap row outside them is reported.
-template <int R, int MODE, bool FAST, bool INTERIOR, bool DMA, int ITER = 0>
+// ITER: what the march does with a row's result (lk_plan.h: kIterSet .. kIterSetWarpRows)
+template <int R, int MODE, bool FAST, bool INTERIOR, bool DMA, int ITER = ofx_plan::kIterSet>
 __device__ __forceinline__ void lk_wave_buf(const LkTable &T, int wave, int lane, uint8_t *xlds)
 {
     using G = TileGeom<R>;
     constexpr int NS = 2 * R + 1;
-    constexpr bool ACC = ITER == 1 || ITER == 2 || ITER == 4, WOUT = ITER >= 2, ROWWIN = ITER >= 4;
+    constexpr bool ACC = ofx_plan::iter_adds(ITER), WOUT = ofx_plan::iter_warps(ITER), ROWWIN = ofx_plan::iter_row_window(ITER);
     constexpr bool DEFER = ACC; // the deferred flow store (above)
 
     if (wave >= T.first_block[T.n]) return;

@@ -24,10 +24,12 @@ int levels(int radius, const LkLevelIn *lv, int n, bool sums, hipStream_t st)
 }
 
 template <int MODE, bool FAST, int ITER>
-int iter(int radius, const LkLevelIn *lv, int n, hipStream_t st)
+int iter(int radius, const LkLevelIn *lv, int n, bool deep, hipStream_t st)
 {
     int rc = OFX_E_UNSUPPORTED;
-    const bool known = dispatch_radius<lk_max_radius(MODE)>(radius, [&](auto R) { rc = launch_iter_r<decltype(R)::value, MODE, FAST, ITER>(lv, n, st); });
+    const bool known = dispatch_radius<lk_max_radius(MODE)>(radius, [&](auto R) {
+        rc = deep ? launch_iter_r<decltype(R)::value, MODE, FAST, ITER, true>(lv, n, st) : launch_iter_r<decltype(R)::value, MODE, FAST, ITER, false>(lv, n, st);
+    });
     if (!known) ofx_set_error("ofx_lk_level: window %d not supported in mode %d", 2 * radius + 1, MODE);
     return rc;
 }
@@ -42,10 +44,18 @@ int iter_pair(int radius, const LkLevelIn *lv, int n, const ofx_pair_opts *opts,
 }
 
 template <int MODE, bool FAST, int WOUT>
-int stream(int radius, const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st)
+int stream(int radius, const LkLevelIn *lv, int n, bool deep, bool many, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st)
 {
     int rc = OFX_E_UNSUPPORTED;
-    const bool known = dispatch_radius<lk_max_radius(MODE)>(radius, [&](auto R) { rc = launch_stream_r<decltype(R)::value, MODE, FAST, WOUT>(lv, n, S, stage_blocks, lds, st); });
+    const bool known = dispatch_radius<lk_max_radius(MODE)>(radius, [&](auto R) {
+        if constexpr (WOUT == ofx_plan::kIterSet) { // (the ticks that write warped images have no deep-fetch kernels)
+            if (deep) {
+                rc = launch_stream_r<decltype(R)::value, MODE, FAST, true, WOUT>(lv, n, many, S, stage_blocks, lds, st);
+                return;
+            }
+        }
+        rc = launch_stream_r<decltype(R)::value, MODE, FAST, false, WOUT>(lv, n, many, S, stage_blocks, lds, st);
+    });
     if (!known) ofx_set_error("ofx_stream_launch: window %d not supported in mode %d", 2 * radius + 1, MODE);
     return rc;
 }

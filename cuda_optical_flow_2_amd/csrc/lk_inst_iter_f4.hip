@@ -2,4 +2,4 @@
 // (an accumulating launch that also writes the next warped image, on the row windows of a shard).
 #include "lk_inst.h"
 
-template int ofx_launch::iter<OFX_MODE_LK_FLOAT, false, 4>(int, const LkLevelIn *, int, hipStream_t);
+template int ofx_launch::iter<OFX_MODE_LK_FLOAT, false, 4>(int, const LkLevelIn *, int, bool, hipStream_t);

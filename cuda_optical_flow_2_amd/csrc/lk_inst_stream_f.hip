@@ -1,4 +1,4 @@
 // One family of instantiations of the templates in lk_launch.h (see there).
 #include "lk_inst.h"
 
-template int ofx_launch::stream<OFX_MODE_LK_FLOAT, false>(int, const LkLevelIn *, int, StreamArgs &, const int *, size_t, hipStream_t);
+template int ofx_launch::stream<OFX_MODE_LK_FLOAT, false>(int, const LkLevelIn *, int, bool, bool, StreamArgs &, const int *, size_t, hipStream_t);

@@ -5,13 +5,12 @@
 #pragma once
 
 #include <stdio.h>
-#include <stdlib.h>
 
 #include "corner_body.h"
 #include "lk_body.h"
+#include "lk_plan.h"
 #include "pair_plan.h"
 #include "pyr_march.h"
-#include "session_plan.h"
 #include "stages_body.h"
 
 using namespace ofx_dev;
@@ -30,7 +29,7 @@ struct StreamArgs {
     PatchBuildSlot patch_slot[OFX_STREAM_MAX_BATCH];
     // blocks [0, OFX_STREAM_MAX_BATCH) = one corner wave each; [.., first[0]) LK (four waves per block);
     // [first[i], first[i+1]) pyramid stage i (four marching waves per block, pyr_march.h).
-    // The LK blocks come first and are planned for a whole number of waves per SIMD (lk_wave_target): they all start at
+    // The LK blocks come first and are planned for a whole number of waves per SIMD (lk_wave_capacity): they all start at
     // once and run for the whole launch, while the short staging blocks stream through the remaining slots underneath.
     int first[kPyrStages + 1];
     int n_corner;
@@ -38,8 +37,7 @@ struct StreamArgs {
     int trace_blocks;
 };
 struct LkLevelIn {
-    LkArgs a;     // everything but strip_h / tiles_x
-    int rows_out;
+    LkArgs a; // everything but strip_h / tiles_x, which the plan fills in (plan_table_g)
 };
 using ofx_plan::kPairMaxSegs;
 using ofx_plan::PairSeg;
@@ -50,7 +48,12 @@ struct PairPlanDev {
     const PairSeg *segs;
     int waves;
 };
-int pair_plan_get(ofx_pair_cache **cache, int radius, int out_w, const LkLevelIn *lv, int n, int capacity, PairPlanDev *out);
+int pair_plan_get(ofx_pair_cache **cache, int radius, int out_w, const LkLevelIn *lv, int n, int min_h, int capacity, PairPlanDev *out);
+ofx_plan::LkSwitches lk_switches(); // the environment's (lk_level.hip)
+inline ofx_plan::LkItem lk_item(const LkArgs &a)
+{
+    return ofx_plan::LkItem{a.w, a.h, a.pitch, a.row0, a.row_end, a.out_y0, a.out_y1, a.flow_row0, a.accumulate, a.warp_out != nullptr};
+}
 } // namespace ofx_launch
 
 namespace {
@@ -65,9 +68,8 @@ __global__ __launch_bounds__(64, kLkMinWaves) void lk_level_kernel(const LkTable
     lk_wave<R, MODE, SUMS, true, FAST>(T, (int)blockIdx.x, (int)threadIdx.x, xlds);
 }
 
-// A refinement iteration of lk_iter on the buffer march (lk_body_buf.h): ITER = 1 adds to the flow, ITER = 2 also writes the warped
-// image of the next iteration (lk_body_warp.h).
-// ITER = 2 needs 126 VGPRs in interior tiles and 130 in the tiles at the image's left and right edge (128 for 9x9: four waves per
+// A refinement iteration of lk_iter on the buffer march (lk_body_buf.h; ITER: lk_plan.h).
+// kIterAddWarp needs 126 VGPRs in interior tiles and 130 in the tiles at the image's left and right edge (128 for 9x9: four waves per
 // SIMD, three for the other windows).  Capping it at 128 everywhere spills 2-8 registers and measured 1-3 % slower at 1080p, 4K
 // and 8K (profiles/r03_ablation.txt), so the cap stays at three waves.
 // DMA: the rows are fetched two steps ahead through LDS (lk_body_buf.h; chosen per launch as for the stream kernel)
@@ -165,18 +167,16 @@ namespace ofx_launch { // shared by the translation units that instantiate the k
 extern unsigned long long *g_stream_trace; // tools/stream_timeline.py
 extern int g_stream_trace_blocks;
 extern int g_trace_header[2 * OFX_STREAM_MAX_BATCH + 1];
-extern thread_local int g_stream_deep_fetch; // ofx_stream_stages.deep_fetch of the launch being dispatched (set by ofx_stream_launch)
 } // namespace ofx_launch
 namespace {
 using ofx_launch::g_stream_trace;
 using ofx_launch::g_stream_trace_blocks;
 using ofx_launch::g_trace_header;
-using ofx_launch::g_stream_deep_fetch;
 
 constexpr int kPyrPrio = 3; // priority of the marching-pyramid waves next to the LK waves (which go 3 -> 0 along their strips)
-// DMA: the LK stage fetches its rows two steps ahead through LDS (lk_body_buf.h); chosen per launch by launch_stream_r
-// WOUT: the LK stage is iteration 1 of pairs that have more (lk_iter): it also writes the warped images of their second iteration
-// (lk_body_buf.h, ITER = WOUT = 3, or 5 on the row windows of a shard; ~128 VGPRs: three blocks per CU at least); 0: it does not
+// DMA: the LK stage fetches its rows two steps ahead through LDS (lk_body_buf.h); chosen per launch (lk_plan.h: lk_tick_variant)
+// WOUT: the LK stage's ITER (lk_plan.h): kIterSet, or kIterSetWarp / kIterSetWarpRows where it is iteration 1 of pairs that have more
+// and also writes the warped images of their second iteration (~128 VGPRs: three blocks per CU at least)
 // blocks per CU: lk_float fits 5 (<= 96 VGPRs) without scratch for every radius; compat_cpu needs ~120: 4 blocks (<= 128)
 constexpr int stream_min_blocks(int mode, int wout)
 {
@@ -225,130 +225,83 @@ __global__ __launch_bounds__(256, stream_min_blocks(MODE, WOUT)) void stream_ker
 // ---- host side ----------------------------------------------------------------------------------------------------
 using ofx_launch::LkLevelIn;
 
-int env_int(const char *name, int dflt)
-{
-    const char *e = getenv(name);
-    return e && atoi(e) > 0 ? atoi(e) : dflt;
-}
-
-// One strip height for all levels (so all waves run about equally long): the smallest that keeps the wave count within
-// `capacity` (lk_wave_target), but at least `min_h` so the 2R priming rows of a strip stay a minor cost.
-// The grid is sized to fit in ONE residency round: every wave runs for the whole kernel, so a second, partly filled
-// round would nearly double the run time.
-// G: the tile's geometry (its OUT_W; TileGeom<R> or TileGeomP<R>)
+// The launch's table: the items' LkArgs with the strips of the plan (lk_plan.h: lk_strips).  G: the tile's geometry (its OUT_W;
+// TileGeom<R> or TileGeomP<R>).  Returns the wave count.
 template <typename G>
-int plan_table_g(const LkLevelIn *lv, int n, int capacity, LkTable *out)
+int plan_table_g(const LkLevelIn *lv, int n, int min_h, int capacity, LkTable *out)
 {
-    const int min_h = env_int("OFX_LK_MIN_STRIP", 8);
-    int max_rows = 1;
-    for (int i = 0; i < n; ++i) max_rows = lv[i].rows_out > max_rows ? lv[i].rows_out : max_rows;
-    auto height = [&](int i, int H) {
-        const int hi = H < min_h ? min_h : H;
-        return hi < lv[i].rows_out ? hi : lv[i].rows_out;
-    };
-    auto item_waves = [&](int i, int H) { return (long)ofx_div_up(lv[i].a.w, G::OUT_W) * ofx_div_up(lv[i].rows_out, height(i, H)); };
-    int strip_h = min_h;
-    for (; strip_h < max_rows; ++strip_h) {
-        long waves = 0;
-        for (int i = 0; i < n; ++i) waves += item_waves(i, strip_h);
-        if (waves <= (long)capacity) break;
-    }
+    ofx_plan::LkItem items[OFX_MAX_LK_ITEMS];
+    for (int i = 0; i < n; ++i) items[i] = ofx_launch::lk_item(lv[i].a);
+    ofx_plan::LkStrips s;
+    ofx_plan::lk_strips(items, n, G::OUT_W, min_h, capacity, &s);
     LkTable t{};
     t.n = n;
-    int blocks = 0;
     for (int i = 0; i < n; ++i) {
         t.lv[i] = lv[i].a;
-        t.lv[i].tiles_x = ofx_div_up(lv[i].a.w, G::OUT_W);
-        t.lv[i].strip_h = height(i, strip_h);
-        t.first_block[i] = blocks;
-        blocks += t.lv[i].tiles_x * ofx_div_up(lv[i].rows_out, t.lv[i].strip_h);
+        t.lv[i].tiles_x = s.tiles_x[i];
+        t.lv[i].strip_h = s.strip_h[i];
+        t.first_block[i] = s.first_block[i];
     }
-    t.first_block[n] = blocks;
+    t.first_block[n] = s.blocks;
     *out = t;
-    return blocks;
+    return s.blocks;
 }
 
-template <int R>
-int plan_table(const LkLevelIn *lv, int n, int capacity, LkTable *out)
-{
-    return plan_table_g<TileGeom<R>>(lv, n, capacity, out);
-}
-
-// Number of LK waves a launch is planned for.  Every LK wave runs for the whole launch, so what matters is how many of
-// them share a SIMD: fewer leave issue slots empty, more shorten the strips (each strip pays its priming rows), and a count
-// that is not a whole number per SIMD makes the fuller SIMDs set the time.  Measured on MI355X (one 4K pair, 9x9): with 2R
-// priming steps per strip 3 per SIMD was the optimum; with the folded priming (R + 1 steps, lk_body.h) it is 4 -- 48.9 /
-// 42.0 / 40.4 / 41.6 us at 2 / 3 / 4 / 5.  `reserve` slots per SIMD are left to the other
-// stages of the stream kernel.
-// `full_fill`: per cent of the slots a plan that needs every slot may use.
+// What lk_wave_capacity (lk_plan.h) needs to know of the device: its CUs, and the waves of `kernel` a SIMD holds.  Asked once per
+// kernel instantiation.
+struct LkDevice {
+    int cus, occ;
+};
 template <typename K>
-int lk_wave_target(K kernel, int threads, size_t lds, int reserve, int dflt_per_simd, int full_fill = 95)
+LkDevice lk_device(K kernel, int threads, size_t lds)
 {
     int dev = 0, cus = 256, per_cu = 0;
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds) != hipSuccess || per_cu <= 0) per_cu = 8 * 64 / threads;
     (void)hipGetLastError();
-    const int occ = per_cu * (threads / 64) / 4; // waves per SIMD (4 SIMDs per CU)
-    int per_simd = env_int("OFX_LK_WAVES_PER_SIMD", dflt_per_simd);
-    if (per_simd > occ - reserve) per_simd = occ - reserve;
-    if (per_simd < 1) per_simd = 1;
-    // with wave slots to spare the plan may use the whole target (an uneven placement still fits in one round); a plan
-    // that needs every slot keeps 5 % back, because a second, mostly empty round would double the run time
-    const int fill = env_int("OFX_LK_FILL", per_simd < occ ? 100 : full_fill);
-    return env_int("OFX_LK_TARGET_WAVES", (int)((long)cus * 4 * per_simd * fill / 100));
+    return LkDevice{cus, per_cu * (threads / 64) / 4}; // (4 SIMDs per CU)
 }
 
 template <int R, int MODE, bool SUMS, bool FAST>
 int launch_r(const LkLevelIn *lv, int n, hipStream_t st)
 {
-    static const int capacity = lk_wave_target(lk_level_kernel<R, MODE, SUMS, FAST>, 64, 0, 0, 4);
+    static const LkDevice dev = lk_device(lk_level_kernel<R, MODE, SUMS, FAST>, 64, 0);
+    const ofx_plan::LkSwitches sw = ofx_launch::lk_switches();
     LkTable t{};
-    const int blocks = plan_table<R>(lv, n, capacity, &t);
+    const int blocks = plan_table_g<TileGeom<R>>(lv, n, sw.min_strip, ofx_plan::lk_wave_capacity(dev.cus, dev.occ, 0, ofx_plan::kLkWavesPerSimd, ofx_plan::kLkFullFill, sw), &t);
     hipLaunchKernelGGL((lk_level_kernel<R, MODE, SUMS, FAST>), dim3((unsigned)blocks), dim3(64), 0, st, t);
     OFX_HIP(hipGetLastError());
     return OFX_OK;
 }
 
 template <int R, int MODE, bool FAST, int ITER, bool DMA>
-int launch_iter_rd(const LkLevelIn *lv, int n, hipStream_t st)
+int launch_iter_r(const LkLevelIn *lv, int n, hipStream_t st)
 {
-    static const int capacity = lk_wave_target(lk_iter_kernel<R, MODE, FAST, ITER, DMA>, 64, 0, 0, 4);
+    static const LkDevice dev = lk_device(lk_iter_kernel<R, MODE, FAST, ITER, DMA>, 64, 0);
+    const ofx_plan::LkSwitches sw = ofx_launch::lk_switches();
     LkTable t{};
-    const int blocks = plan_table<R>(lv, n, capacity, &t);
+    const int blocks = plan_table_g<TileGeom<R>>(lv, n, sw.min_strip, ofx_plan::lk_wave_capacity(dev.cus, dev.occ, 0, ofx_plan::kLkWavesPerSimd, ofx_plan::kLkFullFill, sw), &t);
     hipLaunchKernelGGL((lk_iter_kernel<R, MODE, FAST, ITER, DMA>), dim3((unsigned)blocks), dim3(64), 0, st, t);
     OFX_HIP(hipGetLastError());
     return OFX_OK;
 }
 
-template <int R, int MODE, bool FAST, int ITER>
-int launch_iter_r(const LkLevelIn *lv, int n, hipStream_t st)
-{
-    // the deep fetch, chosen as for the stream kernel (8K, 10 iterations: 15 380 vs 15 110 Mpix/s; 4K: no difference beyond the
-    // +-1.5 % between runs -- profiles/r03_ablation.txt).  OFX_ITER_DMA=0 / 1 overrides.
-    static const int forced = [] { const char *e = getenv("OFX_ITER_DMA"); return e ? atoi(e) : -1; }();
-    long max_px = 0;
-    for (int i = 0; i < n; ++i) max_px = (long)lv[i].a.w * lv[i].a.h > max_px ? (long)lv[i].a.w * lv[i].a.h : max_px;
-    if (forced > 0 || (forced < 0 && ofx_plan::deep_fetch_by_size(max_px))) return launch_iter_rd<R, MODE, FAST, ITER, true>(lv, n, st);
-    return launch_iter_rd<R, MODE, FAST, ITER, false>(lv, n, st);
-}
-
-// two iterations per launch: two waves per SIMD (a launch carries the work of two, so its strips are about twice as tall)
+// two iterations per launch (a launch carries the work of two, so its strips are about twice as tall)
 // opts (NULL: none): the caller's plan cache and switches.  With opts->pack the waves carry equal STEPS instead of one strip each
 // (pair_plan.h); opts->waves > 0 sets the wave count of that plan.
 template <int R, bool FAST, bool WOUT>
 int launch_pair_r(const LkLevelIn *lv, int n, const ofx_pair_opts *opts, hipStream_t st)
 {
-    // Every slot is planned for: at two waves per SIMD a SIMD that gets one wave idles half the launch while the full ones set its
-    // time -- measured at 4K, 9x9: 1 945 waves (95 %) 2.137 ms per tick, 2 048 waves 1.992, 1 800 waves 2.463 (the block is one
-    // wave of 19.1 KB: eight fit every CU, so a plan of cus x 8 waves still runs in one round)
-    static const int capacity = lk_wave_target(lk_pair_kernel<R, FAST, WOUT>, 64, 0, 0, 2, 100);
+    static const LkDevice dev = lk_device(lk_pair_kernel<R, FAST, WOUT>, 64, 0);
+    const ofx_plan::LkSwitches sw = ofx_launch::lk_switches();
+    const int capacity = ofx_plan::lk_wave_capacity(dev.cus, dev.occ, 0, ofx_plan::kPairWavesPerSimd, ofx_plan::kPairFullFill, sw);
     LkTable t{};
-    int blocks = plan_table_g<TileGeomP<R>>(lv, n, capacity, &t);
+    int blocks = plan_table_g<TileGeomP<R>>(lv, n, sw.min_strip, capacity, &t);
     ofx_launch::PairPlanDev plan{nullptr, 0};
     if (opts && opts->pack && opts->cache) {
         const int want = opts->waves > 0 && opts->waves < capacity ? opts->waves : capacity;
-        OFX_TRY(ofx_launch::pair_plan_get(opts->cache, R, TileGeomP<R>::OUT_W, lv, n, want, &plan));
+        OFX_TRY(ofx_launch::pair_plan_get(opts->cache, R, TileGeomP<R>::OUT_W, lv, n, sw.min_strip, want, &plan));
         if (plan.segs) blocks = plan.waves;
     }
     hipLaunchKernelGGL((lk_pair_kernel<R, FAST, WOUT>), dim3((unsigned)blocks), dim3(64), 0, st, t, plan.segs);
@@ -356,23 +309,16 @@ int launch_pair_r(const LkLevelIn *lv, int n, const ofx_pair_opts *opts, hipStre
     return OFX_OK;
 }
 
-// Deep fetch (DMA = true) pays where a step's row loads come from HBM -- measured on MI355X (profiles/r03_ablation.txt): 8K,
-// two frames per launch: 279 vs 295 us (-5 %); 4K with its frames in the Infinity Cache: 247 vs 237 us (+4 %: the form costs
-// ~60 more scalar instructions per step, and the loads are short there) -- so it is chosen by the size of the largest level:
-// planes of 16 Mpx and more do not stay cached between their two uses.  OFX_LK_DMA=0 / 1 overrides.
+// many: the tick carries two pairs or more (lk_plan.h: lk_tick_variant)
 template <int R, int MODE, bool FAST, bool DMA, int WOUT>
-int launch_stream_rd(const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st)
+int launch_stream_r(const LkLevelIn *lv, int n, bool many, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st)
 {
     constexpr size_t wave_lds = DMA ? kLkWaveLdsDma : kLkWaveLdsX;
-    // Next to the staging blocks the LK stage does best with 2 waves per SIMD when the tick carries one pair and 4 when it
-    // carries more (measured, 4K: one pair 58.2 / 59.8 us per frame at 2 / 3; two pairs 59.7 / 57.2 / 56.5 at 2 / 3 / 4)
-    static const int capacity1 = lk_wave_target(stream_kernel<R, MODE, FAST, DMA, WOUT>, 256, 4 * wave_lds, 1, 2);
-    static const int capacity2 = lk_wave_target(stream_kernel<R, MODE, FAST, DMA, WOUT>, 256, 4 * wave_lds, 1, 4);
-    int pairs = 0;
-    for (int i = 0; i < n; ++i) pairs += (lv[i].a.w == lv[0].a.w && lv[i].a.h == lv[0].a.h) ? 1 : 0;
-    const int capacity = pairs >= 2 ? capacity2 : capacity1;
+    static const LkDevice dev = lk_device(stream_kernel<R, MODE, FAST, DMA, WOUT>, 256, 4 * wave_lds);
+    const ofx_plan::LkSwitches sw = ofx_launch::lk_switches();
+    const int capacity = ofx_plan::lk_wave_capacity(dev.cus, dev.occ, ofx_plan::kTickReserve, ofx_plan::tick_waves_per_simd(many), ofx_plan::kLkFullFill, sw);
     int lk_blocks = 0;
-    if (n > 0) lk_blocks = ofx_div_up(plan_table<R>(lv, n, capacity, &S.lk), 4);
+    if (n > 0) lk_blocks = ofx_div_up(plan_table_g<TileGeom<R>>(lv, n, sw.min_strip, capacity, &S.lk), 4);
     S.first[0] = OFX_STREAM_MAX_BATCH + lk_blocks;
     for (int i = 0; i < kPyrStages; ++i) S.first[i + 1] = S.first[i] + stage_blocks[i];
     const int blocks = S.first[kPyrStages];
@@ -392,22 +338,6 @@ int launch_stream_rd(const LkLevelIn *lv, int n, StreamArgs &S, const int *stage
     return OFX_OK;
 }
 
-template <int R, int MODE, bool FAST, int WOUT>
-int launch_stream_r(const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st)
-{
-    if constexpr (!WOUT) { // (a tick that also writes warped images measured slower with it: 8K 440 vs 416 us)
-        static const int forced = [] { const char *e = getenv("OFX_LK_DMA"); return e ? atoi(e) : -1; }();
-        long max_px = 0;
-        for (int i = 0; i < n; ++i) max_px = (long)lv[i].a.w * lv[i].a.h > max_px ? (long)lv[i].a.w * lv[i].a.h : max_px;
-        // (round 4, second session: WHERE the rows come from decides, not the level's size as such -- a ring of 4K or 1080p frames
-        // longer than the Infinity Cache gains 5 % / 3.5 % with the deep fetch, a warm one loses 2 %: the caller can say which,
-        // ofx_params.deep_fetch)
-        const int want = forced >= 0 ? (forced > 0 ? 1 : -1) : g_stream_deep_fetch;
-        if (want > 0 || (want == 0 && ofx_plan::deep_fetch_by_size(max_px))) return launch_stream_rd<R, MODE, FAST, true, WOUT>(lv, n, S, stage_blocks, lds, st);
-    }
-    return launch_stream_rd<R, MODE, FAST, false, WOUT>(lv, n, S, stage_blocks, lds, st);
-}
-
 // Calls f(std::integral_constant<int, R>{}) for R = radius when 1 <= radius <= MAX_R (which instantiates f for every such R);
 // false: the radius is outside that range and f was not called.
 template <int MAX_R, int R = 1, typename F>
@@ -423,7 +353,7 @@ bool dispatch_radius(int radius, F &&f)
         return false;
     }
 }
-constexpr int lk_max_radius(int mode) { return mode == OFX_MODE_COMPAT_CPU ? 12 : 11; } // windows up to 23x23 / 25x25
+using ofx_plan::lk_max_radius;
 
 } // namespace
 
@@ -433,16 +363,14 @@ namespace ofx_launch {
 // all levels of a fused launch (sums: the inspection variant, which does not depend on the solve: FAST = false only)
 template <int MODE, bool FAST>
 int levels(int radius, const LkLevelIn *lv, int n, bool sums, hipStream_t st);
-// refinement iterations on the buffer march (lk_wave_buf's ITER): 1 flow += result; 2 the launch also writes the next iteration's
-// warped images; 3 iteration 1 of pairs that have more: flow = result and the warped images of iteration 2; 4: 2 on the row
-// windows of a shard
+// refinement iterations on the buffer march (ITER: lk_plan.h, kIterAdd .. kIterAddWarpRows); deep: with the deep fetch
 template <int MODE, bool FAST, int ITER>
-int iter(int radius, const LkLevelIn *lv, int n, hipStream_t st);
+int iter(int radius, const LkLevelIn *lv, int n, bool deep, hipStream_t st);
 // two refinement iterations per launch (lk_body_pair.h; radii 1..kLkPairMaxR, lk_float solves, whole levels): lv[i].a.flow_in is
 // the flow set read, .flow the one written; WOUT: the launch also writes the warped images of the iteration after its second
 template <bool FAST, bool WOUT>
 int iter_pair(int radius, const LkLevelIn *lv, int n, const ofx_pair_opts *opts, hipStream_t st);
-// one stream tick.  WOUT = 3: its LK stage also writes the warped images of its pairs' second iteration (5: on row windows)
-template <int MODE, bool FAST, int WOUT = 0>
-int stream(int radius, const LkLevelIn *lv, int n, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st);
+// one stream tick (WOUT, deep, many: lk_plan.h, lk_tick_variant; no deep fetch with WOUT)
+template <int MODE, bool FAST, int WOUT = ofx_plan::kIterSet>
+int stream(int radius, const LkLevelIn *lv, int n, bool deep, bool many, StreamArgs &S, const int *stage_blocks, size_t lds, hipStream_t st);
 } // namespace ofx_launch

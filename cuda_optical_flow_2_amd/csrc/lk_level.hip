@@ -22,19 +22,41 @@
 // Border semantics follow the reference exactly: image taps outside the image contribute nothing
 // (OptFlowCPU.cpp:98, OptFlowGpu.cu:1066-1075) and window taps outside the image are skipped
 // (OptFlowCPU.cpp:182-191) -- i.e. the image and the derivative planes are zero-extended.
+#include <stdlib.h>
 #include <string.h>
 
 #include <vector>
 
 #include "lk_launch.h"
 
-
 namespace ofx_launch {
 unsigned long long *g_stream_trace = nullptr; // tools/stream_timeline.py
 int g_stream_trace_blocks = 0;
 int g_trace_header[2 * OFX_STREAM_MAX_BATCH + 1] = {0};
-thread_local int g_stream_deep_fetch = 0;
 } // namespace ofx_launch
+
+static int env_int(const char *name, int dflt)
+{
+    const char *e = getenv(name);
+    return e && atoi(e) > 0 ? atoi(e) : dflt;
+}
+
+// OFX_LK_MIN_STRIP is read at every launch (the tests set it in mid-process), the others once per process.
+ofx_plan::LkSwitches ofx_launch::lk_switches()
+{
+    static const ofx_plan::LkSwitches once = [] {
+        ofx_plan::LkSwitches s;
+        if (const char *e = getenv("OFX_LK_DMA")) s.lk_dma = atoi(e);
+        if (const char *e = getenv("OFX_ITER_DMA")) s.iter_dma = atoi(e);
+        s.waves_per_simd = env_int("OFX_LK_WAVES_PER_SIMD", 0);
+        s.fill = env_int("OFX_LK_FILL", 0);
+        s.target_waves = env_int("OFX_LK_TARGET_WAVES", 0);
+        return s;
+    }();
+    ofx_plan::LkSwitches s = once;
+    s.min_strip = env_int("OFX_LK_MIN_STRIP", s.min_strip);
+    return s;
+}
 
 // ---- the packed plans of the fused two-iteration launch (pair_plan.h), on the device --------------------------------------------
 // A session sees a handful of launch shapes (a full tick, the partial ticks at its start and in the drain); each gets its plan the
@@ -56,7 +78,7 @@ void ofx_pair_cache_free(ofx_pair_cache *c)
     delete c;
 }
 
-int ofx_launch::pair_plan_get(ofx_pair_cache **cache, int radius, int out_w, const LkLevelIn *lv, int n, int capacity, PairPlanDev *out)
+int ofx_launch::pair_plan_get(ofx_pair_cache **cache, int radius, int out_w, const LkLevelIn *lv, int n, int min_h, int capacity, PairPlanDev *out)
 {
     std::vector<int> key{radius, out_w, capacity};
     for (int i = 0; i < n; ++i) key.push_back(lv[i].a.w), key.push_back(lv[i].a.h);
@@ -70,7 +92,7 @@ int ofx_launch::pair_plan_get(ofx_pair_cache **cache, int radius, int out_w, con
     for (int i = 0; i < n; ++i) items[i] = ofx_plan::PairItem{lv[i].a.w, lv[i].a.h};
     ofx_plan::PairPlan plan;
     ofx_pair_cache::Entry e{key, nullptr, 0};
-    const bool fits = ofx_plan::pair_plan_make(items.data(), n, out_w, pair_seg_steps(radius), env_int("OFX_LK_MIN_STRIP", 8), capacity, &plan);
+    const bool fits = ofx_plan::pair_plan_make(items.data(), n, out_w, pair_seg_steps(radius), min_h, capacity, &plan);
     if (fits) {
         const size_t bytes = plan.segs.size() * sizeof(PairSeg);
         OFX_HIP(hipMalloc(reinterpret_cast<void **>(&e.d_segs), bytes));
@@ -109,8 +131,7 @@ int lk_build_levels(const ofx_lk_desc *d, int n, int window, int mode, int32_t *
         OFX_REQUIRE(((uintptr_t)d[i].d_prev & 3) == 0 && ((uintptr_t)d[i].d_next & 3) == 0, "ofx_lk_level: planes must be 4-byte aligned");
         OFX_REQUIRE(d[i].flow_row0 <= g->out_y0, "ofx_lk_level: flow_row0 %d > out_y0 %d", d[i].flow_row0, g->out_y0);
         OFX_TRY(ofx_check_halo(g, radius + 1, "ofx_lk_level"));
-        const int rows_out = g->out_y1 - g->out_y0;
-        if (rows_out <= 0) continue;
+        if (g->out_y1 <= g->out_y0) continue;
         LkArgs a{};
         a.prev = d[i].d_prev;
         a.next = d[i].d_next;
@@ -143,23 +164,10 @@ int lk_build_levels(const ofx_lk_desc *d, int n, int window, int mode, int32_t *
             OFX_REQUIRE(a.warp_status == nullptr || (a.warp_status_bit >= 0 && a.warp_status_bit < 31), "ofx_lk_levels: bad warp_status_bit");
         }
         lv[m].a = a;
-        lv[m].rows_out = rows_out;
         ++m;
     }
     *count = m;
     return OFX_OK;
-}
-
-// The buffer march addresses a level's planes and its flow rows through buffer resources with 32-bit offsets (lk_body_buf.h)
-bool fits_buffer_offsets(const LkArgs &a)
-{
-    return ofx_plan::fits_buffer_offsets(a.row_end - a.row0, a.pitch, a.out_y1 - a.flow_row0, a.w);
-}
-bool fit_buffer_offsets(const LkLevelIn *lv, int m)
-{
-    for (int i = 0; i < m; ++i)
-        if (!fits_buffer_offsets(lv[i].a)) return false;
-    return true;
 }
 
 int lk_dispatch(const ofx_lk_desc *d, int n, int window, int mode, int32_t *d_sums, void *stream)
@@ -168,35 +176,31 @@ int lk_dispatch(const ofx_lk_desc *d, int n, int window, int mode, int32_t *d_su
     int m = 0;
     OFX_TRY(lk_build_levels(d, n, window, mode, d_sums, lv, &m));
     if (m == 0) return OFX_OK;
+    ofx_plan::LkItem items[OFX_MAX_LK_ITEMS];
+    for (int i = 0; i < m; ++i) items[i] = ofx_launch::lk_item(lv[i].a);
     const int radius = window >> 1;
-    hipStream_t st = ofx_stream(stream);
-    if ((lv[0].a.accumulate || lv[0].a.warp_out) && !d_sums) {
-        // refinement iterations run on the buffer march (32-bit offsets: levels below 2 GB; larger ones keep the old form, which
-        // cannot write the warped image)
-        const bool small = fit_buffer_offsets(lv, m);
-        const bool wout = lv[0].a.warp_out != nullptr;
-        OFX_REQUIRE(!wout || (small && mode != OFX_MODE_COMPAT_CPU), "ofx_lk_levels: d_warp_out needs mode lk_float and levels below 2 GB");
-        bool rowwin = false; // a shard's row window: the warp reports taps it cannot reach (ITER 4 / 5)
-        for (int i = 0; i < m; ++i) rowwin = rowwin || lv[i].a.row0 != 0 || lv[i].a.row_end != lv[i].a.h;
-        OFX_REQUIRE(!(wout && rowwin && !lv[0].a.accumulate), "ofx_lk_levels: iteration 1 with d_warp_out on a row window runs in the stream tick only");
-        const int iter = wout ? (lv[0].a.accumulate ? (rowwin ? 4 : 2) : 3) : 1; // (lk_wave_buf's ITER)
-        if (small && mode != OFX_MODE_COMPAT_CPU) { // (compat_cpu accumulates in the old form below)
-            auto run = [&](auto FAST) {
-                constexpr bool F = decltype(FAST)::value;
-                switch (iter) {
-                case 1: return ofx_launch::iter<OFX_MODE_LK_FLOAT, F, 1>(radius, lv, m, st);
-                case 2: return ofx_launch::iter<OFX_MODE_LK_FLOAT, F, 2>(radius, lv, m, st);
-                case 3: return ofx_launch::iter<OFX_MODE_LK_FLOAT, F, 3>(radius, lv, m, st);
-                default: return ofx_launch::iter<OFX_MODE_LK_FLOAT, F, 4>(radius, lv, m, st);
-                }
-            };
-            return mode == OFX_MODE_LK_FLOAT_FAST ? run(std::true_type{}) : run(std::false_type{});
-        }
+    ofx_plan::LkVariant v;
+    char err[160];
+    const int rc = ofx_plan::lk_levels_variant(items, m, radius, mode, d_sums != nullptr, ofx_launch::lk_switches(), &v, err, sizeof err);
+    if (rc != OFX_OK) {
+        ofx_set_error("%s", err);
+        return rc;
     }
-    const bool sums = d_sums != nullptr; // (the sums do not depend on the solve)
-    if (mode == OFX_MODE_COMPAT_CPU) return ofx_launch::levels<OFX_MODE_COMPAT_CPU, false>(radius, lv, m, sums, st);
-    if (mode == OFX_MODE_LK_FLOAT_FAST && !sums) return ofx_launch::levels<OFX_MODE_LK_FLOAT, true>(radius, lv, m, false, st);
-    return ofx_launch::levels<OFX_MODE_LK_FLOAT, false>(radius, lv, m, sums, st);
+    hipStream_t st = ofx_stream(stream);
+    if (v.family == ofx_plan::kLkLevels) {
+        if (v.mode == OFX_MODE_COMPAT_CPU) return ofx_launch::levels<OFX_MODE_COMPAT_CPU, false>(radius, lv, m, v.sums, st);
+        return v.fast ? ofx_launch::levels<OFX_MODE_LK_FLOAT, true>(radius, lv, m, false, st) : ofx_launch::levels<OFX_MODE_LK_FLOAT, false>(radius, lv, m, v.sums, st);
+    }
+    auto run = [&](auto FAST) {
+        constexpr bool F = decltype(FAST)::value;
+        switch (v.iter) {
+        case ofx_plan::kIterAdd: return ofx_launch::iter<OFX_MODE_LK_FLOAT, F, ofx_plan::kIterAdd>(radius, lv, m, v.deep, st);
+        case ofx_plan::kIterAddWarp: return ofx_launch::iter<OFX_MODE_LK_FLOAT, F, ofx_plan::kIterAddWarp>(radius, lv, m, v.deep, st);
+        case ofx_plan::kIterSetWarp: return ofx_launch::iter<OFX_MODE_LK_FLOAT, F, ofx_plan::kIterSetWarp>(radius, lv, m, v.deep, st);
+        default: return ofx_launch::iter<OFX_MODE_LK_FLOAT, F, ofx_plan::kIterAddWarpRows>(radius, lv, m, v.deep, st);
+        }
+    };
+    return v.fast ? run(std::true_type{}) : run(std::false_type{});
 }
 
 } // namespace
@@ -309,29 +313,28 @@ extern "C" int ofx_stream_launch(const ofx_stream_stages *g, int window, int mod
         OFX_TRY(lk_build_levels(g->lk, g->n_lk, window, mode, nullptr, lv, &m));
     }
     // the stream kernel's LK stage addresses planes and flow through buffer resources with 32-bit offsets (lk_body_buf.h)
+    ofx_plan::LkItem items[OFX_MAX_LK_ITEMS];
     for (int i = 0; i < m; ++i) {
-        const LkArgs &a = lv[i].a;
-        OFX_REQUIRE(fits_buffer_offsets(a),
+        items[i] = ofx_launch::lk_item(lv[i].a);
+        OFX_REQUIRE(ofx_plan::fits_buffer_offsets(items[i]),
                     "ofx_stream_launch: level %dx%d is too large for one launch item (planes and flow rows must stay below 2 GB: "
-                    "shard the level by rows)", a.w, a.h);
+                    "shard the level by rows)", items[i].w, items[i].h);
     }
     if (any == 0 && m == 0 && g->n_corner == 0) return OFX_OK;
     hipStream_t st = ofx_stream(stream);
     OFX_REQUIRE(g->deep_fetch >= -1 && g->deep_fetch <= 1, "ofx_stream_launch: deep_fetch must be -1, 0 or +1 (got %d)", g->deep_fetch);
-    ofx_launch::g_stream_deep_fetch = g->deep_fetch;
+    const ofx_plan::LkVariant v = ofx_plan::lk_tick_variant(items, m, mode, g->deep_fetch, ofx_launch::lk_switches());
     const int radius = window >> 1;
-    if (mode == OFX_MODE_COMPAT_CPU) return ofx_launch::stream<OFX_MODE_COMPAT_CPU, false>(radius, lv, m, S, stage_blocks, lds, st);
+    if (v.mode == OFX_MODE_COMPAT_CPU) return ofx_launch::stream<OFX_MODE_COMPAT_CPU, false>(radius, lv, m, v.deep, v.many, S, stage_blocks, lds, st);
     auto tick = [&](auto FAST) {
         constexpr bool F = decltype(FAST)::value;
-        if (m > 0 && lv[0].a.warp_out) { // the LK stage also writes the warped images of its pairs' second iteration (levels below 2 GB: checked above)
-            bool rw = false; // a shard's row windows
-            for (int i = 0; i < m; ++i) rw = rw || lv[i].a.row0 != 0 || lv[i].a.row_end != lv[i].a.h;
-            return rw ? ofx_launch::stream<OFX_MODE_LK_FLOAT, F, 5>(radius, lv, m, S, stage_blocks, lds, st)
-                      : ofx_launch::stream<OFX_MODE_LK_FLOAT, F, 3>(radius, lv, m, S, stage_blocks, lds, st);
+        switch (v.iter) { // (levels below 2 GB: checked above)
+        case ofx_plan::kIterSetWarp: return ofx_launch::stream<OFX_MODE_LK_FLOAT, F, ofx_plan::kIterSetWarp>(radius, lv, m, v.deep, v.many, S, stage_blocks, lds, st);
+        case ofx_plan::kIterSetWarpRows: return ofx_launch::stream<OFX_MODE_LK_FLOAT, F, ofx_plan::kIterSetWarpRows>(radius, lv, m, v.deep, v.many, S, stage_blocks, lds, st);
+        default: return ofx_launch::stream<OFX_MODE_LK_FLOAT, F>(radius, lv, m, v.deep, v.many, S, stage_blocks, lds, st);
         }
-        return ofx_launch::stream<OFX_MODE_LK_FLOAT, F>(radius, lv, m, S, stage_blocks, lds, st);
     };
-    return mode == OFX_MODE_LK_FLOAT_FAST ? tick(std::true_type{}) : tick(std::false_type{});
+    return v.fast ? tick(std::true_type{}) : tick(std::false_type{});
 }
 
 // Debug / measurement hook (tools/stream_timeline.py): with a device buffer of 8 * capacity_blocks uint64 set, every
@@ -371,7 +374,7 @@ int ofx_lk_levels_pair(const ofx_lk_desc *d, const float *const *d_flow_in, int 
         OFX_REQUIRE(a.accumulate && a.uv == nullptr && a.flow != nullptr && d_flow_in[i] != nullptr && d_flow_in[i] != a.flow && d[i].d_warp_src != nullptr,
                     "ofx_lk_levels_pair: needs accumulate, no d_uv, d_warp_src and two distinct flow buffers");
         OFX_REQUIRE(a.row0 == 0 && a.row_end == a.h && a.out_y0 == 0 && a.out_y1 == a.h && a.flow_row0 == 0, "ofx_lk_levels_pair: whole levels only");
-        OFX_REQUIRE(fits_buffer_offsets(a), "ofx_lk_levels_pair: levels must stay below 2 GB");
+        OFX_REQUIRE(ofx_plan::fits_buffer_offsets(ofx_launch::lk_item(a)), "ofx_lk_levels_pair: levels must stay below 2 GB");
         a.flow_in = d_flow_in[i];
         a.warp_src = d[i].d_warp_src;
         a.warp_scale = d[i].warp_scale;

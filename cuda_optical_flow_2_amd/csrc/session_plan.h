@@ -35,8 +35,9 @@ inline int stream_sets(const ofx_params &p) { return (p.stream_two_stage ? 2 : 3
 inline size_t plane_bytes(int pitch, int rows) { return align_up((size_t)pitch * (size_t)rows + 64, kAlign); }
 
 // Levels of 16 Mpx and more do not stay cached between their two uses: the LK launches fetch their rows two steps ahead through LDS
-// (lk_launch.h: launch_iter_r, launch_stream_r), and such a session's iterations run one per launch.
+// (lk_plan.h: iter_deep_fetch, tick_deep_fetch), and such a session's iterations run one per launch.
 inline bool deep_fetch_by_size(long px) { return px >= 16l * 1000 * 1000; }
+inline bool iter_deep_fetch(int iter_dma, long largest_px); // lk_plan.h (included below): the iteration launch's rule
 
 // The launches that also write the warped image address a level's planes and its flow rows through buffer resources with 32-bit
 // offsets (lk_body_buf.h): both must stay below 2 GB.
@@ -139,9 +140,9 @@ inline int session_plan_make(const ofx_params *in, const SessionSwitches &sw, Se
     // streamed refinement iterations: per flow set three more planes (shifted, warped, warped')
     const int n_iter_sets = q.n_iter_sets = p->iters > 1 ? 3 * B : 0;
     // Two iterations per launch in the stream pipeline (lk_body_pair.h): unsharded lk_float sessions with three iterations or more,
-    // windows up to 9x9, levels that do not take the deep fetch.
+    // windows up to 9x9, levels whose iteration launches may not take the deep fetch, which has no two-iteration form.
     const bool want_pairs = p->iters >= 3 && !p->sharded && (p->mode == OFX_MODE_LK_FLOAT || p->mode == OFX_MODE_LK_FLOAT_FAST) &&
-                            radius >= 1 && radius <= 4 && !deep_fetch_by_size((long)p->width * p->height) && !sw.iter_dma && sw.iter_pairs;
+                            radius >= 1 && radius <= 4 && !iter_deep_fetch(sw.iter_dma ? 1 : -1, (long)p->width * p->height) && sw.iter_pairs;
 
     ArenaOffsets &o = q.off;
     memset(&o, 0xff, sizeof o); // kNoOffset everywhere
@@ -258,3 +259,5 @@ inline int session_plan_make(const ofx_params *in, const SessionSwitches &sw, Se
 #undef OFX_PLAN_REQUIRE
 
 } // namespace ofx_plan
+
+#include "lk_plan.h" // iter_deep_fetch
