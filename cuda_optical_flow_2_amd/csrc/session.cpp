@@ -344,13 +344,14 @@ static int timed_lk_launch(ofx_session *s, const ofx_lk_desc *lk, int nl, void *
                         [&] { return ofx_lk_levels(lk, nl, s->p.window, s->p.mode, stream); });
 }
 
-static int lk_all_levels(ofx_session *s, const float *uv, void *stream)
+// k_lo: the finest level of the launches (0: the whole pyramid; levels - 1: the top level alone, which has no shift and reads no uv)
+static int lk_all_levels(ofx_session *s, const float *uv, void *stream, int k_lo = 0)
 {
     const int L = s->p.levels;
     ofx_lk_desc lk[OFX_MAX_LEVELS];
     if (s->p.iters <= 1) {
         int nl = 0;
-        for (int k = L - 1; k >= 0; --k) // coarse levels first: their few waves start at once and finish early
+        for (int k = L - 1; k >= k_lo; --k) // coarse levels first: their few waves start at once and finish early
             lk[nl++] = ofx_lk_desc{s->plane[0][k], s->plane[1][k], level_geom(s, k, s->own0[k], s->own1[k]), s->flow[k], s->own0[k],
                                    k == L - 1 ? nullptr : uv + 2 * k, 0, s->p.min_det};
         return timed_lk_launch(s, lk, nl, stream);
@@ -361,7 +362,7 @@ static int lk_all_levels(ofx_session *s, const float *uv, void *stream)
     // sh[0] holds the globally shifted next image (the warp source), sh[1] the warped image.
     ofx_shift_desc sd[OFX_MAX_LEVELS];
     int ns = 0;
-    for (int k = L - 2; k >= 0; --k)
+    for (int k = L - 2; k >= k_lo; --k)
         sd[ns++] = ofx_shift_desc{s->plane[1][k], s->sh[0][k], level_geom(s, k, 0, s->h[k]), uv + 2 * k};
     if (ns) OFX_TRY(timed_launch(s, OFX_TIME_SHIFT, stream, [&] { return ofx_shift_levels(sd, ns, stream); }));
     auto src = [&](int k) { return k == L - 1 ? s->plane[1][k] : s->sh[0][k]; };
@@ -370,7 +371,7 @@ static int lk_all_levels(ofx_session *s, const float *uv, void *stream)
     // Which plane a launch reads and writes is the schedule's (iter_plan.h); iteration 1 writes plane 0.
     uint8_t *const *wbuf[2] = {s->sh[1], s->itsh[0][2]};
     int nl = 0;
-    for (int k = L - 1; k >= 0; --k) {
+    for (int k = L - 1; k >= k_lo; --k) {
         lk[nl] = ofx_lk_desc{s->plane[0][k], src(k), level_geom(s, k, 0, s->h[k]), s->flow[k], 0, nullptr, 0, s->p.min_det};
         if (s->fused_iters) lk[nl].d_warp_src = src(k), lk[nl].d_warp_out = wbuf[0][k], lk[nl].warp_scale = OFX_ITER_SCALE;
         ++nl;
@@ -380,7 +381,7 @@ static int lk_all_levels(ofx_session *s, const float *uv, void *stream)
         const ofx_plan::IterPass &q = s->iter_plan1[i];
         ofx_warp_desc wd[OFX_MAX_LEVELS];
         nl = 0;
-        for (int k = L - 1; k >= 0; --k) {
+        for (int k = L - 1; k >= k_lo; --k) {
             wd[nl] = ofx_warp_desc{src(k), wbuf[q.win][k], level_geom(s, k, 0, s->h[k]), s->flow[k], 0, OFX_ITER_SCALE, nullptr, 0};
             lk[nl] = ofx_lk_desc{s->plane[0][k], wbuf[q.win][k], level_geom(s, k, 0, s->h[k]), s->flow[k], 0, nullptr, 1, s->p.min_det};
             if (q.wout) lk[nl].d_warp_src = src(k), lk[nl].d_warp_out = wbuf[q.wo][k], lk[nl].warp_scale = OFX_ITER_SCALE;
@@ -416,6 +417,42 @@ extern "C" int ofx_session_run_flow(ofx_session *s, void *stream)
                                                    "form the shift vectors; use corner_flows + broadcast + run_levels");
     OFX_TRY(ofx_session_corner_flows(s, stream));
     return ofx_session_run_levels(s, stream);
+}
+
+// The pair's dense flow ("coarse-to-fine propagation", include/ofx.h): the top level as run_flow runs it, then level by level one
+// prolongation (which also writes the first warped image) and `iters` accumulating single-level LK launches.  The warped images
+// alternate between sh[0][k] and sh[1][k]: nothing is shifted here, so both are free.
+extern "C" int ofx_session_run_flow_dense(ofx_session *s, float max_px, void *stream)
+{
+    OFX_REQUIRE(s, "ofx_session_run_flow_dense: null session");
+    OFX_REQUIRE(__builtin_isfinite(max_px) && max_px >= 0.0f, "ofx_session_run_flow_dense: max_px must be finite and >= 0 (0 = off)");
+    auto unsupported = [](const char *what) {
+        ofx_set_error("ofx_session_run_flow_dense: %s", what);
+        return OFX_E_UNSUPPORTED;
+    };
+    if (s->p.sharded) return unsupported("not available on a sharded session (a level's warp crosses shard rows)");
+    if (s->p.mode == OFX_MODE_COMPAT_CPU) return unsupported("needs mode lk_float or lk_float_fast (the accumulating launches)");
+    if (s->p.borrow_frames)
+        return unsupported("not available with borrow_frames (level 0 of the next frame is a warp source, which must be followed by three readable bytes)");
+    if (!s->have_prev || !s->have_next) {
+        ofx_set_error("ofx_session_run_flow_dense: need a previous and a next frame (load, build, swap, load, build)");
+        return OFX_E_STATE;
+    }
+    const int L = s->p.levels, iters = s->p.iters > 1 ? s->p.iters : 1;
+    for (int k = 0; k + 1 < L; ++k) // (the launches that also write the warped image address a level through 32-bit offsets)
+        if (iters > 1 && !ofx_plan::fits_buffer_offsets(s->h[k], s->pitch[k], s->h[k], s->w[k])) return unsupported("a level of 2 GB or more");
+    OFX_TRY(lk_all_levels(s, s->uv_cur(), stream, L - 1));
+    for (int k = L - 2; k >= 0; --k) {
+        const ofx_prolong_desc pd{s->flow[k + 1], s->w[k + 1], s->h[k + 1], s->flow[k], s->w[k], s->h[k], OFX_ITER_SCALE, max_px,
+                                  s->plane[1][k], s->pitch[k], s->sh[0][k], s->pitch[k]};
+        OFX_TRY(timed_launch(s, OFX_TIME_WARP, stream, [&] { return ofx_flow_prolong(&pd, 1, stream); }));
+        for (int i = 0; i < iters; ++i) {
+            ofx_lk_desc lk{s->plane[0][k], s->sh[i & 1][k], level_geom(s, k, 0, s->h[k]), s->flow[k], 0, nullptr, 1, s->p.min_det};
+            if (i + 1 < iters) lk.d_warp_src = s->plane[1][k], lk.d_warp_out = s->sh[(i + 1) & 1][k], lk.warp_scale = OFX_ITER_SCALE;
+            OFX_TRY(timed_lk_launch(s, &lk, 1, stream));
+        }
+    }
+    return OFX_OK;
 }
 
 // The reference's literal sequence (one level after the other, main.cu:256-262); kept for comparison and tests.

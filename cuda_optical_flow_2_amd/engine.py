@@ -153,6 +153,13 @@ class Session:
     def run_flow(self, stream=None):
         check(self.L.ofx_session_run_flow(self._h, _stream_ptr(stream)), "run_flow")
 
+    def run_flow_dense(self, max_px: Optional[float] = None, stream=None):
+        """ofx_session_run_flow_dense: the pair's dense flow of "coarse-to-fine propagation" in include/ofx.h, in run_flow's place
+        -- every level below the top starts from the prolonged flow of the level above instead of one global shift.  max_px: a
+        coarse vector longer than this many pixels (of its own level) is dropped; None: the window size, 0: no limit."""
+        max_px = float(self.window) if max_px is None else float(max_px)
+        check(self.L.ofx_session_run_flow_dense(self._h, max_px, _stream_ptr(stream)), "run_flow_dense")
+
     def run_flow_sequential(self, stream=None):
         check(self.L.ofx_session_run_flow_sequential(self._h, _stream_ptr(stream)), "run_flow_sequential")
 
@@ -1008,23 +1015,36 @@ def video_interpolate(frames, levels: int, window: int, mode: str = "lk_float", 
     in the REVERSED run's order, holds frame p+1 -> p in bwd[N-2-p].
 
     Memory: the two rings take 2 * (N-1) * H * W * 8 bytes whether they are returned or not."""
-    import torch
-
-    assert frames.dim() == 3, "video_interpolate: grey clips only, uint8 [N, H, W] (colour output is not implemented: convert the clip to grey first)"
-    N, H, W = _clip_shape(frames)
-    assert isinstance(factor, int) and 2 <= factor <= INTERP_MAX_TIMES + 1, f"factor: an integer 2 .. {INTERP_MAX_TIMES + 1}, not {factor!r}"
-    assert frames.stride(2) == 1, "frames: unit column stride"
-    if frames.stride(1) < W or frames.stride(0) < 0:
-        frames = frames.contiguous()
-    T = factor - 1
-    t, tp = _times([np.float32(k / factor) for k in range(1, factor)])
+    frames, N, H, W = _interp_clip(frames, factor)
     rings = []
     for order in (None, range(N - 1, -1, -1)):
         ring = _ring_for(N, H, W, 0, frames.device, None)
         _run_clip(frames, levels, window, mode, iters, min_det, batch, None, None, False,
                   lambda s, ring=ring: s.stream_displacement(ring, 0), order=order)
         rings.append(ring)
-    fwd, bwd = rings
+    return _interpolate_rings(frames, rings[0], rings[1], factor, return_stats, return_displacements)
+
+
+def _interp_clip(frames, factor):
+    """what video_interpolate and video_interpolate_dense require of their clip: (the clip with usable strides, N, H, W)"""
+    assert frames.dim() == 3, "video_interpolate: grey clips only, uint8 [N, H, W] (colour output is not implemented: convert the clip to grey first)"
+    N, H, W = _clip_shape(frames)
+    assert isinstance(factor, int) and 2 <= factor <= INTERP_MAX_TIMES + 1, f"factor: an integer 2 .. {INTERP_MAX_TIMES + 1}, not {factor!r}"
+    assert frames.stride(2) == 1, "frames: unit column stride"
+    if frames.stride(1) < W or frames.stride(0) < 0:
+        frames = frames.contiguous()
+    return frames, N, H, W
+
+
+def _interpolate_rings(frames, fwd, bwd, factor, return_stats, return_displacements):
+    """The in-between frames of every pair of a clip from its two level-0 displacement rings, float32 [N-1, H, W, 2]: fwd[p] is the
+    displacement frame p -> p+1, and bwd, in the REVERSED run's order, holds frame p+1 -> p in bwd[N-2-p].  The pairs go through
+    ofx_interpolate_frames_batch, up to 16 per launch, frames read in place and fields straight out of the two rings."""
+    import torch
+
+    N, H, W = _clip_shape(frames)
+    T = factor - 1
+    t, tp = _times([np.float32(k / factor) for k in range(1, factor)])
     L = _lib.load()
     out = torch.empty((N - 1, T, H, W), dtype=torch.uint8, device=frames.device)
     stats = torch.empty((N - 1, T, 4), dtype=torch.int64, device=frames.device) if return_stats else None
@@ -1044,3 +1064,81 @@ def video_interpolate(frames, levels: int, window: int, mode: str = "lk_float", 
     if return_displacements:
         res += (fwd, bwd)
     return res[0] if len(res) == 1 else res
+
+
+# ---- coarse-to-fine dense flow ----------------------------------------------------------------------------------------------------
+
+def flow_pair_dense(prev1: np.ndarray, next1: np.ndarray, levels: int, window: int, iters: int = 3, min_det: float = 1.0,
+                    max_px: Optional[float] = None, mode: str = "lk_float") -> List[np.ndarray]:
+    """Whole pair through a Session's run_flow_dense: the dense flow pyramid as host arrays.  OFX_ITER_SCALE * flow[k] is level
+    k's motion in pixels."""
+    import torch
+
+    h, w = prev1.shape
+    s = Session(w, h, levels, window, mode, iters=iters, min_det=min_det)
+    try:
+        s.push_frame_host(prev1)
+        s.set_frame_host(next1)
+        s.build_pyramid()
+        s.run_flow_dense(max_px)
+        torch.cuda.synchronize()
+        return [s.flow_host(k) for k in range(levels)]
+    finally:
+        s.close()
+
+
+def _dense_ring(frames, order, levels, window, iters, min_det, max_px, level, mode, out):
+    """the displacement at `level` of every consecutive pair of the clip, its frames taken in `order`, pair at a time: set_frame_device /
+    build_pyramid / run_flow_dense / ofx_flow_displacement (no global shift) into the pair's slot / swap, all on the current stream"""
+    import torch
+
+    N, H, W = _clip_shape(frames)
+    assert frames.dim() == 3, "grey clips only, uint8 [N, H, W]"
+    assert 0 <= level < levels
+    assert frames.stride(2) == 1, "frames: unit column stride"
+    if frames.stride(1) < W:
+        frames = frames.contiguous()
+    out = _ring_for(N, H, W, level, frames.device, out)
+    assert out.stride(3) == 1 and out.stride(2) == 2 and out.stride(1) == 2 * (W >> level) and out.data_ptr() % 8 == 0 and (out.stride(0) * 4) % 8 == 0, \
+        "out: tightly packed rows, 8-byte aligned slots"
+    s = Session(W, H, levels, window, mode, iters=iters, min_det=min_det)
+    try:
+        L, st = s.L, _stream_ptr()
+        s.set_frame_device(frames[order[0]])
+        s.build_pyramid()
+        s.swap()
+        for p in range(1, N):
+            s.set_frame_device(frames[order[p]])
+            s.build_pyramid()
+            s.run_flow_dense(max_px)
+            flow, _ = s.flow(level)
+            check(L.ofx_flow_displacement(flow.data_ptr(), W >> level, H >> level, None, ITER_SCALE, out[p - 1].data_ptr(), st), "ofx_flow_displacement")
+            s.swap()
+        torch.cuda.current_stream().synchronize()   # (the session's buffers go with it)
+    finally:
+        s.close()
+    return out
+
+
+def video_displacement_dense(frames, levels: int, window: int, iters: int = 3, min_det: float = 1.0, max_px: Optional[float] = None,
+                             level: int = 0, out=None, mode: str = "lk_float"):
+    """The motion in pixels of every consecutive pair of a grey clip at `level`, by the coarse-to-fine dense flow
+    (Session.run_flow_dense; "coarse-to-fine propagation" in include/ofx.h): OFX_ITER_SCALE times the level's flow, every level
+    started from the whole flow of the level above.  Unlike video_displacement it follows motions of many pixels per frame and
+    several motions in one scene; it runs pair at a time, levels one after the other.  frames: uint8 CUDA tensor [N, H, W], N >= 2,
+    unit column stride.  Returns float32 [N-1, H >> level, W >> level, 2]: out[p-1] is the displacement frame p-1 -> frame p; `out`
+    may supply the tensor.  mode: "lk_float" or "lk_float_fast"."""
+    N = _clip_shape(frames)[0]
+    return _dense_ring(frames, list(range(N)), levels, window, iters, min_det, max_px, level, mode, out)
+
+
+def video_interpolate_dense(frames, levels: int, window: int, factor: int = 2, iters: int = 3, min_det: float = 1.0,
+                            max_px: Optional[float] = None, return_stats: bool = False, return_displacements: bool = False,
+                            mode: str = "lk_float"):
+    """video_interpolate with the displacements of the coarse-to-fine dense flow: the clip goes through _dense_ring at level 0 as it
+    is and in reverse frame order (the frames are not copied), and the two rings then go through ofx_interpolate_frames_batch as
+    video_interpolate's do.  Arguments and results as there."""
+    frames, N, H, W = _interp_clip(frames, factor)
+    fwd = _dense_ring(frames, list(range(N)), levels, window, iters, min_det, max_px, 0, mode, None)
+    bwd = _dense_ring(frames, list(range(N - 1, -1, -1)), levels, window, iters, min_det, max_px, 0, mode, None)
+    return _interpolate_rings(frames, fwd, bwd, factor, return_stats, return_displacements)

@@ -41,6 +41,13 @@ class Params(C.Structure):
                 ("stream_two_stage", C.c_int), ("frames_partial", C.c_int), ("deep_fetch", C.c_int)]
 
 
+class ProlongDesc(C.Structure):
+    """ofx_prolong_desc (include/ofx.h, "coarse-to-fine propagation")"""
+    _fields_ = [("d_coarse", C.c_void_p), ("wc", C.c_int), ("hc", C.c_int), ("d_fine", C.c_void_p), ("w", C.c_int), ("h", C.c_int),
+                ("scale", C.c_float), ("max_px", C.c_float), ("d_src", C.c_void_p), ("src_pitch", C.c_int), ("d_dst", C.c_void_p),
+                ("dst_pitch", C.c_int)]
+
+
 _vp = C.c_void_p
 _i = C.c_int
 _d = C.c_double
@@ -117,6 +124,8 @@ _SIGS = {
     "ofx_flow_displacement": [_vp, _i, _i, _vp, C.c_float, _vp, _vp],
     "ofx_session_stream_displacement": [_vp, _i, C.c_float, _vp, C.c_size_t, _i],
     "ofx_session_displacement_of": [_vp, _i, C.POINTER(_vp)],
+    "ofx_flow_prolong": [C.POINTER(ProlongDesc), _i, _vp],
+    "ofx_session_run_flow_dense": [_vp, C.c_float, _vp],
     "ofx_interpolate_frames": [_vp, _i, _vp, _i, _i, _i, _vp, _vp, C.POINTER(C.c_float), _i, _vp, _i, C.c_size_t, _vp, _vp],
     "ofx_interpolate_frames_batch": [C.POINTER(_vp), C.POINTER(_i), C.POINTER(_vp), C.POINTER(_i), _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp),
                                      C.POINTER(C.c_float), _i, C.POINTER(_vp), _i, C.c_size_t, C.POINTER(_vp), _vp],

@@ -436,6 +436,54 @@ int ofx_interpolate_frames_batch(const uint8_t *const *d_a, const int *a_pitches
                                  uint8_t *const *d_dst, int dst_pitch, size_t time_stride_bytes,
                                  int64_t *const *d_stats /* may be NULL */, void *stream);
 
+/* ---- coarse-to-fine propagation ------------------------------------------------
+ * The reference hands a level ONE vector of the level above -- pixel 0's, as a global translation (ofx_shift_vector) -- and every
+ * consumer of a displacement inherits that: beyond about 2 px per frame, or with two motions in one scene, the local estimate is
+ * noise.  Here a level starts from the whole flow of the level above.  THE definition (everything else quotes it).
+ *
+ * PROLONGATION of a coarse field c (wc x hc, interleaved (u, v) float32, tightly packed) to a fine size w in {2*wc, 2*wc + 1},
+ * h in {2*hc, 2*hc + 1}, with a `scale` (field units -> pixels) and a `max_px` >= 0.  Every float32 operation is rounded once,
+ * nothing is fused, denormals are kept.
+ *   1. Sanitise.  A coarse vector is replaced by (+0, +0) when either component is not finite and, with max_px > 0, when
+ *      |scale*u| > max_px or |scale*v| > max_px (the product rounded once to float; `>` is false for a NaN, and the finiteness
+ *      test has caught those).  max_px == 0: only the finiteness test.
+ *   2. Sample at (x/2, y/2): pixel xc of pyramid level k + 1 sits at position 2*xc of level k, because ofx_downsample_1ch centres
+ *      its stencil there.  x0 = min(x >> 1, wc - 1), x1 = min(x0 + 1, wc - 1), a = c(., x0), b = c(., x1), per component:
+ *        even x: a itself, no arithmetic (a + 0*(b - a) would turn -0 into +0);
+ *        odd x:  a + 0.5f*(b - a): the difference, the product, the sum.
+ *      Horizontally first, on the coarse rows y0 = min(y >> 1, hc - 1) and y1 = min(y0 + 1, hc - 1); then the same rule
+ *      vertically on the two results (even y: row y0's result itself).
+ *   3. fine(x, y) = 2.0f * that (exact, unless it overflows to Inf).
+ *   4. warped = what ofx_warp_levels writes for {src, fine, scale}, byte for byte: orc_warp_bilinear_u8's operation order,
+ *      replicate border, and a pixel with |x + scale*u| > 1e9, |y + scale*v| > 1e9 or a NaN there is NOT WARPED.
+ *
+ * A PAIR'S DENSE FLOW, for L levels and iters >= 1 launches per level, lk_float:
+ *   level L-1:  what ofx_session_run_flow computes for that level: iteration 1 is the reference's level (it is not shifted), then
+ *               iters - 1 refinement iterations.
+ *   level k < L-1, no global shift:  flow_k = prolong(flow_{k+1}; scale = OFX_ITER_SCALE, max_px);  W = warped(next_k, flow_k);
+ *               then iters times:  flow_k += LK(prev_k, W), a float32 add, the solve under the min_det guard;  and
+ *               W = ofx_warp_levels(next_k, flow_k, OFX_ITER_SCALE) for all but the last.
+ *   The level's displacement in pixels is OFX_ITER_SCALE * flow_k: ofx_flow_displacement with d_uv = NULL.
+ *
+ * ofx_flow_prolong: 1 <= n <= OFX_MAX_LEVELS prolongations in ONE launch.  d_src / d_dst (both or neither): the launch also
+ * writes step 4's image, from the fine vectors it holds in registers; d_src is the next image of the fine level (row pitch
+ * src_pitch >= w), d_dst a plane that does not overlap it (row pitch dst_pitch >= w; the bytes beyond column w - 1 of a row are
+ * left untouched).  d_coarse and d_fine 8-byte aligned and not overlapping; w * h < 2^28 and a plane below 2^31 bytes; scale
+ * finite; max_px finite and >= 0; otherwise OFX_E_INVALID, before anything is enqueued.  No tap reads outside the
+ * (h - 1) * pitch + w bytes of d_src or the wc * hc * 8 bytes of d_coarse, whatever the field holds. */
+typedef struct ofx_prolong_desc {
+    const float *d_coarse;
+    int wc, hc;
+    float *d_fine; /* 8-byte aligned, tightly packed */
+    int w, h;
+    float scale, max_px;
+    const uint8_t *d_src; /* warp source (the next image of the fine level); NULL = flow only */
+    int src_pitch;
+    uint8_t *d_dst; /* warped image; bytes beyond column w-1 untouched */
+    int dst_pitch;
+} ofx_prolong_desc;
+int ofx_flow_prolong(const ofx_prolong_desc *levels, int n, void *stream);
+
 /* ---- layout helpers ------------------------------------------------------ */
 int ofx_extract_ch0(const uint8_t *d_src3, uint8_t *d_dst1, int w, int h, int dst_pitch, void *stream);
 int ofx_replicate_3ch(const uint8_t *d_src1, int src_pitch, uint8_t *d_dst3, int w, int h, void *stream);
@@ -631,6 +679,19 @@ int ofx_session_downsample_level(ofx_session *s, int level, void *stream);
 int ofx_session_run_flow(ofx_session *s, void *stream);
 int ofx_session_corner_flows(ofx_session *s, void *stream);
 int ofx_session_run_levels(ofx_session *s, void *stream);
+/* The pair's DENSE flow of "coarse-to-fine propagation" above, in ofx_session_run_flow's place in the call sequence (set frame,
+ * build pyramid, THIS, swap); results through ofx_session_flow(s, k), iters = ofx_params.iters (0 counts as 1), min_det =
+ * ofx_params.min_det.  max_px: the definition's, in pixels of the COARSE level (0 = off; the window size is the usual choice: a
+ * vector the level above could not have measured starts the level below from nothing instead).  The top level runs as in
+ * ofx_session_run_flow; then per level, coarse to fine, one ofx_flow_prolong (timing kind OFX_TIME_WARP) and iters single-level
+ * accumulating ofx_lk_levels launches, all but the last of which also write the next warped image.  The warped images alternate
+ * between the level's two shifted-scratch planes, which nothing shifts here; the levels depend on each other, so a pair takes
+ * (levels - 1) * (iters + 1) launches below its top level.  Never allocates, never synchronises.
+ * Unsharded lk_float / lk_float_fast sessions that copy their frames: OFX_E_UNSUPPORTED for a sharded session, compat_cpu and
+ * borrow_frames (level 0 of the next frame would be the warp source, and a caller's buffer need not be followed by the three
+ * readable bytes of ofx_lk_desc.d_warp_src).  OFX_E_STATE without a previous and a next frame; max_px negative or not finite:
+ * OFX_E_INVALID. */
+int ofx_session_run_flow_dense(ofx_session *s, float max_px, void *stream);
 /* The same result the reference's way: per level ofx_session_compute_uv then ofx_session_run_level, coarse to fine. */
 int ofx_session_run_flow_sequential(ofx_session *s, void *stream);
 /* Shift vector of `level` from the coarser flows' pixel 0 into the session's uv slot (meaningful on the rank that
