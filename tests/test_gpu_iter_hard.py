@@ -113,16 +113,10 @@ def test_determinant_guard_with_iterations(eng, oracle, monkeypatch, case):
     _against_the_oracle(eng, oracle, monkeypatch, case, min_det=ih.MIN_DET)
 
 
-@pytest.mark.parametrize("case", ih.E_CASES, ids=_ids(ih.E_CASES))
-def test_fast_solve_step_by_step(eng, oracle, monkeypatch, case):
-    """E.  lk_float_fast is not restated on the CPU and 1 ulp may flip a byte of the next warped image, so whole chains cannot be
-    compared; single steps can.  F_j and F_{j+1} are the GPU's own (sessions of j and j + 1 iterations); the oracle makes the step
-    from F_j (iter_hard.check_fast_step: 1 ulp of the step's solve, lk_solve.h's cancelling numerators by their own bound).  F_1
-    against the oracle's first iteration with assert_flow_close(..., 1).  Streamed cases: level 1 is unshifted, level 0's next is
-    the oracle's global shift by the GPU's own first-iteration level-1 flow."""
-    frames = ih.case_frames(case)
+def fast_steps_against_the_oracle(oracle, case, frames, runs):
+    """The body of test_fast_solve_step_by_step: runs = {j: {pair: flow pyramid}} of lk_float_fast sessions of j = 1 .. case.iters
+    iterations on `frames`.  tests/test_gpu_deep_iter.py calls it with the runs of a child process."""
     L, win = case.levels, case.win
-    runs = {j: _run(eng, monkeypatch, case, frames, "lk_float_fast", iters=j) for j in range(1, case.iters + 1)}
     steps = exempt = 0
     for p in runs[1]:
         pp = oracle.gauss_pyramid(synth.to_3ch(frames[p - 1]), L)
@@ -137,3 +131,15 @@ def test_fast_solve_step_by_step(eng, oracle, monkeypatch, case):
                 steps += s
                 exempt += e
     assert exempt <= 1e-3 * steps, f"{case.id}: {exempt} of {steps} values took the exception's bound"
+
+
+@pytest.mark.parametrize("case", ih.E_CASES, ids=_ids(ih.E_CASES))
+def test_fast_solve_step_by_step(eng, oracle, monkeypatch, case):
+    """E.  lk_float_fast is not restated on the CPU and 1 ulp may flip a byte of the next warped image, so whole chains cannot be
+    compared; single steps can.  F_j and F_{j+1} are the GPU's own (sessions of j and j + 1 iterations); the oracle makes the step
+    from F_j (iter_hard.check_fast_step: 1 ulp of the step's solve, lk_solve.h's cancelling numerators by their own bound).  F_1
+    against the oracle's first iteration with assert_flow_close(..., 1).  Streamed cases: level 1 is unshifted, level 0's next is
+    the oracle's global shift by the GPU's own first-iteration level-1 flow."""
+    frames = ih.case_frames(case)
+    runs = {j: _run(eng, monkeypatch, case, frames, "lk_float_fast", iters=j) for j in range(1, case.iters + 1)}
+    fast_steps_against_the_oracle(oracle, case, frames, runs)

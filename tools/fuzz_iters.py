@@ -1,11 +1,14 @@
 """Randomised parity of the refinement iterations (lk_iter): the launches that write the next iteration's warped image themselves
 (csrc/lk_body_warp.h; the default) against one warp launch per iteration (OFX_ITER_FUSED=0), pair at a time and through the
-stream pipeline -- random size, levels, window, iterations, solve, frames per tick, borrowed frames, deep row fetch, row sharding
+stream pipeline -- random size, levels, window, iterations, solve, frames per tick, borrowed frames, row sharding
 (logical ranks on one device; a result that differs must come with a non-zero status word), and frames with flat blocks and
 noise (non-finite and huge flows).  Against the oracle, tests/test_gpu_parity.py pins the two-launch form on smooth pairs, and
 tests/test_gpu_iter_hard.py the default form on such frames: every window 3x3 .. 23x23 pair at a time, the stream pipeline with two
 iterations per launch, min_det against the guarded restatement, lk_float_fast step by step.
-    python tools/fuzz_iters.py [n_configs] [seed]"""
+    [OFX_ITER_DMA=0|1] python tools/fuzz_iters.py [n_configs] [seed]
+The deep row fetch of the iteration launches is a property of the PROCESS: the library reads OFX_ITER_DMA once, at its first LK
+launch, so every configuration of a run takes the form the tool was started under (printed once; unset: by the level's size).  Run
+the tool once per value; tests/test_gpu_deep_iter.py pins the deep form to the oracle."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -30,7 +33,7 @@ def run(n_cfg: int, seed: int) -> int:
         mode = "lk_float" if rng.random() < 0.75 else "lk_float_fast"
         B = int(rng.choice([1, 2, 4, 8]))
         borrow = bool(rng.random() < 0.5)
-        dma = int(rng.choice([0, 1]))
+        rng.choice([0, 1])   # (once the deep fetch, drawn per configuration but latched by the first: kept so that a seed draws what it drew)
         R = int(rng.choice([1, 1, 2, 3])) if L >= 2 else 1
         if R > 1 and (h >> (L - 1)) < 2 * R:
             R = 1
@@ -47,10 +50,9 @@ def run(n_cfg: int, seed: int) -> int:
             buf = torch.zeros((h, pitch), dtype=torch.uint8, device="cuda")
             buf[:, :w] = torch.from_numpy(a).cuda()
             frames.append(buf[:, :w])
-        desc = f"{w}x{h} L{L} w{win} iters{iters} {mode} B{B} borrow={borrow} dma={dma} R{R} nf={nf} {kind}"
+        desc = f"{w}x{h} L{L} w{win} iters{iters} {mode} B{B} borrow={borrow} R{R} nf={nf} {kind}"
         if os.environ.get("OFX_FUZZ_ONLY") and it != int(os.environ["OFX_FUZZ_ONLY"]):
             continue
-        os.environ["OFX_ITER_DMA"] = str(dma)
         try:
             def plain_all(fused):
                 os.environ["OFX_ITER_FUSED"] = "1" if fused else "0"
@@ -113,6 +115,7 @@ def run(n_cfg: int, seed: int) -> int:
 if __name__ == "__main__":
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 40
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+    print(f"deep fetch of the iteration launches: OFX_ITER_DMA={os.environ.get('OFX_ITER_DMA', 'unset (by size: levels of 16 Mpx and more)')}, every configuration")
     nb = run(n, seed)
     print(f"{n} configurations, {nb} failing")
     sys.exit(1 if nb else 0)
