@@ -83,6 +83,7 @@ int ofx_corner_args(const ofx_lk_desc *levels, int n_levels, int window, int mod
         if (cols && cols[k] > 0 && cols[k] < g->w) gc.w = cols[k];
         OFX_TRY(ofx_check_geom(&gc, "ofx_corner_flows"));
         OFX_REQUIRE(levels[k].d_prev && levels[k].d_next, "ofx_corner_flows: null plane at level %d", k);
+        OFX_REQUIRE(((uintptr_t)levels[k].d_prev & 3) == 0 && ((uintptr_t)levels[k].d_next & 3) == 0, "ofx_corner_flows: planes must be 4-byte aligned (level %d)", k);
         OFX_REQUIRE(g->row0 == 0, "ofx_corner_flows: level %d buffer must start at row 0 (it holds rows from %d)", k, g->row0);
         const int need = a.radius + 2 < g->h ? a.radius + 2 : g->h;
         OFX_REQUIRE(g->rows >= need, "ofx_corner_flows: level %d holds %d rows, the corner needs %d", k, g->rows, need);

@@ -129,6 +129,8 @@ int lk_build_levels(const ofx_lk_desc *d, int n, int window, int mode, int32_t *
         OFX_TRY(ofx_check_geom(g, "ofx_lk_level"));
         OFX_REQUIRE(d[i].d_prev && d[i].d_next && (d[i].d_flow || d_sums), "ofx_lk_level: null pointer");
         OFX_REQUIRE(((uintptr_t)d[i].d_prev & 3) == 0 && ((uintptr_t)d[i].d_next & 3) == 0, "ofx_lk_level: planes must be 4-byte aligned");
+        // (the marches store a flow row as 8-byte pairs and as 16-byte pieces declared 8-byte aligned: lk_body.h, lk_body_buf.h)
+        OFX_REQUIRE(((uintptr_t)d[i].d_flow & 7) == 0, "ofx_lk_level: d_flow must be 8-byte aligned");
         OFX_REQUIRE(d[i].flow_row0 <= g->out_y0, "ofx_lk_level: flow_row0 %d > out_y0 %d", d[i].flow_row0, g->out_y0);
         OFX_TRY(ofx_check_halo(g, radius + 1, "ofx_lk_level"));
         if (g->out_y1 <= g->out_y0) continue;
@@ -156,6 +158,7 @@ int lk_build_levels(const ofx_lk_desc *d, int n, int window, int mode, int32_t *
             OFX_REQUIRE(!d_sums && d[i].d_warp_src && d[i].d_flow, "ofx_lk_levels: d_warp_out needs d_warp_src and d_flow");
             OFX_REQUIRE(d[i].d_warp_out != d[i].d_next && d[i].d_warp_out != d[i].d_warp_src && d[i].d_warp_out != d[i].d_prev,
                         "ofx_lk_levels: d_warp_out must be a plane of its own");
+            OFX_REQUIRE(((uintptr_t)d[i].d_warp_src & 3) == 0 && ((uintptr_t)d[i].d_warp_out & 3) == 0, "ofx_lk_levels: d_warp_src and d_warp_out must be 4-byte aligned");
             a.warp_src = d[i].d_warp_src;
             a.warp_out = d[i].d_warp_out;
             a.warp_scale = d[i].warp_scale;

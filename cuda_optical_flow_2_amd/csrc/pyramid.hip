@@ -166,7 +166,8 @@ int ofx_pyramid_args(const uint8_t *d_level0, int pitch0, int w, int h, uint8_t 
     OFX_REQUIRE(d_level0 && d_levels && pitches && w > 0 && h > 0, "ofx_pyramid_1ch: bad arguments");
     OFX_REQUIRE(levels >= 2 && levels - 1 <= kPyrMaxProduced, "ofx_pyramid_1ch: %d levels unsupported (2..%d)", levels,
                 kPyrMaxProduced + 1);
-    OFX_REQUIRE(((uintptr_t)d_level0 & 3) == 0 && (pitch0 & 3) == 0, "ofx_pyramid_1ch: level 0 must be 4-byte aligned with a pitch multiple of 4");
+    OFX_REQUIRE(((uintptr_t)d_level0 & 3) == 0 && (pitch0 & 3) == 0 && pitch0 >= w,
+                "ofx_pyramid_1ch: level 0 must be 4-byte aligned with a pitch that is a multiple of 4 and >= the width");
     PyrArgs a{};
     a.src = d_level0;
     a.pitch[0] = pitch0;
@@ -178,6 +179,7 @@ int ofx_pyramid_args(const uint8_t *d_level0, int pitch0, int w, int h, uint8_t 
     for (int k = 1; k < levels; ++k) {
         OFX_REQUIRE(((w >> (k - 1)) & 1) == 0 && ((h >> (k - 1)) & 1) == 0, "ofx_pyramid_1ch: level %d has odd dimensions", k - 1);
         OFX_REQUIRE(d_levels[k] != nullptr && pitches[k] >= (w >> k), "ofx_pyramid_1ch: bad plane for level %d", k);
+        OFX_REQUIRE(((uintptr_t)d_levels[k] & 3) == 0 && (pitches[k] & 3) == 0, "ofx_pyramid_1ch: level %d must be 4-byte aligned with a pitch multiple of 4", k);
         a.dst[k] = d_levels[k];
         a.pitch[k] = pitches[k];
         a.w[k] = w >> k;
@@ -334,6 +336,7 @@ int ofx_shift_table(const ofx_shift_desc *levels, int n, ShiftTable *out, int *b
         OFX_TRY(ofx_check_geom(g, "ofx_shift_1ch"));
         OFX_REQUIRE(levels[i].d_src && levels[i].d_dst && levels[i].d_uv, "ofx_shift_1ch: null pointer");
         OFX_REQUIRE(levels[i].d_src != levels[i].d_dst, "ofx_shift_1ch: in-place shift is not supported");
+        OFX_REQUIRE(((uintptr_t)levels[i].d_src & 3) == 0 && ((uintptr_t)levels[i].d_dst & 3) == 0, "ofx_shift_1ch: planes must be 4-byte aligned");
         OFX_REQUIRE(g->out_y0 >= g->row0 && g->out_y1 <= g->row0 + g->rows, "ofx_shift_1ch: output rows outside the buffer");
         if (g->out_y1 <= g->out_y0) continue;
         const int bx = ofx_div_up(ofx_div_up(g->pitch, 16), 256);
@@ -378,6 +381,8 @@ extern "C" int ofx_warp_levels(const ofx_warp_desc *levels, int n, void *stream)
         OFX_TRY(ofx_check_geom(g, "ofx_warp_levels"));
         OFX_REQUIRE(levels[i].d_src && levels[i].d_dst && levels[i].d_flow, "ofx_warp_levels: null pointer");
         OFX_REQUIRE(levels[i].d_src != levels[i].d_dst, "ofx_warp_levels: in-place warp is not supported");
+        OFX_REQUIRE(((uintptr_t)levels[i].d_src & 3) == 0 && ((uintptr_t)levels[i].d_dst & 3) == 0, "ofx_warp_levels: planes must be 4-byte aligned");
+        OFX_REQUIRE(((uintptr_t)levels[i].d_flow & 7) == 0, "ofx_warp_levels: d_flow must be 8-byte aligned");
         OFX_REQUIRE(g->out_y0 >= g->row0 && g->out_y1 <= g->row0 + g->rows, "ofx_warp_levels: output rows outside the planes");
         OFX_REQUIRE(levels[i].flow_row0 <= g->out_y0, "ofx_warp_levels: flow_row0 > out_y0");
         if (g->out_y1 <= g->out_y0) continue;

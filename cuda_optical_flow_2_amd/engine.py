@@ -604,11 +604,7 @@ def compose_flow(flow_levels: List[np.ndarray], levels: int, level: int) -> np.n
 
 def warp_u8(src1: np.ndarray, flow: np.ndarray, scale: float) -> np.ndarray:
     import torch
-    from .lib import Geom
-
-    class WarpDesc(C.Structure):
-        _fields_ = [("d_src", _vp), ("d_dst", _vp), ("geom", Geom), ("d_flow", _vp), ("flow_row0", C.c_int), ("scale", C.c_float),
-                    ("d_status", _vp), ("status_bit", C.c_int)]
+    from .lib import WarpDesc
 
     L = _lib.load()
     h, w = src1.shape

@@ -48,6 +48,24 @@ class ProlongDesc(C.Structure):
                 ("dst_pitch", C.c_int)]
 
 
+class LkDesc(C.Structure):
+    """ofx_lk_desc (include/ofx.h): one level of an ofx_lk_levels / ofx_corner_flows launch"""
+    _fields_ = [("d_prev", C.c_void_p), ("d_next", C.c_void_p), ("geom", Geom), ("d_flow", C.c_void_p), ("flow_row0", C.c_int),
+                ("d_uv", C.c_void_p), ("accumulate", C.c_int), ("min_det", C.c_float), ("d_warp_src", C.c_void_p),
+                ("d_warp_out", C.c_void_p), ("warp_scale", C.c_float), ("d_warp_status", C.c_void_p), ("warp_status_bit", C.c_int)]
+
+
+class ShiftDesc(C.Structure):
+    """ofx_shift_desc (include/ofx.h): one level of an ofx_shift_levels launch"""
+    _fields_ = [("d_src", C.c_void_p), ("d_dst", C.c_void_p), ("geom", Geom), ("d_uv", C.c_void_p)]
+
+
+class WarpDesc(C.Structure):
+    """ofx_warp_desc (include/ofx.h): one level of an ofx_warp_levels launch"""
+    _fields_ = [("d_src", C.c_void_p), ("d_dst", C.c_void_p), ("geom", Geom), ("d_flow", C.c_void_p), ("flow_row0", C.c_int),
+                ("scale", C.c_float), ("d_status", C.c_void_p), ("status_bit", C.c_int)]
+
+
 _vp = C.c_void_p
 _i = C.c_int
 _d = C.c_double

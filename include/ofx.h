@@ -17,9 +17,14 @@
  *     entry points only enqueue work; they never synchronise or allocate.
  *   - "3ch" images are HWC interleaved u8, 3 bytes per pixel, tightly packed
  *     (the reference's layout, main.cu:95-104).  "1ch" planes are u8 with a row
- *     pitch in bytes that is a multiple of 4 and >= w.
+ *     pitch in bytes that is a multiple of 4 and >= w.  A plane pointer is 4-byte
+ *     aligned (the kernels load and store dwords); otherwise OFX_E_INVALID.  Pad
+ *     bytes (columns [w, pitch) of a row) of an input may hold anything.
  *   - flow is interleaved (u,v) float32, 2*w floats per row, tightly packed
- *     (OptFlowGpu.cu:1844-1845).
+ *     (OptFlowGpu.cu:1844-1845).  A flow pointer handed to ofx_lk_level(s) or
+ *     ofx_warp_levels is 8-byte aligned (a (u,v) pair is loaded and stored as one
+ *     piece, rows as 16-byte pieces at 8-byte aligned addresses); otherwise
+ *     OFX_E_INVALID.  Nothing more is needed: not 16 bytes, not a padded row.
  *   - window sizes are the reference's ww/wh (full size, not radius).
  */
 #ifndef OFX_H
@@ -106,7 +111,7 @@ typedef struct ofx_lk_desc {
     /* Extension (the reference divides unguarded, OptFlowGpu.cu:1833-1838 / OptFlowCPU.cpp:369-372, and writes
      * NaN / Inf / huge vectors where a window has no texture or a single edge): > 0 = a pixel whose determinant Sxx*Syy - Sxy^2,
      * rounded to float, is below min_det gets the flow (0, 0).  0 = the reference.  One value per launch: the first
-     * descriptor's. */
+     * descriptor's -- levels[0].min_det, also when levels[0] is empty (out_y1 == out_y0) and launches nothing itself. */
     float min_det;
     /* Extension (lk_iter; csrc/lk_body_warp.h).  d_warp_out non-NULL, with accumulate set: the launch also writes the warped image
      * the NEXT refinement iteration reads as its d_next -- d_warp_out = ofx_warp_levels(d_warp_src, the flow this launch leaves in
@@ -117,7 +122,9 @@ typedef struct ofx_lk_desc {
      * is followed by 64.)
      * For all descriptors of a launch or for none.  On a row window (a shard: geom.row0 / rows / out rows are not the whole level)
      * d_warp_out receives the out rows, a tap row outside [row0, row0 + rows) is replaced by the nearest row held, and bit
-     * warp_status_bit of *d_warp_status (optional) is set when a pixel with a finite flow needed such a row. */
+     * warp_status_bit of *d_warp_status (optional) is set when a pixel with a finite flow needed such a row.
+     * Pad bytes of d_warp_out: an out row is stored as whole dwords, so its columns [w, (w + 3) & ~3) are written with unspecified
+     * values; the columns from (w + 3) & ~3 on, and every row that is not an out row, are left untouched. */
     const uint8_t *d_warp_src;
     uint8_t *d_warp_out;
     float warp_scale;
@@ -227,12 +234,14 @@ int ofx_lk_level_sums(const uint8_t *d_prev, const uint8_t *d_next, const ofx_ge
  * of gpu::gauss_pyramid (OptFlowGpu.cu:1198-1232) / cpu::downscale_gaussian
  * (OptFlowCPU.cpp:112-148) for grey images.  `dst` describes the destination
  * level; the source level is (2*dst->w) x (2*dst->h) and src_row0/src_rows say
- * which of its rows d_src holds. */
+ * which of its rows d_src holds.  Pad bytes of d_dst: the columns [w, (w + 3) & ~3)
+ * of the out rows are written as 0, everything else is left untouched. */
 int ofx_downsample_1ch(const uint8_t *d_src, int src_pitch, int src_row0, int src_rows,
                        uint8_t *d_dst, const ofx_geom *dst, void *stream);
 
 /* All levels of a grey pyramid from level 0 in ONE launch (same arithmetic as ofx_downsample_1ch level by level;
- * whole, unsharded levels only).  d_levels[k] / pitches[k] for k = 1..levels-1 (index 0 unused). */
+ * whole, unsharded levels only).  d_levels[k] / pitches[k] for k = 1..levels-1 (index 0 unused).  Only the pixels are
+ * stored: the pad bytes of the planes (columns >= w >> k) are left untouched. */
 int ofx_pyramid_1ch(const uint8_t *d_level0, int pitch0, int w, int h, uint8_t *const *d_levels, const int *pitches,
                     int levels, void *stream);
 
@@ -251,7 +260,8 @@ int ofx_shift_vector(const float *const *d_flow_levels, int level, int max_level
  * Descriptors: index k = pyramid level k, d_next = the UNSHIFTED next plane, geom.row0 must be 0. */
 int ofx_corner_flows(const ofx_lk_desc *levels, int n_levels, int window, int mode, float *d_uv, void *stream);
 
-/* Several ofx_shift_1ch calls in one launch (ofx_shift_desc is declared above). */
+/* Several ofx_shift_1ch calls in one launch (ofx_shift_desc is declared above).  Pad bytes of d_dst: the out rows are
+ * stored over their whole pitch, columns [w, pitch) as 0; rows that are not out rows are left untouched. */
 int ofx_shift_levels(const ofx_shift_desc *levels, int n, void *stream);
 
 /* dst(x,y) = src((int)(x+u), (int)(y+v)) when that lands inside the image,
@@ -267,7 +277,9 @@ int ofx_shift_1ch(const uint8_t *d_src, uint8_t *d_dst, const ofx_geom *g, const
  * the window is replaced by the nearest row held and, when d_status is not NULL, bit status_bit is OR-ed into *d_status (a
  * row-sharded caller's flow reached beyond its halo).  One refinement
  * iteration of a level = this warp of the (shifted) next image by the flow so far, then ofx_lk_levels with
- * accumulate = 1.  scale = OFX_ITER_SCALE turns the reference's flow units into pixels (Sobel gain 8 / Dt_3x3 gain 15). */
+ * accumulate = 1.  scale = OFX_ITER_SCALE turns the reference's flow units into pixels (Sobel gain 8 / Dt_3x3 gain 15).
+ * Pad bytes of d_dst: the out rows are stored over their whole pitch, columns [w, pitch) as 0; rows that are not out rows
+ * are left untouched.  No tap reads outside the rows * pitch bytes of d_src, whatever the flow holds. */
 #define OFX_ITER_SCALE 0.533333361148834228515625f
 typedef struct ofx_warp_desc {
     const uint8_t *d_src;

@@ -52,15 +52,15 @@ class Field:
 
 
 class Plane:
-    """A [h, w] uint8 plane with rows `pitch` bytes apart inside a larger buffer: `lead` bytes before it, 64 after its last row,
-    and the pad columns of every row, all holding the byte `around`."""
+    """A [h, w] uint8 plane with rows `pitch` bytes apart inside a larger buffer: `lead` bytes before it, `trail` (64) after its
+    last row, and the pad columns of every row, all holding the byte `around`."""
 
-    def __init__(self, arr, pitch, lead, around):
+    def __init__(self, arr, pitch, lead, around, trail=64):
         import torch
 
         h, w = arr.shape
         assert pitch >= w
-        host = np.full(lead + h * pitch + 64, around, np.uint8)
+        host = np.full(lead + h * pitch + trail, around, np.uint8)
         np.lib.stride_tricks.as_strided(host[lead:], (h, w), (pitch, 1))[...] = arr
         self.t = torch.from_numpy(host).cuda()
         self.ptr, self.pitch = self.t.data_ptr() + lead, pitch
