@@ -196,6 +196,12 @@ struct ofx_interp_batch {
 };
 int ofx_interp_batch_launch(const ofx_interp_batch *a, void *stream);
 
+// colour frame interpolation (interp3.hip; the definition: "colour frame interpolation" in include/ofx.h): ofx_interp_batch's
+// fields with a[i] / b[i] and dst[i] interleaved 3-channel planes, every pitch in bytes and >= 3 * w, the geometry and the counts
+// once per pixel.  Whole quads go out as three dwords where every dst, dst_pitch and time_stride are 4-byte aligned.
+struct ofx_interp3_batch : ofx_interp_batch {};
+int ofx_interp3_batch_launch(const ofx_interp3_batch *a, void *stream);
+
 // the stream pipeline's colour front end (frontend.hip): the filter's tables for one (window, sigma_s, sigma_b), built once on the
 // host (window 0: grey frames only; an unsupported window is OFX_E_UNSUPPORTED), and one launch over n <= OFX_STREAM_MAX_BATCH
 // frames (modes[i]: OFX_FRONTEND_GREY / _BILATERAL / _BILATERAL_FAST; a call that mixes the two bilateral forms launches twice)

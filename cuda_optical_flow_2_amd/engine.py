@@ -1023,7 +1023,8 @@ def video_interpolate(frames, levels: int, window: int, mode: str = "lk_float", 
 
 def _interp_clip(frames, factor):
     """what video_interpolate and video_interpolate_dense require of their clip: (the clip with usable strides, N, H, W)"""
-    assert frames.dim() == 3, "video_interpolate: grey clips only, uint8 [N, H, W] (colour output is not implemented: convert the clip to grey first)"
+    assert frames.dim() == 3, ("video_interpolate: grey clips only, uint8 [N, H, W] (a colour clip [N, H, W, 3] goes through "
+                               "video_interpolate_colour / video_interpolate_colour_dense)")
     N, H, W = _clip_shape(frames)
     assert isinstance(factor, int) and 2 <= factor <= INTERP_MAX_TIMES + 1, f"factor: an integer 2 .. {INTERP_MAX_TIMES + 1}, not {factor!r}"
     assert frames.stride(2) == 1, "frames: unit column stride"
@@ -1035,14 +1036,18 @@ def _interp_clip(frames, factor):
 def _interpolate_rings(frames, fwd, bwd, factor, return_stats, return_displacements):
     """The in-between frames of every pair of a clip from its two level-0 displacement rings, float32 [N-1, H, W, 2]: fwd[p] is the
     displacement frame p -> p+1, and bwd, in the REVERSED run's order, holds frame p+1 -> p in bwd[N-2-p].  The pairs go through
-    ofx_interpolate_frames_batch, up to 16 per launch, frames read in place and fields straight out of the two rings."""
+    ofx_interpolate_frames_batch (a colour clip [N, H, W, 3]: ofx_interpolate_frames_3ch_batch), up to 16 per launch, frames read in
+    place and fields straight out of the two rings."""
     import torch
 
     N, H, W = _clip_shape(frames)
     T = factor - 1
     t, tp = _times([np.float32(k / factor) for k in range(1, factor)])
     L = _lib.load()
-    out = torch.empty((N - 1, T, H, W), dtype=torch.uint8, device=frames.device)
+    colour = frames.dim() == 4
+    row = 3 * W if colour else W    # bytes
+    name = "ofx_interpolate_frames_3ch_batch" if colour else "ofx_interpolate_frames_batch"
+    out = torch.empty((N - 1, T, H, W) + ((3,) if colour else ()), dtype=torch.uint8, device=frames.device)
     stats = torch.empty((N - 1, T, 4), dtype=torch.int64, device=frames.device) if return_stats else None
     pitch = int(frames.stride(1))
     ap = [frames.data_ptr() + p * int(frames.stride(0)) for p in range(N)]
@@ -1052,8 +1057,8 @@ def _interpolate_rings(frames, fwd, bwd, factor, return_stats, return_displaceme
         n = min(16, N - 1 - p0)
         ptrs = [(_vp * n)(*v[p0:p0 + n]) for v in (ap, ap[1:], fp, bp, op, sp)]
         pitches = (C.c_int * n)(*([pitch] * n))
-        check(L.ofx_interpolate_frames_batch(ptrs[0], pitches, ptrs[1], pitches, n, W, H, ptrs[2], ptrs[3], tp, T, ptrs[4], W, H * W,
-                                             ptrs[5] if return_stats else None, _stream_ptr()), "ofx_interpolate_frames_batch")
+        check(getattr(L, name)(ptrs[0], pitches, ptrs[1], pitches, n, W, H, ptrs[2], ptrs[3], tp, T, ptrs[4], row, H * row,
+                               ptrs[5] if return_stats else None, _stream_ptr()), name)
     res = (out,)
     if return_stats:
         res += (stats,)
@@ -1137,4 +1142,105 @@ def video_interpolate_dense(frames, levels: int, window: int, factor: int = 2, i
     frames, N, H, W = _interp_clip(frames, factor)
     fwd = _dense_ring(frames, list(range(N)), levels, window, iters, min_det, max_px, 0, mode, None)
     bwd = _dense_ring(frames, list(range(N - 1, -1, -1)), levels, window, iters, min_det, max_px, 0, mode, None)
+    return _interpolate_rings(frames, fwd, bwd, factor, return_stats, return_displacements)
+
+
+# ---- colour frame interpolation ---------------------------------------------------------------------------------------------------
+
+def interpolate_frames_colour(a: np.ndarray, b: np.ndarray, disp_ab: np.ndarray, disp_ba: np.ndarray, times):
+    """ofx_interpolate_frames_3ch on host arrays: interpolate_frames for a pair of interleaved 3-channel images [h, w, 3] ("colour
+    frame interpolation" in include/ofx.h): one geometry per pixel, every channel blended with it.  Returns (frames uint8
+    [T, h, w, 3], stats int64 [T, 4]), the stats counted once per pixel."""
+    import torch
+
+    L = _lib.load()
+    h, w, _ = a.shape
+    assert a.shape == (h, w, 3) and b.shape == (h, w, 3) and tuple(disp_ab.shape) == (h, w, 2) and tuple(disp_ba.shape) == (h, w, 2)
+    t, tp = _times(times)
+    ta = torch.from_numpy(np.array(a, dtype=np.uint8, order="C")).cuda()    # (copies: the caller's arrays may be read-only)
+    tb = torch.from_numpy(np.array(b, dtype=np.uint8, order="C")).cuda()
+    tab = torch.from_numpy(np.array(disp_ab, dtype=np.float32, order="C")).cuda()
+    tba = torch.from_numpy(np.array(disp_ba, dtype=np.float32, order="C")).cuda()
+    td = torch.zeros((t.size, h, w, 3), dtype=torch.uint8, device="cuda")
+    ts = torch.zeros((t.size, 4), dtype=torch.int64, device="cuda")
+    check(L.ofx_interpolate_frames_3ch(ta.data_ptr(), 3 * w, tb.data_ptr(), 3 * w, w, h, tab.data_ptr(), tba.data_ptr(), tp, int(t.size),
+                                       td.data_ptr(), 3 * w, h * 3 * w, ts.data_ptr(), _stream_ptr()), "ofx_interpolate_frames_3ch")
+    torch.cuda.synchronize()
+    return td.cpu().numpy(), ts.cpu().numpy()
+
+
+def _interp_clip_colour(frames, factor):
+    """what video_interpolate_colour and video_interpolate_colour_dense require of their clip: (the clip with usable strides, N, H, W)"""
+    import torch
+
+    assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and int(frames.shape[3]) == 3, \
+        "video_interpolate_colour: colour clips only, uint8 CUDA tensor [N, H, W, 3] (a grey clip goes through video_interpolate)"
+    N, H, W = _clip_shape(frames)
+    assert isinstance(factor, int) and 2 <= factor <= INTERP_MAX_TIMES + 1, f"factor: an integer 2 .. {INTERP_MAX_TIMES + 1}, not {factor!r}"
+    assert frames.stride(3) == 1 and frames.stride(2) == 3, "frames: unit channel stride and a pixel stride of 3"
+    if frames.stride(1) < 3 * W or frames.stride(0) < 0:
+        frames = frames.contiguous()
+    return frames, N, H, W
+
+
+def video_interpolate_colour(frames, levels: int, window: int, mode: str = "lk_float", factor: int = 2, iters: int = 1, min_det: float = 0.0,
+                             batch: Optional[int] = None, frontend: str = "grey", bilateral=(9, 2.0, 10.0), fast: bool = False,
+                             return_stats: bool = False, return_displacements: bool = False):
+    """video_interpolate for a colour clip: the factor - 1 in-between COLOUR frames of every consecutive pair, by "colour frame
+    interpolation" of include/ofx.h.  The clip goes through the stream pipeline twice with a level-0 displacement ring -- as it is
+    and in reverse frame order -- its colour front end making the grey images the flow is computed on (frontend: "grey", the
+    channel average, or "bilateral", the average then the pre-filter with bilateral = (window, sigma_s, sigma_b), fast as in
+    video_flow.  "main_cu" is refused: it treats the first frame submitted differently from the others, so the two runs would
+    see different images of frames 0 and N-1).  The colour frames are then read in place, at the tensor's own pitch and
+    alignment, by ofx_interpolate_frames_3ch_batch, up to 16 pairs per launch: one launch reads a pair's two fields once and
+    writes all three channels of all its in-between frames.
+
+    frames: uint8 CUDA tensor [N, H, W, 3], N >= 2, unit channel stride and a pixel stride of 3; factor: 2 .. 9.  Returns uint8
+    [N-1, factor-1, H, W, 3]; return_stats and return_displacements as video_interpolate (the stats count pixels, not bytes)."""
+    frames, N, H, W = _interp_clip_colour(frames, factor)
+    assert frontend in ("grey", "bilateral"), \
+        f"frontend: 'grey' or 'bilateral', not {frontend!r} ('main_cu' filters all frames but the first one submitted: the reversed run would see other images)"
+    rings = []
+    for order in (None, range(N - 1, -1, -1)):
+        ring = _ring_for(N, H, W, 0, frames.device, None)
+        _run_clip(frames, levels, window, mode, iters, min_det, batch, frontend, bilateral, fast,
+                  lambda s, ring=ring: s.stream_displacement(ring, 0), order=order)
+        rings.append(ring)
+    return _interpolate_rings(frames, rings[0], rings[1], factor, return_stats, return_displacements)
+
+
+def _grey_clip(frames):
+    """the channel average of a colour clip [N, H, W, 3] on the device (ofx_frontend_1ch in OFX_FRONTEND_GREY mode, 16 frames per
+    call) as a grey clip [N, H, W] with rows pitch_for(W) apart"""
+    import torch
+
+    N, H, W = _clip_shape(frames)
+    L, st = _lib.load(), _stream_ptr()
+    src = frames
+    if not (src.data_ptr() % 4 == 0 and int(src.stride(0)) % 4 == 0 and src.stride(1) >= 3 * W):
+        # (every frame's base 4-byte aligned: rows padded to a multiple of four bytes, as _run_clip does)
+        padded = torch.empty((N, H, 3 * W + (-3 * W) % 4), dtype=torch.uint8, device=frames.device)
+        padded[:, :, :3 * W] = frames.reshape(N, H, 3 * W)
+        src = padded[:, :, :3 * W].unflatten(2, (W, 3))
+    pitch = pitch_for(W)
+    grey = torch.zeros((N, H, pitch), dtype=torch.uint8, device=frames.device)
+    for i0 in range(0, N, 16):
+        n = min(16, N - i0)
+        srcs = (_vp * n)(*[src[i0 + i].data_ptr() for i in range(n)])
+        dsts = (_vp * n)(*[grey[i0 + i].data_ptr() for i in range(n)])
+        check(L.ofx_frontend_1ch(srcs, None, int(src.stride(1)), dsts, None, pitch, n, W, H, None, 1, 9, 2.0, 10.0, st), "ofx_frontend_1ch")
+    torch.cuda.current_stream().synchronize()   # (a padded copy goes with this call)
+    return grey[:, :, :W]
+
+
+def video_interpolate_colour_dense(frames, levels: int, window: int, factor: int = 2, iters: int = 3, min_det: float = 1.0,
+                                   max_px: Optional[float] = None, return_stats: bool = False, return_displacements: bool = False,
+                                   mode: str = "lk_float"):
+    """video_interpolate_colour with the displacements of the coarse-to-fine dense flow: the clip's channel average, made on the
+    device, goes through _dense_ring at level 0 forwards and in reverse frame order, and the two rings and the colour frames (read
+    in place) then go through ofx_interpolate_frames_3ch_batch.  Arguments and results as video_interpolate_dense."""
+    frames, N, H, W = _interp_clip_colour(frames, factor)
+    grey = _grey_clip(frames)
+    fwd = _dense_ring(grey, list(range(N)), levels, window, iters, min_det, max_px, 0, mode, None)
+    bwd = _dense_ring(grey, list(range(N - 1, -1, -1)), levels, window, iters, min_det, max_px, 0, mode, None)
     return _interpolate_rings(frames, fwd, bwd, factor, return_stats, return_displacements)

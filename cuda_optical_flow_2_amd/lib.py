@@ -147,6 +147,9 @@ _SIGS = {
     "ofx_interpolate_frames": [_vp, _i, _vp, _i, _i, _i, _vp, _vp, C.POINTER(C.c_float), _i, _vp, _i, C.c_size_t, _vp, _vp],
     "ofx_interpolate_frames_batch": [C.POINTER(_vp), C.POINTER(_i), C.POINTER(_vp), C.POINTER(_i), _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp),
                                      C.POINTER(C.c_float), _i, C.POINTER(_vp), _i, C.c_size_t, C.POINTER(_vp), _vp],
+    "ofx_interpolate_frames_3ch": [_vp, _i, _vp, _i, _i, _i, _vp, _vp, C.POINTER(C.c_float), _i, _vp, _i, C.c_size_t, _vp, _vp],
+    "ofx_interpolate_frames_3ch_batch": [C.POINTER(_vp), C.POINTER(_i), C.POINTER(_vp), C.POINTER(_i), _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp),
+                                         C.POINTER(C.c_float), _i, C.POINTER(_vp), _i, C.c_size_t, C.POINTER(_vp), _vp],
     "ofx_session_stream_frontend": [_vp, _i, _i, _d, _d, _i],
     "ofx_session_stream_submit_3ch": [_vp, _vp, _i, _vp, C.POINTER(_i)],
     "ofx_session_stream_submit_frames_3ch": [_vp, C.POINTER(_vp), C.POINTER(_i), _i, _i, _vp, C.POINTER(_i)],

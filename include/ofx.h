@@ -448,6 +448,27 @@ int ofx_interpolate_frames_batch(const uint8_t *const *d_a, const int *a_pitches
                                  uint8_t *const *d_dst, int dst_pitch, size_t time_stride_bytes,
                                  int64_t *const *d_stats /* may be NULL */, void *stream);
 
+/* ---- colour frame interpolation ------------------------------------------------
+ * "frame interpolation" above, for interleaved 3-channel u8 planes a and b of w x h pixels, each with its own row pitch in bytes
+ * >= 3*w; no alignment is required of a plane, its pitch or the destination, and the channel order does not matter.  Dab, Dba,
+ * the times and the host step for c00 / c01 / c10 are exactly as there.  Steps 1 to 4 and the class are computed ONCE per pixel;
+ * step 5's blend and step 6's value and rounding are applied to each channel with the same fx, fy and class.  Hence the byte at
+ * channel c of a pixel is, bit for bit, what "frame interpolation" gives for the planes a[..., c] and b[..., c].  stats are its
+ * four words per (pair, time), counted once per pixel, not per channel.  The motion of a picture is one geometry: three grey calls
+ * would read both fields three times.  No tap reads outside the (h-1)*pitch + 3*w bytes of a plane or the w*h*8 bytes of a field,
+ * whatever the fields hold; bytes of a destination row beyond column 3*w - 1 are left untouched.
+ *
+ * ofx_interpolate_frames_3ch / ofx_interpolate_frames_3ch_batch: as ofx_interpolate_frames / ofx_interpolate_frames_batch, frame k
+ * at d_dst3 + k*time_stride_bytes, rows dst_pitch >= 3*w apart.  The refusals are theirs, every pitch compared against 3*w, and a
+ * plane of 2^31 bytes or more: OFX_E_INVALID, before anything is enqueued.  The host arrays are read before the call returns. */
+int ofx_interpolate_frames_3ch(const uint8_t *d_a3, int a_pitch, const uint8_t *d_b3, int b_pitch, int w, int h,
+                               const float *d_disp_ab, const float *d_disp_ba, const float *h_times, int n_times,
+                               uint8_t *d_dst3, int dst_pitch, size_t time_stride_bytes, int64_t *d_stats /* may be NULL */, void *stream);
+int ofx_interpolate_frames_3ch_batch(const uint8_t *const *d_a3, const int *a_pitches, const uint8_t *const *d_b3, const int *b_pitches,
+                               int n, int w, int h, const float *const *d_disp_ab, const float *const *d_disp_ba, const float *h_times,
+                               int n_times, uint8_t *const *d_dst3, int dst_pitch, size_t time_stride_bytes,
+                               int64_t *const *d_stats /* may be NULL */, void *stream);
+
 /* ---- coarse-to-fine propagation ------------------------------------------------
  * The reference hands a level ONE vector of the level above -- pixel 0's, as a global translation (ofx_shift_vector) -- and every
  * consumer of a displacement inherits that: beyond about 2 px per frame, or with two motions in one scene, the local estimate is
