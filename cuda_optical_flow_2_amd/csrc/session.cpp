@@ -419,15 +419,13 @@ extern "C" int ofx_session_run_flow(ofx_session *s, void *stream)
     return ofx_session_run_levels(s, stream);
 }
 
-// The pair's dense flow ("coarse-to-fine propagation", include/ofx.h): the top level as run_flow runs it, then level by level one
-// prolongation (which also writes the first warped image) and `iters` accumulating single-level LK launches.  The warped images
-// alternate between sh[0][k] and sh[1][k]: nothing is shifted here, so both are free.
-extern "C" int ofx_session_run_flow_dense(ofx_session *s, float max_px, void *stream)
+// what both dense calls require of the session and of max_px before anything is enqueued; `who` names the entry point
+static int dense_check(ofx_session *s, const char *who, float max_px)
 {
-    OFX_REQUIRE(s, "ofx_session_run_flow_dense: null session");
-    OFX_REQUIRE(__builtin_isfinite(max_px) && max_px >= 0.0f, "ofx_session_run_flow_dense: max_px must be finite and >= 0 (0 = off)");
-    auto unsupported = [](const char *what) {
-        ofx_set_error("ofx_session_run_flow_dense: %s", what);
+    OFX_REQUIRE(s, "%s: null session", who);
+    OFX_REQUIRE(__builtin_isfinite(max_px) && max_px >= 0.0f, "%s: max_px must be finite and >= 0 (0 = off)", who);
+    auto unsupported = [who](const char *what) {
+        ofx_set_error("%s: %s", who, what);
         return OFX_E_UNSUPPORTED;
     };
     if (s->p.sharded) return unsupported("not available on a sharded session (a level's warp crosses shard rows)");
@@ -435,12 +433,22 @@ extern "C" int ofx_session_run_flow_dense(ofx_session *s, float max_px, void *st
     if (s->p.borrow_frames)
         return unsupported("not available with borrow_frames (level 0 of the next frame is a warp source, which must be followed by three readable bytes)");
     if (!s->have_prev || !s->have_next) {
-        ofx_set_error("ofx_session_run_flow_dense: need a previous and a next frame (load, build, swap, load, build)");
+        ofx_set_error("%s: need a previous and a next frame (load, build, swap, load, build)", who);
         return OFX_E_STATE;
     }
     const int L = s->p.levels, iters = s->p.iters > 1 ? s->p.iters : 1;
     for (int k = 0; k + 1 < L; ++k) // (the launches that also write the warped image address a level through 32-bit offsets)
         if (iters > 1 && !ofx_plan::fits_buffer_offsets(s->h[k], s->pitch[k], s->h[k], s->w[k])) return unsupported("a level of 2 GB or more");
+    return OFX_OK;
+}
+
+// The pair's dense flow ("coarse-to-fine propagation", include/ofx.h): the top level as run_flow runs it, then level by level one
+// prolongation (which also writes the first warped image) and `iters` accumulating single-level LK launches.  The warped images
+// alternate between sh[0][k] and sh[1][k]: nothing is shifted here, so both are free.
+extern "C" int ofx_session_run_flow_dense(ofx_session *s, float max_px, void *stream)
+{
+    OFX_TRY(dense_check(s, "ofx_session_run_flow_dense", max_px));
+    const int L = s->p.levels, iters = s->p.iters > 1 ? s->p.iters : 1;
     OFX_TRY(lk_all_levels(s, s->uv_cur(), stream, L - 1));
     for (int k = L - 2; k >= 0; --k) {
         const ofx_prolong_desc pd{s->flow[k + 1], s->w[k + 1], s->h[k + 1], s->flow[k], s->w[k], s->h[k], OFX_ITER_SCALE, max_px,
@@ -450,6 +458,60 @@ extern "C" int ofx_session_run_flow_dense(ofx_session *s, float max_px, void *st
             ofx_lk_desc lk{s->plane[0][k], s->sh[i & 1][k], level_geom(s, k, 0, s->h[k]), s->flow[k], 0, nullptr, 1, s->p.min_det};
             if (i + 1 < iters) lk.d_warp_src = s->plane[1][k], lk.d_warp_out = s->sh[(i + 1) & 1][k], lk.warp_scale = OFX_ITER_SCALE;
             OFX_TRY(timed_lk_launch(s, &lk, 1, stream));
+        }
+    }
+    return OFX_OK;
+}
+
+// the caller's second flow pyramid of ofx_session_run_flow_dense_median: level k at the sum of the sizes of the levels below it
+static size_t median_scratch_offset(const ofx_session *s, int k)
+{
+    size_t o = 0;
+    for (int j = 0; j < k; ++j) o += (size_t)s->w[j] * (size_t)s->h[j] * 8;
+    return o;
+}
+
+extern "C" int ofx_session_dense_median_scratch_bytes(ofx_session *s, size_t *bytes)
+{
+    OFX_REQUIRE(s && bytes, "ofx_session_dense_median_scratch_bytes: bad arguments");
+    *bytes = median_scratch_offset(s, s->p.levels);
+    return OFX_OK;
+}
+
+// "A pair's dense flow with median" (the block "flow median", include/ofx.h): run_flow_dense's calls, with one ofx_flow_median after
+// the top level and after every accumulating launch below it.  The median is out of place: a level's flow alternates between
+// flow[k] and the caller's scratch, starting where `iters` flips end in flow[k]; the medians, not the LK launches, write the next
+// warped image (from the filtered vectors).
+extern "C" int ofx_session_run_flow_dense_median(ofx_session *s, float max_px, int radius, void *d_scratch, size_t scratch_bytes, void *stream)
+{
+    const char *who = "ofx_session_run_flow_dense_median";
+    OFX_TRY(dense_check(s, who, max_px));
+    OFX_REQUIRE(radius == 1 || radius == 2, "%s: the radius %d is not 1 (3x3) or 2 (5x5)", who, radius);
+    OFX_REQUIRE(d_scratch, "%s: the scratch is null", who);
+    OFX_REQUIRE(((uintptr_t)d_scratch & 7) == 0, "%s: the scratch must be 8-byte aligned", who);
+    const int L = s->p.levels, iters = s->p.iters > 1 ? s->p.iters : 1;
+    OFX_REQUIRE(scratch_bytes >= median_scratch_offset(s, L), "%s: the scratch holds %zu bytes, the flow pyramid has %zu (ofx_session_dense_median_scratch_bytes)",
+                who, scratch_bytes, median_scratch_offset(s, L));
+    auto scratch = [&](int k) { return reinterpret_cast<float *>(static_cast<char *>(d_scratch) + median_scratch_offset(s, k)); };
+    auto median = [&](int k, const float *from, float *to, uint8_t *warped) {
+        const ofx_median_desc md{from, to, s->w[k], s->h[k], radius, OFX_ITER_SCALE, warped ? s->plane[1][k] : nullptr, warped ? s->pitch[k] : 0,
+                                 warped, warped ? s->pitch[k] : 0};
+        return timed_launch(s, OFX_TIME_WARP, stream, [&] { return ofx_flow_median(&md, 1, stream); });
+    };
+    OFX_TRY(lk_all_levels(s, s->uv_cur(), stream, L - 1));
+    OFX_TRY(median(L - 1, s->flow[L - 1], scratch(L - 1), nullptr));
+    OFX_HIP(hipMemcpyAsync(s->flow[L - 1], scratch(L - 1), (size_t)s->w[L - 1] * (size_t)s->h[L - 1] * 8, hipMemcpyDeviceToDevice, ofx_stream(stream)));
+    for (int k = L - 2; k >= 0; --k) {
+        float *buf[2] = {s->flow[k], scratch(k)};
+        int cur = iters & 1; // (iters flips from here end in buf[0], the session's plane)
+        const ofx_prolong_desc pd{s->flow[k + 1], s->w[k + 1], s->h[k + 1], buf[cur], s->w[k], s->h[k], OFX_ITER_SCALE, max_px,
+                                  s->plane[1][k], s->pitch[k], s->sh[0][k], s->pitch[k]};
+        OFX_TRY(timed_launch(s, OFX_TIME_WARP, stream, [&] { return ofx_flow_prolong(&pd, 1, stream); }));
+        for (int i = 0; i < iters; ++i) {
+            const ofx_lk_desc lk{s->plane[0][k], s->sh[i & 1][k], level_geom(s, k, 0, s->h[k]), buf[cur], 0, nullptr, 1, s->p.min_det};
+            OFX_TRY(timed_lk_launch(s, &lk, 1, stream));
+            OFX_TRY(median(k, buf[cur], buf[cur ^ 1], i + 1 < iters ? s->sh[(i + 1) & 1][k] : nullptr));
+            cur ^= 1;
         }
     }
     return OFX_OK;

@@ -88,6 +88,7 @@ class Session:
         self.strict = bool(strict)
         self._status = 0
         self.width, self.height, self.levels, self.window, self.mode = width, height, levels, window, mode
+        self.device, self._median_scratch = device, None
         p = Params()
         p.width, p.height, p.levels, p.window, p.mode, p.device = width, height, levels, window, MODES[mode], device
         p.iters = iters
@@ -153,12 +154,26 @@ class Session:
     def run_flow(self, stream=None):
         check(self.L.ofx_session_run_flow(self._h, _stream_ptr(stream)), "run_flow")
 
-    def run_flow_dense(self, max_px: Optional[float] = None, stream=None):
+    def run_flow_dense(self, max_px: Optional[float] = None, stream=None, median: int = 0):
         """ofx_session_run_flow_dense: the pair's dense flow of "coarse-to-fine propagation" in include/ofx.h, in run_flow's place
         -- every level below the top starts from the prolonged flow of the level above instead of one global shift.  max_px: a
-        coarse vector longer than this many pixels (of its own level) is dropped; None: the window size, 0: no limit."""
+        coarse vector longer than this many pixels (of its own level) is dropped; None: the window size, 0: no limit.
+        median: 0, or the radius (1: 3x3, 2: 5x5) of the median that filters the flow after the top level and after every
+        iteration below it (ofx_session_run_flow_dense_median, "flow median" in include/ofx.h); the session object then keeps a
+        second flow pyramid as a torch tensor, made at the first such call."""
         max_px = float(self.window) if max_px is None else float(max_px)
-        check(self.L.ofx_session_run_flow_dense(self._h, max_px, _stream_ptr(stream)), "run_flow_dense")
+        if not median:
+            check(self.L.ofx_session_run_flow_dense(self._h, max_px, _stream_ptr(stream)), "run_flow_dense")
+            return
+        if self._median_scratch is None:
+            import torch
+
+            n = C.c_size_t()
+            check(self.L.ofx_session_dense_median_scratch_bytes(self._h, C.byref(n)), "dense_median_scratch_bytes")
+            self._median_scratch = torch.empty(n.value // 4, dtype=torch.float32, device=f"cuda:{self.device}")
+        t = self._median_scratch
+        check(self.L.ofx_session_run_flow_dense_median(self._h, max_px, int(median), t.data_ptr(), t.numel() * 4, _stream_ptr(stream)),
+              "run_flow_dense_median")
 
     def run_flow_sequential(self, stream=None):
         check(self.L.ofx_session_run_flow_sequential(self._h, _stream_ptr(stream)), "run_flow_sequential")
@@ -1069,10 +1084,32 @@ def _interpolate_rings(frames, fwd, bwd, factor, return_stats, return_displaceme
 
 # ---- coarse-to-fine dense flow ----------------------------------------------------------------------------------------------------
 
+def flow_median(field: np.ndarray, radius: int = 2, src: Optional[np.ndarray] = None, scale: float = ITER_SCALE):
+    """ofx_flow_median on host arrays ("flow median" in include/ofx.h): the 3x3 (radius 1) or 5x5 (radius 2) median of a flow
+    field float32 [h, w, 2], per component, border replicated, a vector that is not finite read as (0, 0).  With src (uint8
+    [h, w]) returns (filtered field, src warped by scale * the filtered field) from the one fused launch."""
+    import torch
+    from .lib import MedianDesc
+
+    L = _lib.load()
+    h, w, two = field.shape
+    assert two == 2 and (src is None or src.shape == (h, w))
+    tf = torch.from_numpy(np.array(field, dtype=np.float32, order="C")).cuda()    # (copies: the caller's array may be read-only)
+    to = torch.zeros_like(tf)
+    d = MedianDesc(tf.data_ptr(), to.data_ptr(), w, h, int(radius), float(scale), None, 0, None, 0)
+    if src is not None:
+        ts, pitch = _u8_plane(src)
+        td = torch.zeros_like(ts)
+        d.d_src, d.src_pitch, d.d_dst, d.dst_pitch = ts.data_ptr(), pitch, td.data_ptr(), pitch
+    check(L.ofx_flow_median(C.byref(d), 1, _stream_ptr()), "ofx_flow_median")
+    torch.cuda.synchronize()
+    return to.cpu().numpy() if src is None else (to.cpu().numpy(), td[:, :w].cpu().numpy())
+
+
 def flow_pair_dense(prev1: np.ndarray, next1: np.ndarray, levels: int, window: int, iters: int = 3, min_det: float = 1.0,
-                    max_px: Optional[float] = None, mode: str = "lk_float") -> List[np.ndarray]:
+                    max_px: Optional[float] = None, mode: str = "lk_float", median: int = 0) -> List[np.ndarray]:
     """Whole pair through a Session's run_flow_dense: the dense flow pyramid as host arrays.  OFX_ITER_SCALE * flow[k] is level
-    k's motion in pixels."""
+    k's motion in pixels.  median: Session.run_flow_dense's (0: none; 1, 2: the radius of the flow median after every iteration)."""
     import torch
 
     h, w = prev1.shape
@@ -1081,14 +1118,14 @@ def flow_pair_dense(prev1: np.ndarray, next1: np.ndarray, levels: int, window: i
         s.push_frame_host(prev1)
         s.set_frame_host(next1)
         s.build_pyramid()
-        s.run_flow_dense(max_px)
+        s.run_flow_dense(max_px, median=median)
         torch.cuda.synchronize()
         return [s.flow_host(k) for k in range(levels)]
     finally:
         s.close()
 
 
-def _dense_ring(frames, order, levels, window, iters, min_det, max_px, level, mode, out):
+def _dense_ring(frames, order, levels, window, iters, min_det, max_px, level, mode, out, median=0):
     """the displacement at `level` of every consecutive pair of the clip, its frames taken in `order`, pair at a time: set_frame_device /
     build_pyramid / run_flow_dense / ofx_flow_displacement (no global shift) into the pair's slot / swap, all on the current stream"""
     import torch
@@ -1111,7 +1148,7 @@ def _dense_ring(frames, order, levels, window, iters, min_det, max_px, level, mo
         for p in range(1, N):
             s.set_frame_device(frames[order[p]])
             s.build_pyramid()
-            s.run_flow_dense(max_px)
+            s.run_flow_dense(max_px, median=median)
             flow, _ = s.flow(level)
             check(L.ofx_flow_displacement(flow.data_ptr(), W >> level, H >> level, None, ITER_SCALE, out[p - 1].data_ptr(), st), "ofx_flow_displacement")
             s.swap()
@@ -1122,26 +1159,27 @@ def _dense_ring(frames, order, levels, window, iters, min_det, max_px, level, mo
 
 
 def video_displacement_dense(frames, levels: int, window: int, iters: int = 3, min_det: float = 1.0, max_px: Optional[float] = None,
-                             level: int = 0, out=None, mode: str = "lk_float"):
+                             level: int = 0, out=None, mode: str = "lk_float", median: int = 0):
     """The motion in pixels of every consecutive pair of a grey clip at `level`, by the coarse-to-fine dense flow
     (Session.run_flow_dense; "coarse-to-fine propagation" in include/ofx.h): OFX_ITER_SCALE times the level's flow, every level
     started from the whole flow of the level above.  Unlike video_displacement it follows motions of many pixels per frame and
     several motions in one scene; it runs pair at a time, levels one after the other.  frames: uint8 CUDA tensor [N, H, W], N >= 2,
     unit column stride.  Returns float32 [N-1, H >> level, W >> level, 2]: out[p-1] is the displacement frame p-1 -> frame p; `out`
-    may supply the tensor.  mode: "lk_float" or "lk_float_fast"."""
+    may supply the tensor.  mode: "lk_float" or "lk_float_fast".  median: 0, or the radius (1, 2) of the flow median that filters
+    every level's flow after every iteration ("flow median" in include/ofx.h): isolated wrong vectors go, motion edges stay."""
     N = _clip_shape(frames)[0]
-    return _dense_ring(frames, list(range(N)), levels, window, iters, min_det, max_px, level, mode, out)
+    return _dense_ring(frames, list(range(N)), levels, window, iters, min_det, max_px, level, mode, out, median)
 
 
 def video_interpolate_dense(frames, levels: int, window: int, factor: int = 2, iters: int = 3, min_det: float = 1.0,
                             max_px: Optional[float] = None, return_stats: bool = False, return_displacements: bool = False,
-                            mode: str = "lk_float"):
+                            mode: str = "lk_float", median: int = 0):
     """video_interpolate with the displacements of the coarse-to-fine dense flow: the clip goes through _dense_ring at level 0 as it
     is and in reverse frame order (the frames are not copied), and the two rings then go through ofx_interpolate_frames_batch as
-    video_interpolate's do.  Arguments and results as there."""
+    video_interpolate's do.  Arguments and results as there; median as video_displacement_dense's."""
     frames, N, H, W = _interp_clip(frames, factor)
-    fwd = _dense_ring(frames, list(range(N)), levels, window, iters, min_det, max_px, 0, mode, None)
-    bwd = _dense_ring(frames, list(range(N - 1, -1, -1)), levels, window, iters, min_det, max_px, 0, mode, None)
+    fwd = _dense_ring(frames, list(range(N)), levels, window, iters, min_det, max_px, 0, mode, None, median)
+    bwd = _dense_ring(frames, list(range(N - 1, -1, -1)), levels, window, iters, min_det, max_px, 0, mode, None, median)
     return _interpolate_rings(frames, fwd, bwd, factor, return_stats, return_displacements)
 
 
@@ -1235,12 +1273,12 @@ def _grey_clip(frames):
 
 def video_interpolate_colour_dense(frames, levels: int, window: int, factor: int = 2, iters: int = 3, min_det: float = 1.0,
                                    max_px: Optional[float] = None, return_stats: bool = False, return_displacements: bool = False,
-                                   mode: str = "lk_float"):
+                                   mode: str = "lk_float", median: int = 0):
     """video_interpolate_colour with the displacements of the coarse-to-fine dense flow: the clip's channel average, made on the
     device, goes through _dense_ring at level 0 forwards and in reverse frame order, and the two rings and the colour frames (read
     in place) then go through ofx_interpolate_frames_3ch_batch.  Arguments and results as video_interpolate_dense."""
     frames, N, H, W = _interp_clip_colour(frames, factor)
     grey = _grey_clip(frames)
-    fwd = _dense_ring(grey, list(range(N)), levels, window, iters, min_det, max_px, 0, mode, None)
-    bwd = _dense_ring(grey, list(range(N - 1, -1, -1)), levels, window, iters, min_det, max_px, 0, mode, None)
+    fwd = _dense_ring(grey, list(range(N)), levels, window, iters, min_det, max_px, 0, mode, None, median)
+    bwd = _dense_ring(grey, list(range(N - 1, -1, -1)), levels, window, iters, min_det, max_px, 0, mode, None, median)
     return _interpolate_rings(frames, fwd, bwd, factor, return_stats, return_displacements)

@@ -48,6 +48,12 @@ class ProlongDesc(C.Structure):
                 ("dst_pitch", C.c_int)]
 
 
+class MedianDesc(C.Structure):
+    """ofx_median_desc (include/ofx.h, "flow median")"""
+    _fields_ = [("d_src_flow", C.c_void_p), ("d_dst_flow", C.c_void_p), ("w", C.c_int), ("h", C.c_int), ("radius", C.c_int),
+                ("scale", C.c_float), ("d_src", C.c_void_p), ("src_pitch", C.c_int), ("d_dst", C.c_void_p), ("dst_pitch", C.c_int)]
+
+
 class LkDesc(C.Structure):
     """ofx_lk_desc (include/ofx.h): one level of an ofx_lk_levels / ofx_corner_flows launch"""
     _fields_ = [("d_prev", C.c_void_p), ("d_next", C.c_void_p), ("geom", Geom), ("d_flow", C.c_void_p), ("flow_row0", C.c_int),
@@ -144,6 +150,9 @@ _SIGS = {
     "ofx_session_displacement_of": [_vp, _i, C.POINTER(_vp)],
     "ofx_flow_prolong": [C.POINTER(ProlongDesc), _i, _vp],
     "ofx_session_run_flow_dense": [_vp, C.c_float, _vp],
+    "ofx_flow_median": [C.POINTER(MedianDesc), _i, _vp],
+    "ofx_session_run_flow_dense_median": [_vp, C.c_float, _i, _vp, C.c_size_t, _vp],
+    "ofx_session_dense_median_scratch_bytes": [_vp, C.POINTER(C.c_size_t)],
     "ofx_interpolate_frames": [_vp, _i, _vp, _i, _i, _i, _vp, _vp, C.POINTER(C.c_float), _i, _vp, _i, C.c_size_t, _vp, _vp],
     "ofx_interpolate_frames_batch": [C.POINTER(_vp), C.POINTER(_i), C.POINTER(_vp), C.POINTER(_i), _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp),
                                      C.POINTER(C.c_float), _i, C.POINTER(_vp), _i, C.c_size_t, C.POINTER(_vp), _vp],

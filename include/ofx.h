@@ -517,6 +517,46 @@ typedef struct ofx_prolong_desc {
 } ofx_prolong_desc;
 int ofx_flow_prolong(const ofx_prolong_desc *levels, int n, void *stream);
 
+/* ---- flow median ---------------------------------------------------------------
+ * Lucas-Kanade on weak texture leaves isolated wrong vectors, prolongation spreads each of them over four fine pixels and their
+ * neighbours, and max_px only removes the wildest.  The standard remedy is a median filter on the intermediate flow fields after
+ * every warping step (Sun, Roth, Black, "Secrets of optical flow estimation and their principles").  A median is a pure selection:
+ * it needs no rounding.  THE definition (everything else quotes it), for a field f (w x h, interleaved (u, v) float32, tightly
+ * packed) and a radius r in {1, 2}, i.e. a 3x3 or 5x5 window:
+ *   1. Sanitise.  A vector with a component that is not finite is read as (+0, +0): prolongation's finiteness rule, without max_px.
+ *   2. Select.  The window is the (2r+1)^2 vectors at (clamp(x + i, 0, w - 1), clamp(y + j, 0, h - 1)), |i|, |j| <= r: the border
+ *      is replicated, so the count is always odd, also when w or h is smaller than the window.  Per component on its own, the
+ *      result is the middle one of the (2r+1)^2 sanitised values ordered by value.  A selection: no arithmetic, no averaging.
+ *   3. Zeros.  -0 and +0 compare equal, so a result equal to zero is stored as +0 (m + 0.0f, one add); every other result has the
+ *      selected value's bits, denormals kept.
+ *   4. warped (optional) = what ofx_warp_levels writes for {src, the filtered field, scale}, byte for byte; the "not warped" rule
+ *      of prolongation's step 4 applies.
+ *
+ * A PAIR'S DENSE FLOW WITH MEDIAN, for L levels, iters >= 1 and a radius r: the pair's dense flow above with one median after
+ * every step that leaves a flow --
+ *   level L-1:  as above, then flow_{L-1} = median(flow_{L-1}; r).
+ *   level k < L-1:  flow_k = prolong(flow_{k+1}; OFX_ITER_SCALE, max_px);  W = warped(next_k, flow_k);  then iters times:
+ *               flow_k += LK(prev_k, W);  flow_k = median(flow_k; r);  and W = ofx_warp_levels(next_k, flow_k, OFX_ITER_SCALE) for
+ *               all but the last.
+ *
+ * ofx_flow_median: 1 <= n <= OFX_STREAM_MAX_BATCH items in ONE launch; they may differ in size and radius.  d_src / d_dst (both or
+ * neither): the launch also writes step 4's image, from the filtered vectors it holds in registers; d_src has row pitch src_pitch
+ * >= w, d_dst is a plane that does not overlap it (row pitch dst_pitch >= w; the bytes beyond column w - 1 of a row are left
+ * untouched).  d_src_flow and d_dst_flow 8-byte aligned and not overlapping (a median is out of place); w, h > 0, w * h < 2^28 and
+ * a plane below 2^31 bytes; radius 1 or 2; scale finite; otherwise OFX_E_INVALID, before anything is enqueued.  No tap reads
+ * outside the w * h * 8 bytes of d_src_flow or the (h - 1) * pitch + w bytes of d_src, whatever the field holds. */
+typedef struct ofx_median_desc {
+    const float *d_src_flow;
+    float *d_dst_flow; /* 8-byte aligned, tightly packed, not overlapping d_src_flow */
+    int w, h, radius;
+    float scale;          /* for the warp only */
+    const uint8_t *d_src; /* warp source; NULL = flow only */
+    int src_pitch;
+    uint8_t *d_dst; /* warped image; bytes beyond column w-1 untouched */
+    int dst_pitch;
+} ofx_median_desc;
+int ofx_flow_median(const ofx_median_desc *items, int n, void *stream);
+
 /* ---- layout helpers ------------------------------------------------------ */
 int ofx_extract_ch0(const uint8_t *d_src3, uint8_t *d_dst1, int w, int h, int dst_pitch, void *stream);
 int ofx_replicate_3ch(const uint8_t *d_src1, int src_pitch, uint8_t *d_dst3, int w, int h, void *stream);
@@ -725,6 +765,18 @@ int ofx_session_run_levels(ofx_session *s, void *stream);
  * readable bytes of ofx_lk_desc.d_warp_src).  OFX_E_STATE without a previous and a next frame; max_px negative or not finite:
  * OFX_E_INVALID. */
 int ofx_session_run_flow_dense(ofx_session *s, float max_px, void *stream);
+/* "A pair's dense flow with median" of the block "flow median" above, in ofx_session_run_flow_dense's place: the same calls, and one
+ * ofx_flow_median (radius 1 or 2; timing kind OFX_TIME_WARP) after the top level and after every accumulating launch below it.  A
+ * median is out of place, so a level's flow alternates between the session's flow plane and d_scratch: a second flow pyramid that
+ * the CALLER owns, like the output rings (level k at the sum of the sizes of the levels below it, w_k * h_k * 8 bytes each;
+ * ofx_session_dense_median_scratch_bytes tells the total; 8-byte aligned).  Below the top level the accumulating launches write no
+ * warped image: all but the last median of a level write it, from the filtered vectors, into the level's other shifted-scratch
+ * plane.  Afterwards ofx_session_flow(s, k) holds the filtered flow of every level, whatever iters is (a level starts in the buffer
+ * that makes its last median end in the session's plane; the top level's one median is copied back).  Never allocates, never
+ * synchronises; the scratch holds nothing the next call needs.  Refusals: ofx_session_run_flow_dense's, and OFX_E_INVALID for a
+ * radius other than 1 or 2 and a scratch that is null, not 8-byte aligned or smaller than the total. */
+int ofx_session_run_flow_dense_median(ofx_session *s, float max_px, int radius, void *d_scratch, size_t scratch_bytes, void *stream);
+int ofx_session_dense_median_scratch_bytes(ofx_session *s, size_t *bytes);
 /* The same result the reference's way: per level ofx_session_compute_uv then ofx_session_run_level, coarse to fine. */
 int ofx_session_run_flow_sequential(ofx_session *s, void *stream);
 /* Shift vector of `level` from the coarser flows' pixel 0 into the session's uv slot (meaningful on the rank that

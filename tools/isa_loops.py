@@ -1,11 +1,13 @@
 """Instruction histogram of the LK march loops of one kernel in an ISA listing (hipcc -S --cuda-device-only).
-usage: python tools/isa_loops.py file.s <kernel name substring> [unroll=3]
-Prints NumVgprs / scratch, then for every loop (of any depth; its own blocks only) that holds v_dot2c: VALU / SALU / memory instructions per step (loop body / unroll),
+usage: python tools/isa_loops.py file.s <kernel name substring> [unroll=3] [op=v_dot2c_i32_i16_e32]
+Prints NumVgprs / scratch, then for every loop (of any depth; its own blocks only) that holds `op` (v_dot2c: the LK marches; v_min_f32_e32: the
+flow median's quad march, unroll 1, one loop per radius): VALU / SALU / memory instructions per step (loop body / unroll),
 split into the two issue classes of tools/ubench/valu_rates.hip (cheap: plain 32-bit add / sub / and / or / xor / mov / fp32 add, mul, fma;
 full: everything else) and an estimate of the VALU time per step from the measured rates (1.15 / 1.85 ns, v_rcp_f64 6.85)."""
 import collections, re, sys
 path, name = sys.argv[1], sys.argv[2]
 unroll = int(sys.argv[3]) if len(sys.argv) > 3 else 3
+op = sys.argv[4] if len(sys.argv) > 4 else "v_dot2c_i32_i16_e32"
 lines = open(path).read().split("\n")
 start = next(i for i, l in enumerate(lines) if l.startswith("_Z") and name in l.split(":")[0] and ":" in l)
 end = next(i for i in range(start, len(lines)) if "s_endpgm" in lines[i])
@@ -39,7 +41,7 @@ for a, (depth, seg) in loops.items():
         if not l or l.startswith(";") or l.startswith("."):
             continue
         ops[l.split()[0]] += 1
-    if not ops["v_dot2c_i32_i16_e32"]:
+    if not ops[op]:
         continue
     valu = sum(c for o, c in ops.items() if o.startswith("v_"))
     cheap = sum(c for o, c in ops.items() if o in CHEAP)
