@@ -1282,3 +1282,105 @@ def video_interpolate_colour_dense(frames, levels: int, window: int, factor: int
     fwd = _dense_ring(grey, list(range(N)), levels, window, iters, min_det, max_px, 0, mode, None, median)
     bwd = _dense_ring(grey, list(range(N - 1, -1, -1)), levels, window, iters, min_det, max_px, 0, mode, None, median)
     return _interpolate_rings(frames, fwd, bwd, factor, return_stats, return_displacements)
+
+
+# ---- texture strength and feature selection --------------------------------------------------------------------------------------
+
+def _texture_plane(img):
+    """(tensor that owns the plane, pointer, pitch, w, h) of an (h, w) uint8 host array or CUDA tensor; a CUDA tensor is read in
+    place when its rows are a multiple of 4 bytes apart and 4-byte aligned, otherwise through a padded copy"""
+    import torch
+
+    if isinstance(img, torch.Tensor) and img.is_cuda:
+        assert img.dtype == torch.uint8 and img.dim() == 2, "img: uint8 [h, w]"
+        h, w = (int(v) for v in img.shape)
+        if (img.stride(1) == 1 or w == 1) and img.stride(0) % 4 == 0 and img.stride(0) >= w and img.data_ptr() % 4 == 0:
+            return img, img.data_ptr(), int(img.stride(0)), w, h
+        t = torch.zeros((h, pitch_for(w)), dtype=torch.uint8, device=img.device)
+        t[:, :w] = img
+        return t, t.data_ptr(), pitch_for(w), w, h
+    arr = np.asarray(img)
+    assert arr.dtype == np.uint8 and arr.ndim == 2, "img: uint8 [h, w]"
+    t, pitch = _u8_plane(arr)
+    return t, t.data_ptr(), pitch, arr.shape[1], arr.shape[0]
+
+
+def texture_strength(img, window: int):
+    """The texture strength of a uint8 plane [h, w] (host array or CUDA tensor) for an odd window 3 .. 23 ("texture strength and
+    feature selection" in include/ofx.h): the smaller eigenvalue of the window's structure tensor, float32 [h, w], +0 where the
+    window is flat or holds a single edge.  A host array comes back as an array, a CUDA tensor as a CUDA tensor."""
+    import torch
+    from .lib import TextureDesc
+
+    keep, ptr, pitch, w, h = _texture_plane(img)
+    out = torch.empty((h, w), dtype=torch.float32, device=keep.device)
+    d = TextureDesc(ptr, pitch, w, h, out.data_ptr(), w, None, None, None, 0, 0, 0.0)
+    check(_lib.load().ofx_texture_features(C.byref(d), 1, int(window), _stream_ptr()), "ofx_texture_features")
+    if isinstance(img, torch.Tensor):
+        return out
+    torch.cuda.synchronize()
+    return out.cpu().numpy()
+
+
+def _good_features_device(ptr, pitch, w, h, window, cell, border, min_strength, max_points, device):
+    """(points float32 [n, 2], strengths float32 [n]) as CUDA tensors, of a plane on the device"""
+    import torch
+    from .lib import TextureDesc
+
+    L, st = _lib.load(), _stream_ptr()
+    border = window // 2 + 1 if border is None else int(border)
+    ncx, ncy = -(-w // cell), -(-h // cell)
+    cap = ncx * ncy if max_points is None else max(0, min(int(max_points), ncx * ncy))
+    strength = torch.empty((h, w), dtype=torch.float32, device=device)
+    cells = torch.empty((ncy, ncx, 2), dtype=torch.int32, device=device)
+    cs = torch.empty((ncy, ncx), dtype=torch.float32, device=device)
+    points = torch.zeros((max(cap, 1), 2), dtype=torch.float32, device=device)
+    count = torch.zeros(1, dtype=torch.int32, device=device)
+    d = TextureDesc(ptr, pitch, w, h, strength.data_ptr(), w, cells.data_ptr(), cs.data_ptr(), None, int(cell), border, float(min_strength))
+    check(L.ofx_texture_features(C.byref(d), 1, int(window), st), "ofx_texture_features")
+    check(L.ofx_compact_features(cells.data_ptr(), ncx * ncy, cap, points.data_ptr(), count.data_ptr(), st), "ofx_compact_features")
+    n = int(count.item())
+    pts = points[:n]
+    # the strengths of the points: the occupied cells' in the same (cell raster) order
+    occupied = cs.reshape(-1)[cells.reshape(-1, 2)[:, 0] >= 0]
+    return pts, occupied[:n]
+
+
+def good_features(img, window: int, cell: int = 16, border: Optional[int] = None, min_strength: float = 0.0, max_points: Optional[int] = None):
+    """Points worth tracking in a uint8 plane [h, w] (host array or CUDA tensor): per cell of cell x cell pixels the local maximum
+    of the texture strength with the largest strength, at least `border` pixels from the image's edge (None: window // 2 + 1, the
+    first border at which no candidate's window touches the edge) and stronger than min_strength ("texture strength and feature
+    selection" in include/ofx.h; ofx_texture_features, ofx_compact_features).  Returns (points float32 [n, 2] of (x, y) in cell raster
+    order, strengths float32 [n]); at most max_points of them (None: all).  A host array gives arrays, a CUDA tensor CUDA tensors."""
+    import torch
+
+    keep, ptr, pitch, w, h = _texture_plane(img)
+    pts, strengths = _good_features_device(ptr, pitch, w, h, int(window), int(cell), border, min_strength, max_points, keep.device)
+    if isinstance(img, torch.Tensor):
+        return pts, strengths
+    return pts.cpu().numpy(), strengths.cpu().numpy()
+
+
+def video_tracks_auto(frames, levels: int, window: int, cell: int = 16, level: int = 0, border: Optional[int] = None, min_strength: float = 0.0,
+                      max_points: Optional[int] = None, **kw):
+    """video_tracks with the points chosen on the device: good_features of frame 0 at `level` -- the level of the pyramid that
+    ofx_pyramid_1ch makes of frame 0, which is the plane the session tracks on -- and then video_tracks, unchanged, with these
+    points.  frames: a grey clip, uint8 CUDA tensor [N, H, W].  kw: video_tracks' other arguments (mode, iters, min_det, batch).
+    Returns (positions float32 [N, n, 2], status int32 [n], strengths float32 [n]); a clip without a single feature is an error."""
+    import torch
+
+    N, H, W = _clip_shape(frames)
+    assert frames.dim() == 3, "video_tracks_auto: a grey clip [N, H, W] (a colour clip's grey frames live inside the session)"
+    assert 0 <= level < levels
+    keep, ptr, pitch, w, h = _texture_plane(frames[0])
+    if level > 0:
+        planes = [None] + [torch.zeros((H >> k, pitch_for(W >> k)), dtype=torch.uint8, device=frames.device) for k in range(1, level + 1)]
+        d_levels = (_vp * (level + 1))(None, *[p.data_ptr() for p in planes[1:]])
+        pitches = (C.c_int * (level + 1))(0, *[pitch_for(W >> k) for k in range(1, level + 1)])
+        check(_lib.load().ofx_pyramid_1ch(ptr, pitch, W, H, d_levels, pitches, level + 1, _stream_ptr()), "ofx_pyramid_1ch")
+        keep, ptr, pitch, w, h = planes[level], planes[level].data_ptr(), pitch_for(W >> level), W >> level, H >> level
+    pts, strengths = _good_features_device(ptr, pitch, w, h, int(window), int(cell), border, min_strength, max_points, frames.device)
+    if pts.shape[0] == 0:
+        raise OfxError(f"video_tracks_auto: frame 0 has no feature at level {level} (window {window}, cell {cell}, min_strength {min_strength})")
+    positions, status = video_tracks(frames, pts, levels, window, level=level, **kw)
+    return positions, status, strengths

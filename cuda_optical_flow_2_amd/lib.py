@@ -54,6 +54,13 @@ class MedianDesc(C.Structure):
                 ("scale", C.c_float), ("d_src", C.c_void_p), ("src_pitch", C.c_int), ("d_dst", C.c_void_p), ("dst_pitch", C.c_int)]
 
 
+class TextureDesc(C.Structure):
+    """ofx_texture_desc (include/ofx.h, "texture strength and feature selection")"""
+    _fields_ = [("d_plane", C.c_void_p), ("pitch", C.c_int), ("w", C.c_int), ("h", C.c_int), ("d_strength", C.c_void_p),
+                ("strength_pitch", C.c_int), ("d_cells", C.c_void_p), ("d_cell_strength", C.c_void_p), ("d_stats", C.c_void_p),
+                ("cell", C.c_int), ("border", C.c_int), ("min_strength", C.c_float)]
+
+
 class LkDesc(C.Structure):
     """ofx_lk_desc (include/ofx.h): one level of an ofx_lk_levels / ofx_corner_flows launch"""
     _fields_ = [("d_prev", C.c_void_p), ("d_next", C.c_void_p), ("geom", Geom), ("d_flow", C.c_void_p), ("flow_row0", C.c_int),
@@ -153,6 +160,8 @@ _SIGS = {
     "ofx_flow_median": [C.POINTER(MedianDesc), _i, _vp],
     "ofx_session_run_flow_dense_median": [_vp, C.c_float, _i, _vp, C.c_size_t, _vp],
     "ofx_session_dense_median_scratch_bytes": [_vp, C.POINTER(C.c_size_t)],
+    "ofx_texture_features": [C.POINTER(TextureDesc), _i, _i, _vp],
+    "ofx_compact_features": [_vp, _i, _i, _vp, _vp, _vp],
     "ofx_interpolate_frames": [_vp, _i, _vp, _i, _i, _i, _vp, _vp, C.POINTER(C.c_float), _i, _vp, _i, C.c_size_t, _vp, _vp],
     "ofx_interpolate_frames_batch": [C.POINTER(_vp), C.POINTER(_i), C.POINTER(_vp), C.POINTER(_i), _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp),
                                      C.POINTER(C.c_float), _i, C.POINTER(_vp), _i, C.c_size_t, C.POINTER(_vp), _vp],

@@ -557,6 +557,55 @@ typedef struct ofx_median_desc {
 } ofx_median_desc;
 int ofx_flow_median(const ofx_median_desc *items, int n, void *stream);
 
+/* ---- texture strength and feature selection -------------------------------------
+ * The trackers (ofx_session_stream_tracks, ofx_advect_points) take caller-owned points.  Where Lucas-Kanade can measure motion at all
+ * is decided by the smaller eigenvalue of the window's structure tensor (Shi, Tomasi, "Good features to track"): on a flat window
+ * and on a single edge the 2x2 system is singular and the flow is NaN or noise.  THE definition (everything else quotes it):
+ *
+ * TEXTURE STRENGTH of a u8 plane p of w x h pixels (rows `pitch` apart), for an odd window 3 .. 23:
+ *   1. Sxx, Syy, Sxy are planes 0, 1, 2 of what ofx_lk_level_sums(p, p, the whole level's geometry, window, OFX_MODE_LK_FLOAT, ..)
+ *      writes: Ix, Iy the 3x3 Sobel correlations of p with the taps outside the image skipped, and the sums of Ix^2, Iy^2, Ix Iy over
+ *      the window clipped at the image.  |Ix|, |Iy| <= 1020, so the sums are exact integers below 2^31 that depend on p only.
+ *   2. In float64, every operation rounded once, nothing fused:
+ *        tr = Sxx + Syy;  d = Sxx - Syy  (both exact);  q = d * d;  p2 = Sxy * Sxy;  p4 = 4 * p2 (exact);  r = q + p4;
+ *        s = sqrt(r), correctly rounded (IEEE);  m = tr - s;  lambda = 0.5 * m (exact).
+ *   3. strength = lambda rounded once to float32 when lambda > 0, else +0: never a NaN, never negative, never -0.
+ *
+ * FEATURE SELECTION on a strength plane R (float32, w x h) for a cell size c in 4 .. 256, a border b >= 0 and a min_strength that
+ * is finite and >= 0:
+ *   1. A pixel is a CANDIDATE when  b <= x < w - b  and  b <= y < h - b;  R(x, y) > min_strength (strict: with 0 a flat or singular
+ *      pixel is never a candidate);  and, among its up to eight neighbours inside the image, R(x, y) > R(n) for every neighbour
+ *      that comes before it in raster order and R(x, y) >= R(n) for every one after it (of a plateau the first pixel remains).
+ *   2. The cell of a pixel is (x / c, y / c) on a grid of ncx x ncy = ceil(w / c) x ceil(h / c).  A cell's FEATURE is its candidate
+ *      with the largest R; among equal ones the one with the smallest y * w + x.
+ *   3. Per item:  cells = int32 [ncy][ncx][2] = (x, y), or (-1, -1);  cell_strength = float32 [ncy][ncx] = R of the feature, or +0;
+ *      stats = four int64: [0] cells, [1] cells with a feature, [2] candidates, [3] pixels inside the border with
+ *      R <= min_strength.  The counts are integers: they depend on no order, tile or batch.
+ *
+ * COMPACTION: the points are ((float)x, (float)y) of the occupied cells in cell raster order; only the first max_points of them
+ * are written, *d_count = min(occupied, max_points), and the entries beyond *d_count are left untouched.
+ *
+ * ofx_texture_features: 1 <= n <= OFX_STREAM_MAX_BATCH items of any sizes; ONE launch writes every item's strength (the plane is read
+ * once, through a buffer resource of exactly (h - 1) * pitch + w bytes: nothing is read outside it), a second one selects for the
+ * items that have d_cells.  Refused with OFX_E_INVALID and a message naming the item, before anything is enqueued: null pointers,
+ * n outside 1 .. OFX_STREAM_MAX_BATCH, an even window or one outside 3 .. 23, w or h <= 0, w * h >= 2^28, a pitch below w or no
+ * multiple of 4 or a plane of 2^31 bytes, a pointer that is not 4-byte (d_stats: 8-byte) aligned, strength_pitch < w, a cell
+ * outside 4 .. 256, a negative border, a min_strength that is negative or not finite, only one of d_cells and d_cell_strength, or
+ * d_stats without cells.  The points for ofx_session_stream_tracks at `level`: these two calls on ofx_session_plane(s, 0, level). */
+typedef struct ofx_texture_desc {
+    const uint8_t *d_plane;
+    int pitch, w, h;         /* pitch a multiple of 4, plane 4-byte aligned: what ofx_geom asks */
+    float *d_strength;
+    int strength_pitch;      /* in floats, >= w; the pad floats of a row are left untouched */
+    int32_t *d_cells;        /* [ncy][ncx][2]; NULL = strength only */
+    float *d_cell_strength;  /* [ncy][ncx]; with d_cells or not at all */
+    int64_t *d_stats;        /* four int64, 8-byte aligned; may be NULL */
+    int cell, border;
+    float min_strength;
+} ofx_texture_desc;
+int ofx_texture_features(const ofx_texture_desc *items, int n, int window, void *stream);
+int ofx_compact_features(const int32_t *d_cells, int n_cells, int max_points, float *d_points, int32_t *d_count, void *stream);
+
 /* ---- layout helpers ------------------------------------------------------ */
 int ofx_extract_ch0(const uint8_t *d_src3, uint8_t *d_dst1, int w, int h, int dst_pitch, void *stream);
 int ofx_replicate_3ch(const uint8_t *d_src1, int src_pitch, uint8_t *d_dst3, int w, int h, void *stream);
