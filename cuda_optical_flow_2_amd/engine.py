@@ -1384,3 +1384,138 @@ def video_tracks_auto(frames, levels: int, window: int, cell: int = 16, level: i
         raise OfxError(f"video_tracks_auto: frame 0 has no feature at level {level} (window {window}, cell {cell}, min_strength {min_strength})")
     positions, status = video_tracks(frames, pts, levels, window, level=level, **kw)
     return positions, status, strengths
+
+
+# ---- sparse Lucas-Kanade tracking ---------------------------------------------------------------------------------------------------
+
+TRACK_START, TRACK_SINGULAR, TRACK_OUT, TRACK_RESIDUAL, TRACK_FB = 1, 2, 3, 4, 5
+
+
+class _KltPyramid:
+    """The grey pyramid of one frame for ofx_track_points: level 0 the frame itself (read in place when its rows are pitch_for(w)
+    apart and 4-byte aligned, otherwise a padded copy), the levels above made by ofx_pyramid_1ch"""
+
+    def __init__(self, img, levels: int):
+        import torch
+
+        keep, ptr, pitch, w, h = _texture_plane(img)
+        if pitch != pitch_for(w):                       # one pitch per level for every frame of a clip
+            t = torch.zeros((h, pitch_for(w)), dtype=torch.uint8, device=keep.device)
+            t[:, :w] = keep[:, :w]
+            keep, ptr, pitch = t, t.data_ptr(), pitch_for(w)
+        self.w, self.h, self.levels = w, h, int(levels)
+        assert 1 <= self.levels <= 8 and (w >> (self.levels - 1)) >= 1 and (h >> (self.levels - 1)) >= 1, "levels: 1 .. 8, the coarsest level not empty"
+        self.planes = [keep] + [torch.zeros((h >> k, pitch_for(w >> k)), dtype=torch.uint8, device=keep.device) for k in range(1, self.levels)]
+        self.ptrs = [ptr] + [p.data_ptr() for p in self.planes[1:]]
+        self.pitches = [pitch] + [pitch_for(w >> k) for k in range(1, self.levels)]
+        if self.levels > 1:
+            d_levels = (_vp * self.levels)(None, *self.ptrs[1:])
+            pitches = (C.c_int * self.levels)(*self.pitches)
+            check(_lib.load().ofx_pyramid_1ch(ptr, pitch, w, h, d_levels, pitches, self.levels, _stream_ptr()), "ofx_pyramid_1ch")
+
+    def host(self):
+        """the levels as arrays [h >> k, w >> k] (tests: what the referee is fed)"""
+        return [p[:, :self.w >> k].cpu().numpy() for k, p in enumerate(self.planes)]
+
+
+def klt_pyramid(img, levels: int) -> _KltPyramid:
+    """The pyramid engine.track_points and engine.video_klt track on, of a uint8 plane [h, w] (host array or CUDA tensor)"""
+    return _KltPyramid(img, levels)
+
+
+def _track_params(window, max_iters, eps, min_lambda, max_sad):
+    import math
+    from .lib import TrackParams
+
+    return TrackParams(int(window), int(max_iters), int(math.floor(float(eps) * 32.0)), int(max_sad), float(min_lambda))
+
+
+def _track_launch(pyramids, prm, pair0, points, status, history=None, sad=None, stats=None):
+    """ofx_track_points on the pyramids of consecutive frames; points [n, 2] float32 and status [n] int32 are CUDA tensors updated in
+    place, history [pairs, n, 2] float32, sad [pairs, n] int32 and stats [pairs, 7] int64 contiguous CUDA tensors or None"""
+    from .lib import TrackClip
+
+    p0 = pyramids[0]
+    assert all(p.w == p0.w and p.h == p0.h and p.levels == p0.levels and p.pitches == p0.pitches for p in pyramids)
+    n_frames, levels = len(pyramids), p0.levels
+    table = (_vp * (n_frames * levels))(*[p.ptrs[k] for p in pyramids for k in range(levels)])
+    pitches = (C.c_int * levels)(*p0.pitches)
+    clip = TrackClip(p0.w, p0.h, levels, n_frames, table, pitches)
+    assert points.is_contiguous() and status.is_contiguous() and all(t is None or t.is_contiguous() for t in (history, sad, stats))
+    ptr = lambda t: None if t is None else t.data_ptr()
+    check(_lib.load().ofx_track_points(C.byref(clip), C.byref(prm), int(pair0), points.data_ptr(), status.data_ptr(), int(points.shape[0]),
+                                       ptr(history), ptr(sad), ptr(stats), _stream_ptr()), "ofx_track_points")
+
+
+def track_points(prev, next, points, levels: int, window: int, max_iters: int = 10, eps: float = 1 / 32, min_lambda: float = 0.0, max_sad: int = 0,
+                 fb_max: Optional[float] = None):
+    """Track points from `prev` to `next` in pixels ("sparse Lucas-Kanade tracking" in include/ofx.h; ofx_track_points): per point
+    an iterative, coarse-to-fine Lucas-Kanade on a lattice of 1/32 px over `levels` levels of the pyramids ofx_pyramid_1ch makes of
+    the two frames.  prev, next: uint8 [h, w], host arrays or CUDA tensors; points: float32 [n, 2] of (x, y), n >= 1.  eps: an
+    iteration whose step is at most this many pixels in both coordinates is the last (in 1/32 px, rounded down); min_lambda: the
+    smaller eigenvalue of the window's gradient matrix a level needs; max_sad: the largest residual a tracked point may have (0:
+    any).  Returns (positions float32 [n, 2], status int32 [n], sad int32 [n]): status 0 = tracked, otherwise (1 << 8) | reason
+    with reason 1 START, 2 SINGULAR, 3 OUT, 4 RESIDUAL, and the point keeps its position; sad is -1 for a lost point.  With fb_max
+    the tracked points are tracked back next -> prev as well, and one that gets lost on the way or misses its start (on the
+    lattice) by more than fb_max pixels in either coordinate is lost with reason 5 (FB).  Host frames give arrays, CUDA tensors
+    CUDA tensors."""
+    import math
+    import torch
+
+    pa, pb = _KltPyramid(prev, levels), _KltPyramid(next, levels)
+    dev = pa.planes[0].device
+    start = torch.as_tensor(np.asarray(points, np.float32) if not isinstance(points, torch.Tensor) else points, dtype=torch.float32, device=dev).reshape(-1, 2).contiguous()
+    n = int(start.shape[0])
+    pos, status = start.clone(), torch.zeros(n, dtype=torch.int32, device=dev)
+    sad = torch.empty((1, n), dtype=torch.int32, device=dev)
+    prm = _track_params(window, max_iters, eps, min_lambda, max_sad)
+    _track_launch([pa, pb], prm, 1, pos, status, None, sad)
+    sad = sad[0]
+    if fb_max is not None:
+        back, bstat = pos.clone(), status.clone()
+        _track_launch([pb, pa], prm, 1, back, bstat)
+        lim = int(math.floor(32.0 * float(fb_max)))
+        q0, q1 = torch.round(start * 32.0).to(torch.int64), torch.round(back * 32.0).to(torch.int64)   # (exact: the lattice)
+        miss = (status == 0) & ((bstat != 0) | ((q1 - q0).abs() > lim).any(dim=1))
+        pos[miss] = start[miss]
+        status[miss] = (1 << 8) | TRACK_FB
+        sad[miss] = -1
+    if isinstance(prev, torch.Tensor):
+        return pos, status, sad
+    torch.cuda.synchronize()
+    return pos.cpu().numpy(), status.cpu().numpy(), sad.cpu().numpy()
+
+
+def video_klt(frames, points=None, levels: int = 3, window: int = 9, cell: int = 16, batch: int = 16, max_iters: int = 10, eps: float = 1 / 32,
+              min_lambda: float = 0.0, max_sad: int = 0, return_stats: bool = False):
+    """Track points through a grey clip in pixels: ofx_track_points over chains of up to `batch` pairs per launch (1 .. 16; the
+    result does not depend on it).  frames: uint8 CUDA tensor [N, H, W]; the pyramids are built frame by frame and only those of
+    the chain in flight are kept.  points: float32 [n, 2], or None for good_features(frames[0], window, cell).  Pair p (1 .. N - 1)
+    goes from frame p - 1 to frame p.  Returns (positions float32 [N, n, 2] -- [0] the seeds, [p] after pair p, a lost point
+    staying where it was --, status int32 [n] -- 0 or (pair << 8) | reason --, sad int32 [N - 1, n], -1 where a point was not
+    tracked in that pair) and, with return_stats, the int64 [N - 1, 7] counts of include/ofx.h."""
+    import torch
+
+    N, H, W = _clip_shape(frames)
+    assert frames.dim() == 3, "video_klt: a grey clip [N, H, W]"
+    assert 1 <= batch <= 16, "batch: 1 .. 16"
+    dev = frames.device
+    last = _KltPyramid(frames[0], levels)
+    if points is None:
+        points, _ = _good_features_device(last.ptrs[0], last.pitches[0], W, H, int(window), int(cell), None, 0.0, None, dev)
+        if points.shape[0] == 0:
+            raise OfxError(f"video_klt: frame 0 has no feature (window {window}, cell {cell})")
+    pts = torch.as_tensor(np.asarray(points, np.float32) if not isinstance(points, torch.Tensor) else points, dtype=torch.float32, device=dev).reshape(-1, 2)
+    n = int(pts.shape[0])
+    positions = torch.empty((N, n, 2), dtype=torch.float32, device=dev)
+    positions[0] = pts
+    cur, status = pts.clone().contiguous(), torch.zeros(n, dtype=torch.int32, device=dev)
+    sad = torch.empty((N - 1, n), dtype=torch.int32, device=dev)
+    stats = torch.empty((N - 1, 7), dtype=torch.int64, device=dev) if return_stats else None
+    prm = _track_params(window, max_iters, eps, min_lambda, max_sad)
+    for f0 in range(0, N - 1, batch):
+        f1 = min(f0 + batch, N - 1)                       # the pairs f0 + 1 .. f1
+        chain = [last] + [_KltPyramid(frames[f], levels) for f in range(f0 + 1, f1 + 1)]
+        _track_launch(chain, prm, f0 + 1, cur, status, positions[f0 + 1:f1 + 1], sad[f0:f1], None if stats is None else stats[f0:f1])
+        last = chain[-1]
+    return (positions, status, sad, stats) if return_stats else (positions, status, sad)

@@ -61,6 +61,17 @@ class TextureDesc(C.Structure):
                 ("cell", C.c_int), ("border", C.c_int), ("min_strength", C.c_float)]
 
 
+class TrackClip(C.Structure):
+    """ofx_track_clip (include/ofx.h, "sparse Lucas-Kanade tracking"): planes and pitches are host tables"""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("levels", C.c_int), ("n_frames", C.c_int), ("planes", C.POINTER(C.c_void_p)),
+                ("pitches", C.POINTER(C.c_int))]
+
+
+class TrackParams(C.Structure):
+    """ofx_track_params (include/ofx.h, "sparse Lucas-Kanade tracking")"""
+    _fields_ = [("window", C.c_int), ("max_iters", C.c_int), ("eps_q", C.c_int), ("max_sad", C.c_int), ("min_lambda", C.c_float)]
+
+
 class LkDesc(C.Structure):
     """ofx_lk_desc (include/ofx.h): one level of an ofx_lk_levels / ofx_corner_flows launch"""
     _fields_ = [("d_prev", C.c_void_p), ("d_next", C.c_void_p), ("geom", Geom), ("d_flow", C.c_void_p), ("flow_row0", C.c_int),
@@ -162,6 +173,7 @@ _SIGS = {
     "ofx_session_dense_median_scratch_bytes": [_vp, C.POINTER(C.c_size_t)],
     "ofx_texture_features": [C.POINTER(TextureDesc), _i, _i, _vp],
     "ofx_compact_features": [_vp, _i, _i, _vp, _vp, _vp],
+    "ofx_track_points": [C.POINTER(TrackClip), C.POINTER(TrackParams), _i, _vp, _vp, _i, _vp, _vp, _vp, _vp],
     "ofx_interpolate_frames": [_vp, _i, _vp, _i, _i, _i, _vp, _vp, C.POINTER(C.c_float), _i, _vp, _i, C.c_size_t, _vp, _vp],
     "ofx_interpolate_frames_batch": [C.POINTER(_vp), C.POINTER(_i), C.POINTER(_vp), C.POINTER(_i), _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp),
                                      C.POINTER(C.c_float), _i, C.POINTER(_vp), _i, C.c_size_t, C.POINTER(_vp), _vp],

@@ -606,6 +606,75 @@ typedef struct ofx_texture_desc {
 int ofx_texture_features(const ofx_texture_desc *items, int n, int window, void *stream);
 int ofx_compact_features(const int32_t *d_cells, int n_cells, int max_points, float *d_points, int32_t *d_count, void *stream);
 
+/* ---- sparse Lucas-Kanade tracking --------------------------------------------------
+ * ofx_advect_points adds the composed field of main.cu:138-147 at a point's pixel; that field is not a displacement.  This block
+ * tracks chosen points IN PIXELS: per point an iterative, coarse-to-fine Lucas-Kanade (Lucas, Kanade 1981; Bouguet's pyramidal
+ * form) on a lattice of 1/32 px.  Everything up to the 2x2 solve is exact integer arithmetic, so no order of summation has to be
+ * fixed, and the solve is float64 with one rounding per operation.  THE definition (tests/klt_ref.py restates it in NumPy):
+ *
+ * INPUTS: two grey pyramids A (frame p - 1) and B (frame p) of `levels` u8 planes, 1 <= levels <= 8; level k is (w >> k) x (h >> k)
+ * and the coarsest level has w, h >= 1 (how the planes were made is the caller's business: ofx_pyramid_1ch makes them); w, h <=
+ * 2^19, so that every lattice position is exact in float32; an odd window 3 .. 23, R = window / 2; max_iters in 1 .. 32; eps_q >= 0;
+ * min_lambda >= 0 and finite; max_sad >= 0 (0 = off).
+ *
+ * LATTICE: a position q = 32 ix + a with a in 0 .. 31; ix = q >> 5 and a = q & 31 on the two's-complement value (floor division).
+ * SAMPLE S(P, qx, qy), with (ix, a) of qx and (iy, b) of qy:
+ *   s = (32-a)(32-b) P(ix, iy) + a(32-b) P(ix+1, iy) + (32-a)b P(ix, iy+1) + ab P(ix+1, iy+1), every tap's column and row clamped
+ *   to the plane (replicate);  S = (s + 16) >> 5, in 0 .. 8160 (1/32 grey level).
+ *
+ * A point (x, y) float32 with status 0, per pair:
+ *   START  x, y must be finite and inside [0, w-1] x [0, h-1] of level 0, else the point is lost with reason START.
+ *          d = (0, 0), int32, in 1/32 px of the current level.
+ *   LEVEL  k = levels-1 .. 0:  below the coarsest level d is doubled first.
+ *          c = (lrintf(ldexpf(x, 5 - k)), lrintf(ldexpf(y, 5 - k))), ties to even.
+ *          For i, j in -R .. R:  I(i,j) = S(A_k, cx + 32 i, cy + 32 j);  gx(i,j) = S(A_k, cx + 32 (i+1), cy + 32 j) - S(A_k, cx +
+ *          32 (i-1), cy + 32 j);  gy likewise in j.  Gxx = sum gx^2, Gyy = sum gy^2, Gxy = sum gx gy: exact integers below 2^36.
+ *          In float64:  D = Gxx * Gyy - Gxy * Gxy (two products, one difference);  lambda = step 2 of TEXTURE STRENGTH on (Gxx,
+ *          Gyy, Gxy).  The level is SINGULAR when !(D > 0) or !(lambda > min_lambda): at k > 0 it is skipped and d is kept, at
+ *          k = 0 the point is lost with reason SINGULAR.  Otherwise up to max_iters times:
+ *            e(i,j) = S(B_k, cx + dx + 32 i, cy + dy + 32 j) - I(i,j);  bx = sum gx e, by = sum gy e (exact integers);
+ *            sx = -64 * ((Gyy * bx - Gxy * by) / D),  sy = -64 * ((Gxx * by - Gxy * bx) / D)  in float64: two products, one
+ *            difference, one IEEE division, one (exact) scaling -- g is twice the derivative and the step is wanted in 1/32 px;
+ *            t = rint(s) clamped to [-2048, 2048], ties to even;  d += t;  stop after an update with |tx| <= eps_q and |ty| <= eps_q.
+ *   END    q = c + d at level 0.  Outside [0, 32 (w-1)] x [0, 32 (h-1)]: lost with reason OUT.  sad = sum |S(B_0, q + 32 (i,j)) -
+ *          I(i,j)| (at most 529 * 8160);  max_sad > 0 and sad > max_sad: lost with reason RESIDUAL.  Otherwise the point moves to
+ *          ((float)qx / 32, (float)qy / 32), which is exact: the next pair starts from the same lattice point.
+ * A lost point keeps its position and its status becomes (pair << 8) | reason, reasons OFX_TRACK_START .. OFX_TRACK_RESIDUAL; a
+ * point whose status is not 0 on entry is not touched.
+ *
+ * CHAIN: a launch carries n_frames = 2 .. 17 frames, n_frames - 1 <= OFX_STREAM_MAX_BATCH pairs, numbered pair0, pair0 + 1, ..; a
+ * point walks them in order, the template of a pair taken in its first frame at the point's current position: the result does not
+ * depend on how a clip is cut into launches.
+ *
+ * OUTPUTS per pair b (each may be NULL):  d_history [pairs][n][2] float32, the positions after the pair, frozen ones included;
+ * d_sad [pairs][n] int32, -1 for a point not tracked in that pair;  d_stats [pairs][7] int64: [0] points alive after the pair,
+ * [1 .. 4] points lost in it by reasons 1 .. 4, [5] iterations summed over points and levels, [6] the sum of sad over the points
+ * tracked.  Integer counts: any order of atomics gives them; the call zeroes them on the stream first.
+ *
+ * ofx_track_points: ONE launch.  clip->planes is a HOST table of n_frames x levels device planes (frame-major), clip->pitches one
+ * pitch per level; any pitch >= w >> k and any alignment, the taps are bytes, and every tap is clamped before it becomes an
+ * address.  Refused with OFX_E_INVALID and a message naming the argument, before anything is enqueued: null pointers (a plane
+ * among them), levels outside 1 .. 8 or a coarsest level of width or height 0, w or h above 2^19, n_frames outside 2 .. 17, an
+ * even window or one outside 3 .. 23, max_iters outside 1 .. 32, eps_q < 0, min_lambda negative or not finite, max_sad < 0,
+ * pair0 < 1 or pair0 + pairs >= 2^23, n_points < 1, a pitch below the level's width or a plane of 2^31 bytes or more, d_points or
+ * d_history not 8-byte aligned, d_status or d_sad not 4-byte aligned, d_stats not 8-byte aligned. */
+#define OFX_TRACK_START 1
+#define OFX_TRACK_SINGULAR 2
+#define OFX_TRACK_OUT 3
+#define OFX_TRACK_RESIDUAL 4
+#define OFX_TRACK_MAX_LEVELS 8
+typedef struct ofx_track_clip {
+    int w, h, levels, n_frames;
+    const uint8_t *const *planes; /* host table: planes[f * levels + k] = level k of frame f, on the device */
+    const int *pitches;           /* host table: [levels], in bytes */
+} ofx_track_clip;
+typedef struct ofx_track_params {
+    int window, max_iters, eps_q, max_sad;
+    float min_lambda;
+} ofx_track_params;
+int ofx_track_points(const ofx_track_clip *clip, const ofx_track_params *prm, int pair0, float *d_points, int32_t *d_status, int n_points,
+                     float *d_history, int32_t *d_sad, int64_t *d_stats, void *stream);
+
 /* ---- layout helpers ------------------------------------------------------ */
 int ofx_extract_ch0(const uint8_t *d_src3, uint8_t *d_dst1, int w, int h, int dst_pitch, void *stream);
 int ofx_replicate_3ch(const uint8_t *d_src1, int src_pitch, uint8_t *d_dst3, int w, int h, void *stream);
