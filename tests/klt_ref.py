@@ -1,6 +1,8 @@
 """The definition "sparse Lucas-Kanade tracking" of include/ofx.h in NumPy: int64 up to the 2x2 solve, float64 after it (NumPy
 rounds every operation once and fuses nothing), vectorised over the points.  No GPU, no library: tests/test_klt_ref.py checks this
-file against the definition in words, tests/test_gpu_klt.py checks the kernel against this file by the bits."""
+file against the definition in words, tests/test_gpu_klt.py checks the kernel against this file by the bits.  The inputs that the
+two share are at the end."""
+import functools
 from collections import namedtuple
 
 import numpy as np
@@ -173,3 +175,218 @@ def cosine_texture(w, h, sx=0.0, sy=0.0, seed=17, terms=40, fmax=0.6):
 def interior_points(w, h, nx, ny, margin):
     xs, ys = np.linspace(margin, w - 1 - margin, nx), np.linspace(margin, h - 1 - margin, ny)
     return np.stack(np.meshgrid(np.rint(xs), np.rint(ys)), axis=-1).reshape(-1, 2).astype(np.float32)
+
+
+# ---- the inputs that tests/test_klt_ref.py (the conditions on them, by the referee alone) and tests/test_gpu_klt.py (the kernel
+# ---- against the referee) share, made once ------------------------------------------------------------------------------------------
+NAN, INF = np.float32("nan"), np.float32("inf")
+ALL_WINDOWS = tuple(range(3, 24, 2))                              # one instance of klt_kernel<R> each
+HARD_SHAPE = (67, 45, 4)                                          # (w, h, levels): where every window runs
+
+
+def _shift(img, sx, sy):
+    """the content of img at (x, y) at (x + sx, y + sy), the border replicated"""
+    h, w = img.shape
+    yy, xx = np.clip(np.arange(h) - sy, 0, h - 1), np.clip(np.arange(w) - sx, 0, w - 1)
+    return np.ascontiguousarray(img[yy][:, xx])
+
+
+def _frozen(planes):
+    for p in planes:
+        p.setflags(write=False)
+    return tuple(planes)
+
+
+@functools.lru_cache(maxsize=None)
+def hard_pyramids(w, h, levels):
+    """the hard frame of tests/iter_hard.py (flat blocks, stripes, noise; below 33 x 17 plain noise) against a copy shifted by
+    (2, -1), noise of +-2 grey levels added to it"""
+    import iter_hard
+
+    rng = np.random.RandomState(w * 131 + h)
+    a = iter_hard.hard_frames(w, h, 1, block=(max(h // 4, 1), max(w // 4, 1)), band=max(w // 8, 1))[0] if w >= 33 else rng.randint(0, 256, (h, w)).astype(np.uint8)
+    b = np.clip(_shift(a, 2, -1).astype(np.int32) + rng.randint(-2, 3, (h, w)), 0, 255).astype(np.uint8)
+    return _frozen(pyramid(a, levels)), _frozen(pyramid(b, levels))
+
+
+@functools.lru_cache(maxsize=None)
+def smooth_pyramid(w, h, levels, sx, sy):
+    return _frozen(pyramid(cosine_texture(w, h, sx, sy), levels))
+
+
+def specials(w, h):
+    """positions that a tracker gets wrong first: the four corners, edge points, points whose window hangs over a border, ties of
+    the lattice, NaN, infinities, negative positions and positions past the last pixel"""
+    X, Y = np.float32(w - 1), np.float32(h - 1)
+    return [(0, 0), (X, 0), (0, Y), (X, Y), (X / 2, 0), (0, Y / 2), (X, Y / 2), (X / 2, Y), (1.546875, 1.515625), (X - 1.546875, Y - 0.515625),
+            (NAN, 1), (1, NAN), (INF, 0), (0, -INF), (-0.03125, 0), (0, -1e-30), (X + 0.03125, 0), (0, Y + 1), (-1e30, 1e30), (X - 0.5, Y - 0.25),
+            (0.015625, 0.046875), (2.5, 3.5), (X - 2, Y / 3), (X - 1, Y / 2), (X / 3, 1), (0.5, 0.5), (1e-40, 0), (-0.0, -0.0)]
+
+
+def points_for(w, h, n, seed=0):
+    """(points float32 [n, 2], status int32 [n]): specials(w, h), three points frozen on entry, and random ones on and off the
+    lattice.  n == 1: a random point."""
+    rng = np.random.RandomState(seed + 7 * n)
+    special = specials(w, h)
+    pts = np.zeros((n, 2), np.float32)
+    q = np.stack([rng.randint(0, 32 * (w - 1) + 1, n), rng.randint(0, 32 * (h - 1) + 1, n)], axis=1).astype(np.float32) / np.float32(32)
+    r = (rng.rand(n, 2) * [w - 1, h - 1]).astype(np.float32)
+    pts[:] = np.where((np.arange(n) & 1)[:, None] == 0, q, r)
+    status = np.zeros(n, np.int32)
+    if n > 1:
+        k = min(len(special), n - 1)
+        with np.errstate(invalid="ignore"):
+            pts[1:1 + k] = np.float32(special[:k])
+        for i, st in ((n - 1, (3 << 8) | OUT), (n // 2, 1), (n // 3, -5)):
+            status[i] = st
+    return pts, status
+
+
+def lam_for(win):
+    """a min_lambda between the flat / striped / weak windows and the textured ones of the test frames"""
+    return float(np.float32(2.0e5 * win * win))
+
+
+def combos(windows):
+    """(window, max_iters, eps_q, min_lambda, max_sad, n_points): every window with every n_points; the other parameters take
+    both of their values at every window"""
+    out = []
+    for win in windows:
+        for j, n in enumerate((1, 63, 65, 257)):
+            out.append(Params(win, (1, 32, 32, 4)[j], (0, 1, 0, 1)[j], (0.0, lam_for(win), 0.0, lam_for(win))[j], (0, 0, 60 * win * win, 200 * win * win)[j]) + (n,))
+    return out
+
+
+_WANT = {}
+
+
+def want_chain(key, pyramids, pts, status, pair0, prm):
+    """the referee's chain, computed once per key and shared"""
+    if key not in _WANT:
+        _WANT[key] = track_chain(pyramids, pts, status, pair0, prm)
+        for a in _WANT[key]:
+            a.setflags(write=False)
+    return _WANT[key]
+
+
+def reasons_of(want, status):
+    """[tracked, START, SINGULAR, OUT, RESIDUAL, FB] counts of a chain's final status, of the points alive on entry"""
+    return np.bincount(want[1][status == 0] & 255, minlength=6)[:6]
+
+
+def hard_case(c):
+    """one of combos()'s cases on the hard frame at HARD_SHAPE: (pyramids, points, status, pair0, Params, the referee's chain)"""
+    w, h, levels = HARD_SHAPE
+    pa, pb = hard_pyramids(w, h, levels)
+    prm, n = Params(*c[:5]), c[5]
+    pts, status = points_for(w, h, n, seed=w)
+    return [pa, pb], pts, status, 3, prm, want_chain(("hard", w, h, levels, tuple(c)), [pa, pb], pts, status, 3, prm)
+
+
+# more points than the launch has waves: csrc/klt.hip launches at most 8192 blocks of four waves
+TURN_FIRST = 4 * 8192                                             # the first point that a wave takes on its second visit
+TURN_N = TURN_FIRST + 261
+TURN_WINDOWS = (3, 5)
+TURN_PAIR0 = 300
+
+
+@functools.lru_cache(maxsize=None)
+def turn_case(window):
+    """(pyramids, points, status, pair0, Params, the referee's chain): TURN_N points on three frames of the texture drifting by
+    (0.7, -0.4) px per frame.  points_for's points, and its specials and frozen points once more from TURN_FIRST + 3 on; five more
+    of the last 261 points come with a status."""
+    w, h, levels = HARD_SHAPE
+    pyr = [smooth_pyramid(w, h, levels, 0.7 * i, -0.4 * i) for i in range(3)]
+    pts, status = points_for(w, h, TURN_N, seed=11)
+    sp = specials(w, h)
+    with np.errstate(invalid="ignore"):
+        pts[TURN_FIRST + 3:TURN_FIRST + 3 + len(sp)] = np.float32(sp)
+    for i, st in ((TURN_FIRST, (2 << 8) | SINGULAR), (TURN_FIRST + 64, 1), (TURN_FIRST + 129, -5), (TURN_FIRST + 255, (299 << 8) | RESIDUAL), (TURN_N - 2, 7)):
+        status[i] = st
+    pts.setflags(write=False), status.setflags(write=False)
+    prm = Params(window, 4, 1, 0.0, 60 * window * window)
+    return pyr, pts, status, TURN_PAIR0, prm, want_chain(("turn", window), pyr, pts, status, TURN_PAIR0, prm)
+
+
+# 6, 7 and 8 levels: OFX_TRACK_MAX_LEVELS is 8; the coarsest levels are 6 x 2, 4 x 2, 2 x 1 and 1 x 1 pixels
+DEEP_SHAPES = [(200, 70, 6), (262, 137, 7), (259, 131, 8), (131, 129, 8)]
+DEEP_SHIFTS = ((0.4, -0.3), (-2.75, 1.5), (9.0, 5.0))
+DEEP_WINDOWS = (7, 15)
+
+
+def deep_cases(w, h, levels):
+    """[(name, pyramids, points, status, pair0, Params, padded pitches, the referee's chain)]: every shift x window x min_lambda off
+    and on"""
+    out = []
+    for i, (sx, sy) in enumerate(DEEP_SHIFTS):
+        pyr = [smooth_pyramid(w, h, levels, 0.0, 0.0), smooth_pyramid(w, h, levels, sx, sy)]
+        for win in DEEP_WINDOWS:
+            pts, status = points_for(w, h, 129, seed=int(sx * 4))
+            for lam in (0.0, lam_for(win)):
+                prm = Params(win, 10, 1, lam, 0)
+                key = ("deep", w, h, levels, sx, sy, win, lam)
+                out.append((f"{w}x{h}x{levels} shift ({sx}, {sy}) window {win} min_lambda {lam}", pyr, pts, status, 2, prm, (i + (lam > 0)) & 1,
+                            want_chain(key, pyr, pts, status, 2, prm)))
+    return out
+
+
+# the widest plane the call accepts
+WIDE_W, WIDE_H = 1 << 19, 3
+WIDE_WINDOWS = (5, 9)
+
+
+@functools.lru_cache(maxsize=None)
+def wide_pyramids():
+    """one level of 2^19 x 3: noise smoothed along the rows by a 5-tap box, its contrast stretched to 0 .. 255, against itself rolled by
+    one column: the content of A at (x, y) is at (x + 1, y) in B"""
+    rng = np.random.RandomState(19)
+    n = rng.randint(0, 256, (WIDE_H, WIDE_W + 4)).astype(np.int64)
+    c = np.concatenate([np.zeros((WIDE_H, 1), np.int64), n.cumsum(1)], axis=1)
+    s = (c[:, 5:] - c[:, :-5]).astype(np.float64) / 5.0                         # [3, 2^19]
+    a = np.clip(np.rint((s - s.min()) * (255.0 / (s.max() - s.min()))), 0, 255).astype(np.uint8)
+    assert a.shape == (WIDE_H, WIDE_W)
+    return _frozen([a]), _frozen([np.roll(a, 1, axis=1)])
+
+
+@functools.lru_cache(maxsize=None)
+def wide_case(window):
+    """257 points within 300 columns of the right edge, half of them on the lattice; among them the last pixel, the last lattice
+    point before the last column and a point half a pixel from it"""
+    w, h = WIDE_W, WIDE_H
+    rng = np.random.RandomState(5)
+    q = np.stack([32 * (w - 1) - rng.randint(0, 32 * 300, 257), rng.randint(0, 32 * (h - 1) + 1, 257)], axis=1).astype(np.float32) / np.float32(32)
+    r = np.stack([w - 1 - 300 * rng.rand(257), (h - 1) * rng.rand(257)], axis=1).astype(np.float32)
+    pts = np.where((np.arange(257) & 1)[:, None] == 0, q, r).astype(np.float32)
+    pts[:3] = np.float32([(w - 1, h - 1), (w - 1 - 1 / 32, 0), (w - 1.5, 1)])
+    status = np.zeros(257, np.int32)
+    pts.setflags(write=False), status.setflags(write=False)
+    pa, pb = wide_pyramids()
+    prm = Params(window, 10, 1, 0.0, 0)
+    return [pa, pb], pts, status, 1, prm, want_chain(("wide", window), [pa, pb], pts, status, 1, prm)
+
+
+# saturated contrast: a checkerboard of 0 / 255 in 2-px squares, |gx| = 8160 at every window pixel of a pixel-centred window
+SAT_WINDOWS = (3, 13, 23)
+SAT_LEVELS = (1, 3)
+SAT_KINDS = ("shifted", "inverse")
+
+
+@functools.lru_cache(maxsize=None)
+def sat_pyramids(levels, kind):
+    import texture_ref as T
+
+    w, h = HARD_SHAPE[:2]
+    a = T.checkerboard(w, h)
+    if kind == "inverse":
+        b = (255 - a).astype(np.uint8)
+    else:
+        b = np.clip(_shift(a, 1, 0).astype(np.int32) + np.random.RandomState(23).randint(-2, 3, (h, w)), 0, 255).astype(np.uint8)
+    return _frozen(pyramid(a, levels)), _frozen(pyramid(b, levels))
+
+
+def sat_case(levels, window, kind):
+    w, h = HARD_SHAPE[:2]
+    pa, pb = sat_pyramids(levels, kind)
+    pts, status = points_for(w, h, 257, seed=window)
+    prm = Params(window, 10, 1, 0.0, 0)
+    return [pa, pb], pts, status, 1, prm, want_chain(("sat", levels, window, kind), [pa, pb], pts, status, 1, prm)

@@ -3,12 +3,12 @@ Every comparison is exact, floats by their bits, and no point is excluded.  Outp
 addresses in larger buffers whose surroundings (pad columns included) differ between runs, so that a tap outside a plane, or a
 store outside an output, shows."""
 import ctypes as C
-import functools
+import os
+import re
 
 import numpy as np
 import pytest
 
-import iter_hard
 import klt_ref as K
 from test_gpu_interp import AROUND_P, FILL, Guarded, Plane, same
 
@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 
 OFX_E_INVALID = 1
 SHAPES = [(1, 1, 1), (2, 3, 1), (5, 4, 1), (33, 17, 3), (67, 45, 4), (262, 74, 5)]          # (w, h, levels)
-NAN, INF = np.float32("nan"), np.float32("inf")
+NAN, INF = K.NAN, K.INF
 
 
 @pytest.fixture(scope="module")
@@ -29,56 +29,8 @@ def eng():
     return engine
 
 
-# ---- inputs, made once and shared -------------------------------------------------------------------------------------------------
-def _shift(img, sx, sy):
-    """the content of img at (x, y) at (x + sx, y + sy), the border replicated"""
-    h, w = img.shape
-    yy, xx = np.clip(np.arange(h) - sy, 0, h - 1), np.clip(np.arange(w) - sx, 0, w - 1)
-    return np.ascontiguousarray(img[yy][:, xx])
-
-
-@functools.lru_cache(maxsize=None)
-def hard_pyramids(w, h, levels):
-    """the hard frame of tests/iter_hard.py (flat blocks, stripes, noise; below 33 x 17 plain noise) against a copy shifted by
-    (2, -1), noise of +-2 grey levels added to it"""
-    rng = np.random.RandomState(w * 131 + h)
-    a = iter_hard.hard_frames(w, h, 1, block=(max(h // 4, 1), max(w // 4, 1)), band=max(w // 8, 1))[0] if w >= 33 else rng.randint(0, 256, (h, w)).astype(np.uint8)
-    b = np.clip(_shift(a, 2, -1).astype(np.int32) + rng.randint(-2, 3, (h, w)), 0, 255).astype(np.uint8)
-    return _frozen(K.pyramid(a, levels)), _frozen(K.pyramid(b, levels))
-
-
-@functools.lru_cache(maxsize=None)
-def smooth_pyramid(w, h, levels, sx, sy):
-    return _frozen(K.pyramid(K.cosine_texture(w, h, sx, sy), levels))
-
-
-def _frozen(planes):
-    for p in planes:
-        p.setflags(write=False)
-    return tuple(planes)
-
-
-def points_for(w, h, n, seed=0):
-    """(points float32 [n, 2], status int32 [n]): the four corners, edge points, points whose window hangs over a border, ties of
-    the lattice, NaN, infinities, negative positions and positions past the last pixel, three points frozen on entry, and random
-    ones on and off the lattice.  n == 1: a random point."""
-    rng = np.random.RandomState(seed + 7 * n)
-    X, Y = np.float32(w - 1), np.float32(h - 1)
-    special = [(0, 0), (X, 0), (0, Y), (X, Y), (X / 2, 0), (0, Y / 2), (X, Y / 2), (X / 2, Y), (1.546875, 1.515625), (X - 1.546875, Y - 0.515625),
-               (NAN, 1), (1, NAN), (INF, 0), (0, -INF), (-0.03125, 0), (0, -1e-30), (X + 0.03125, 0), (0, Y + 1), (-1e30, 1e30), (X - 0.5, Y - 0.25),
-               (0.015625, 0.046875), (2.5, 3.5), (X - 2, Y / 3), (X - 1, Y / 2), (X / 3, 1), (0.5, 0.5), (1e-40, 0), (-0.0, -0.0)]
-    pts = np.zeros((n, 2), np.float32)
-    q = np.stack([rng.randint(0, 32 * (w - 1) + 1, n), rng.randint(0, 32 * (h - 1) + 1, n)], axis=1).astype(np.float32) / np.float32(32)
-    r = (rng.rand(n, 2) * [w - 1, h - 1]).astype(np.float32)
-    pts[:] = np.where((np.arange(n) & 1)[:, None] == 0, q, r)
-    status = np.zeros(n, np.int32)
-    if n > 1:
-        k = min(len(special), n - 1)
-        with np.errstate(invalid="ignore"):
-            pts[1:1 + k] = np.float32(special[:k])
-        for i, st in ((n - 1, (3 << 8) | K.OUT), (n // 2, 1), (n // 3, -5)):
-            status[i] = st
-    return pts, status
+# ---- inputs, made once and shared: tests/klt_ref.py has them, for tests/test_klt_ref.py too ---------------------------------------
+hard_pyramids, smooth_pyramid, points_for, lam_for, combos, want_chain = K.hard_pyramids, K.smooth_pyramid, K.points_for, K.lam_for, K.combos, K.want_chain
 
 
 # ---- a launch on guarded buffers ------------------------------------------------------------------------------------------------------
@@ -143,41 +95,15 @@ def check(got, want, what, names=("points", "status", "history", "sad", "stats")
             same(g, w, f"{what}: {name}")
 
 
-_WANT = {}
-
-
-def want_chain(key, pyramids, pts, status, pair0, prm):
-    """the referee's chain, computed once per key and shared"""
-    if key not in _WANT:
-        _WANT[key] = K.track_chain(pyramids, pts, status, pair0, prm)
-        for a in _WANT[key]:
-            a.setflags(write=False)
-    return _WANT[key]
-
-
-def lam_for(win):
-    """a min_lambda between the flat / striped / weak windows and the textured ones of the test frames"""
-    return float(np.float32(2.0e5 * win * win))
-
-
-def combos(windows):
-    """(window, max_iters, eps_q, min_lambda, max_sad, n_points): every window with every n_points; the other parameters take
-    both of their values at every window"""
-    out = []
-    for win in windows:
-        for j, n in enumerate((1, 63, 65, 257)):
-            out.append(K.Params(win, (1, 32, 32, 4)[j], (0, 1, 0, 1)[j], (0.0, lam_for(win), 0.0, lam_for(win))[j], (0, 0, 60 * win * win, 200 * win * win)[j]) + (n,))
-    return out
-
-
 # ---- 1. one pair --------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("w,h,levels", SHAPES)
 def test_a_pair_on_the_hard_frame_equals_the_referee(eng, w, h, levels):
-    """windows 3, 9, 23 (and 5, 21 at 67 x 45) x 1, 63, 65, 257 points -- ragged waves and blocks -- with one and 32 iterations,
-    eps_q 0 and 1, min_lambda and max_sad off and on; each once with tight pitches and once with padded ones, the surroundings of
-    the planes differing"""
+    """windows 3, 9, 23 (at 67 x 45 every window 3 .. 23: each instance of klt_kernel<R>, M = 1 .. 9 window pixels per lane) x 1,
+    63, 65, 257 points -- ragged waves and blocks -- with one and 32 iterations, eps_q 0 and 1, min_lambda and max_sad off and on;
+    each once with tight pitches and once with padded ones, the surroundings of the planes differing.  tests/test_klt_ref.py shows
+    that at 67 x 45 the referee's result at a window is not its result at a neighbouring one."""
     pa, pb = hard_pyramids(w, h, levels)
-    windows = (3, 5, 9, 21, 23) if (w, h) == (67, 45) else (3, 9, 23)
+    windows = K.ALL_WINDOWS if (w, h, levels) == K.HARD_SHAPE else (3, 9, 23)
     reasons = np.zeros(6, np.int64)
     clips = [Clip([pa, pb], loose, AROUND_P[loose]) for loose in (0, 1)]
     for i, c in enumerate(combos(windows)):
@@ -206,6 +132,69 @@ def test_a_pair_on_the_smooth_texture_equals_the_referee(eng, w, h, levels):
             check(run(eng, clip, prm, 1, pts, status), want, f"{w}x{h} shift ({sx}, {sy}) window {win}")
             lost += int((want[1][status == 0] != 0).sum())
     assert lost > 0                                               # the motion drives points OUT
+
+
+# ---- 1b. the regimes of csrc/klt.hip beyond the everyday ones; tests/test_klt_ref.py holds the conditions on these inputs ----------------
+@pytest.mark.parametrize("window", K.TURN_WINDOWS)
+def test_more_points_than_waves_are_taken_in_turn(eng, window):
+    """32 768 + 261 points on two pairs: the launch has 8192 blocks of four waves, so 261 waves come round a second time (the stride
+    of the point loop) and 66 blocks gather more points than they have waves in their LDS counters before the one global atomic.  The stats are
+    sums over all points: a point visited twice or not at all shows there as well as in its own row."""
+    pyr, pts, status, pair0, prm, want = K.turn_case(window)
+    assert len(pts) == K.TURN_N == 4 * 8192 + 261 and pair0 > 1
+    lost = want[4][:, 1:5].sum(axis=1)
+    assert (lost > 0).all() and (want[1][K.TURN_FIRST:] == 0).any() and len(set((want[1][K.TURN_FIRST:][status[K.TURN_FIRST:] == 0] & 255).tolist()) - {0}) >= 3
+    print(f"window {window}: stats {want[4].tolist()}")
+    loose = int(window == 5)
+    check(run(eng, Clip(pyr, loose, AROUND_P[loose]), prm, pair0, pts, status), want, f"{K.TURN_N} points, window {window}")
+
+
+def _max_levels():
+    text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "ofx.h")).read()
+    return int(re.search(r"#define\s+OFX_TRACK_MAX_LEVELS\s+(\d+)\b", text).group(1))
+
+
+@pytest.mark.parametrize("w,h,levels", K.DEEP_SHAPES)
+def test_pyramids_of_6_7_and_8_levels_equal_the_referee(eng, w, h, levels):
+    """up to OFX_TRACK_MAX_LEVELS levels -- the whole plane table of the kernel arguments -- down to coarsest levels of 6 x 2, 4 x 2,
+    2 x 1 and 1 x 1 pixels, where every tap of a patch is clamped; without min_lambda those throw most points far OUT (d of many
+    pixels, doubled level by level), with it they are SINGULAR and skipped"""
+    assert _max_levels() == 8 == max(s[2] for s in K.DEEP_SHAPES)
+    assert (w >> (levels - 1)) >= 1 and (h >> (levels - 1)) >= 1 and levels >= 6
+    reasons = np.zeros(6, np.int64)
+    clips = {}
+    for name, pyr, pts, status, pair0, prm, loose, want in K.deep_cases(w, h, levels):
+        key = (id(pyr[1]), loose)
+        if key not in clips:
+            clips[key] = Clip(pyr, loose, AROUND_P[(loose + levels) % 3])
+        reasons += K.reasons_of(want, status)
+        check(run(eng, clips[key], prm, pair0, pts, status), want, name)
+    print(f"{w}x{h}x{levels}: tracked and lost by reason {reasons.tolist()}")
+    assert reasons[0] > 0 and reasons[K.OUT] > 0 and reasons[K.SINGULAR] > 0
+
+
+@pytest.mark.parametrize("window", K.WIDE_WINDOWS)
+def test_the_widest_plane_is_tracked_at_its_right_edge(eng, window):
+    """w = 2^19, the widest the call accepts: lattice coordinates up to 2^24 - 32, where float32 is exact to the unit and no
+    further.  Both the tight pitch and a padded one, at odd addresses"""
+    pyr, pts, status, pair0, prm, want = K.wide_case(window)
+    assert pyr[0][0].shape == (3, 1 << 19)
+    ok = want[1] == 0
+    assert ok.sum() >= 200 and ((want[1] & 255) == K.OUT).any() and want[0][ok, 0].max() > (1 << 19) - 4
+    for loose in (0, 1):
+        check(run(eng, Clip(pyr, loose, AROUND_P[1 + loose]), prm, pair0, pts, status), want, f"w = 2^19, window {window}, loose {loose}")
+
+
+@pytest.mark.parametrize("levels", K.SAT_LEVELS)
+def test_a_checkerboard_of_full_contrast_equals_the_referee(eng, levels):
+    """|gx| = 8160 at every window pixel: window sums of 2^35 at window 23 and lane partial sums within a factor 3.6 of int32 --
+    the largest that an image can make them"""
+    for kind in K.SAT_KINDS:
+        clip = None
+        for window in K.SAT_WINDOWS:
+            pyr, pts, status, pair0, prm, want = K.sat_case(levels, window, kind)
+            clip = clip or Clip(pyr, kind == "inverse", AROUND_P[levels % 3])
+            check(run(eng, clip, prm, pair0, pts, status), want, f"checkerboard {kind}, {levels} levels, window {window}")
 
 
 # ---- 2. chains ------------------------------------------------------------------------------------------------------------------------

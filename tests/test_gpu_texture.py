@@ -15,12 +15,7 @@ pytestmark = pytest.mark.gpu
 
 OFX_E_INVALID = 1
 NB = 16                                                   # OFX_STREAM_MAX_BATCH
-STRIP = 64                                                # kStrip of csrc/texture.hip: the output rows of a block
-
-
-def tile_out(win):
-    """the output columns of a block of csrc/texture.hip: kTile - 2R"""
-    return 256 - 2 * (win >> 1)
+STRIP, tile_out = T.STRIP, T.tile_out                     # kStrip and kTile - 2R of csrc/texture.hip: a block's output rows and columns
 
 
 def shapes(win):
@@ -141,6 +136,24 @@ def test_strength_equals_the_referee(eng, orc, win):
             launch(eng, items, win)
             for it, (kind, w, h) in zip(items, batch):
                 it.check(orc, want_strength(orc, kind, w, h, win), f"win {win} run {run} {kind} {w}x{h}")
+
+
+@pytest.mark.parametrize("win", [w for w in T.ALL_WINDOWS if w not in T.WINDOWS])
+def test_strength_of_every_other_instance_equals_the_referee(eng, orc, win):
+    """the eight instances of strength_kernel<R> that T.WINDOWS leaves out, each on the fewest shapes and inputs that tell its
+    constants -- the ring's 2R + 1 rows and its wrap, the phases of the march, OUT_W = 256 - 2R and with it the tile seams: twelve
+    items of mixed sizes in one launch, once with tight pitches and once with larger ones, as above.  tests/test_texture_ref.py
+    shows that on the two larger shapes the referee's plane at a window is not its plane at a neighbouring one."""
+    cases = [(kind, w, h) for (w, h) in T.instance_shapes(win) for kind in T.INSTANCE_INPUTS]
+    assert len(cases) <= NB
+    for run in (0, 1):
+        items = []
+        for j, (kind, w, h) in enumerate(cases):
+            loose = (j + run) & 1
+            items.append(Item(_img(kind, w, h), pad4(w) + 8 * loose, AROUND_P[run + 1], w + 3 * loose, lead=8 + 4 * loose))
+        launch(eng, items, win)
+        for it, (kind, w, h) in zip(items, cases):
+            it.check(orc, want_strength(orc, kind, w, h, win), f"win {win} run {run} {kind} {w}x{h}")
 
 
 @pytest.mark.parametrize("win", T.WINDOWS)

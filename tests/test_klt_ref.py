@@ -3,6 +3,7 @@ buys on a moving texture.  NumPy only: no library, no GPU."""
 import functools
 
 import numpy as np
+import pytest
 
 import klt_ref as K
 
@@ -175,3 +176,120 @@ def test_forward_backward_marks_what_does_not_come_back():
     assert np.array_equal(s2[~miss], s[~miss]) and np.array_equal(p2[~miss], p[~miss])
     wide = K.forward_backward(a, b, p, s, sad, pts, 1000.0, 1, prm)
     assert ((wide[1] != 0) == (s != 0) | ((s == 0) & (back[1] != 0))).all()
+
+
+# ---- the inputs of tests/test_gpu_klt.py's regimes: what the referee alone says about them -------------------------------------------
+def _same_result(a, b):
+    return all(np.array_equal(x.view(np.uint32) if x.dtype == np.float32 else x, y.view(np.uint32) if y.dtype == np.float32 else y) for x, y in zip(a, b))
+
+
+def test_every_window_reaches_every_reason_on_the_hard_frame():
+    """67 x 45, four levels, the four cases per window of klt_ref.combos: at each window from 3 to 19 there are tracked points and
+    points lost for each of the four reasons; at 21 and 23 no window of the frame is SINGULAR any more (measured: 0 of 257), and the
+    other three reasons are reached"""
+    assert K.ALL_WINDOWS == (3, 5, 7, 9, 11, 13, 15, 17, 19, 21, 23)
+    for win in K.ALL_WINDOWS:
+        reasons = np.zeros(6, np.int64)
+        for c in K.combos((win,)):
+            _, _, status, _, _, want = K.hard_case(c)
+            reasons += K.reasons_of(want, status)
+        print(f"window {win}: tracked and lost by reason {reasons.tolist()}")
+        must = [0, K.START, K.SINGULAR, K.OUT, K.RESIDUAL] if win <= 19 else [0, K.START, K.OUT, K.RESIDUAL]
+        assert (reasons[must] > 0).all() and reasons[5] == 0, (win, reasons.tolist())
+
+
+def test_on_the_hard_frame_no_window_gives_its_neighbours_result():
+    """A launch that ran the instance of the window next to the one asked for -- the same parameters, W - 2 or W + 2 in W's place --
+    must not pass: in the case of 257 points, and in the cases of 63 and 65, the referee's status or position differs for some
+    point; so does the stats row.  (The case of one point is a single random point: nothing is asked of it.)"""
+    for win in K.ALL_WINDOWS:
+        for c in K.combos((win,))[1:]:
+            pyr, pts, status, pair0, prm, want = K.hard_case(c)
+            for other in (win - 2, win + 2):
+                if other in K.ALL_WINDOWS:
+                    got = K.track_chain(pyr, pts, status, pair0, prm._replace(window=other))
+                    differ = (got[1] != want[1]) | (got[0].view(np.uint32) != want[0].view(np.uint32)).any(axis=1)
+                    print(f"window {win} as {other}, {c[5]} points: {int(differ.sum())} differ")
+                    assert differ.any() and not np.array_equal(got[4], want[4]), (win, other, c)
+
+
+@pytest.mark.parametrize("window", K.TURN_WINDOWS)
+def test_the_many_points_are_lost_in_both_pairs_and_past_the_first_visit(window):
+    """klt_ref.turn_case: of the points from index 32 768 on -- those a wave takes on its second visit -- some are tracked to the end,
+    some are lost for at least three different reasons, some come frozen; points are lost in both pairs; the specials stand at both
+    ends"""
+    pyr, pts, status, pair0, prm, want = K.turn_case(window)
+    F = K.TURN_FIRST
+    assert len(pts) == K.TURN_N == 32768 + 261 and F == 32768 and len(pyr) == 3 and pair0 > 1
+    assert prm == K.Params(window, 4, 1, 0.0, 60 * window * window)
+    sp = np.float32(K.specials(*K.HARD_SHAPE[:2])).view(np.uint32)
+    assert np.array_equal(pts[1:1 + len(sp)].view(np.uint32), sp) and np.array_equal(pts[F + 3:F + 3 + len(sp)].view(np.uint32), sp)
+    lattice = pts[30:F:2] * 32
+    assert (lattice == np.rint(lattice)).all() and not (pts[31:F:2] * 32 == np.rint(pts[31:F:2] * 32)).all(axis=1).all()       # half on, half off
+    tail, alive_in = want[1][F:], status[F:] == 0
+    assert (~alive_in).sum() >= 6 and np.array_equal(tail[~alive_in], status[F:][~alive_in])                                  # frozen: kept
+    assert np.array_equal(want[0][F:][~alive_in].view(np.uint32), pts[F:][~alive_in].view(np.uint32))
+    assert (tail[alive_in] == 0).any()
+    reasons = set((tail[alive_in] & 255).tolist()) - {0}
+    assert len(reasons) >= 3, reasons
+    pairs = set((tail[alive_in & (tail != 0)] >> 8).tolist())
+    assert pairs == {pair0, pair0 + 1}                                                    # ... and in both pairs
+    stats = want[4]
+    print(f"window {window}: stats {stats.tolist()}")
+    assert stats.shape == (2, 7) and (stats[:, 1:5].sum(axis=1) > 0).all() and stats[0, K.START] > 0
+    assert stats[0, :5].sum() == (status == 0).sum() and stats[1, :5].sum() == stats[0, 0]
+
+
+@pytest.mark.parametrize("w,h,levels", K.DEEP_SHAPES)
+def test_deep_pyramids_track_lose_and_skip_their_tiny_levels(w, h, levels):
+    """klt_ref.deep_cases: over a shape's cases points are tracked and go OUT, and with min_lambda the coarsest levels are SINGULAR"""
+    assert levels in (6, 7, 8) and ((w >> (levels - 1)), (h >> (levels - 1))) in ((6, 2), (4, 2), (2, 1), (1, 1))
+    cases = K.deep_cases(w, h, levels)
+    assert len(cases) == 12 and {c[6] for c in cases} == {0, 1}
+    total, with_lam = np.zeros(6, np.int64), np.zeros(6, np.int64)
+    for name, pyr, pts, status, pair0, prm, loose, want in cases:
+        assert len(pyr[0]) == levels and len(pts) == 129 and prm.max_iters == 10 and prm.eps_q == 1
+        r = K.reasons_of(want, status)
+        print(f"{name}: {r.tolist()}, iterations {int(want[4][0, 5])}")
+        total += r
+        if prm.min_lambda > 0:
+            with_lam += r
+    assert total[0] > 0 and total[K.OUT] > 0 and with_lam[K.SINGULAR] > 0
+    # the pair of each shift without min_lambda is tried with the tight pitch or the padded one, and with min_lambda with the other
+    assert all(a[6] != b[6] for a, b in zip(cases[0::2], cases[1::2]))
+
+
+@pytest.mark.parametrize("window", K.WIDE_WINDOWS)
+def test_the_widest_plane_is_followed_to_its_last_columns(window):
+    pyr, pts, status, pair0, prm, want = K.wide_case(window)
+    w, h = K.WIDE_W, K.WIDE_H
+    assert (w, h) == (1 << 19, 3) and pyr[0][0].shape == (h, w) and len(pyr[0]) == 1
+    a = pyr[0][0].astype(np.int32)
+    assert a.min() == 0 and a.max() == 255 and np.abs(np.diff(a, axis=1)).max() <= 2 * 51 + 1    # a box of five: a step is a fifth of the range, stretched
+    assert np.array_equal(pyr[1][0][:, 1:], pyr[0][0][:, :-1])
+    assert len(pts) == 257 and (pts[:, 0] >= w - 1 - 300).all() and (pts[:, 0] <= w - 1).all()
+    assert pts[:3].tolist() == [[w - 1, h - 1], [w - 1 - 1 / 32, 0], [w - 1.5, 1]]
+    ok = want[1] == 0
+    moved = want[0][ok] - pts[ok]
+    print(f"window {window}: {int(ok.sum())} tracked, {int(((want[1] & 255) == K.OUT).sum())} OUT, median motion {np.median(moved[:, 0])}, largest x {want[0][ok, 0].max()}")
+    assert ok.sum() >= 200 and ((want[1] & 255) == K.OUT).any() and want[0][ok, 0].max() > w - 4
+    assert np.median(moved[:, 0]) == 1.0
+
+
+def test_the_checkerboard_drives_the_sums_to_2_to_the_35():
+    a = K.sat_pyramids(1, "shifted")[0][0]
+    q = np.arange(-11, 12) * 32
+    gx = K.sample(a, 32 * 30 + 32 + q[None, :], 32 * 20 + q[:, None]) - K.sample(a, 32 * 30 - 32 + q[None, :], 32 * 20 + q[:, None])
+    assert (np.abs(gx) == 8160).all() and 2 ** 35 < int((gx * gx).sum()) == 529 * 8160 ** 2 < 2 ** 37
+    assert np.array_equal(K.sat_pyramids(3, "inverse")[1][0], 255 - K.sat_pyramids(3, "inverse")[0][0])
+    tracked = out = 0
+    for levels in K.SAT_LEVELS:
+        for kind in K.SAT_KINDS:
+            for window in K.SAT_WINDOWS:
+                _, pts, status, _, _, want = K.sat_case(levels, window, kind)
+                r = K.reasons_of(want, status)
+                print(f"{levels} levels, {kind}, window {window}: {r.tolist()}")
+                assert len(pts) == 257 and r[K.OUT] > 0
+                assert (r[0] > 0) != ((levels, kind, window) == (3, "inverse", 23))       # there every point goes OUT: kept
+                tracked, out = tracked + int(r[0]), out + int(r[K.OUT])
+    assert tracked > 0 and out > 0

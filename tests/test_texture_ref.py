@@ -144,3 +144,24 @@ def test_the_strength_rounds_once_and_is_never_negative_zero():
     assert s.dtype == np.float32 and not np.signbit(s).any() and not np.isnan(s).any()
     assert s[0] == 0 and s[1] == 0 and s[2] == 0 and s[4] == 0           # flat; Sxy^2 = Sxx Syy; one edge; the same with Sxy < 0
     assert s[3] == np.float32(0.5 * (2.0 ** 31 - np.sqrt(4.0 * float(2 ** 30 - 1) ** 2)))
+
+
+@pytest.mark.parametrize("win", T.ALL_WINDOWS)
+def test_no_window_has_its_neighbours_strength_on_the_instance_inputs(oracle, win):
+    """tests/test_gpu_texture.py runs every instance of the strength kernel on T.instance_shapes x T.INSTANCE_INPUTS.  A launch that
+    ran the instance of window W - 2 or W + 2 in W's place must not pass: on the two larger shapes the referee's planes of
+    neighbouring windows differ, by the bits, in more than 0.99 of the pixels on the noise and on the checkerboard (measured: in every
+    pixel) and in more than 0.75 on the hard frame (measured: 0.81 .. 0.95; its flat blocks have strength 0 at both).  The two
+    small shapes are there for the clipping: every window covers the whole of 1 x 1, and from 9 on the whole of 5 x 4."""
+    assert T.ALL_WINDOWS == (3, 5, 7, 9, 11, 13, 15, 17, 19, 21, 23) and set(T.WINDOWS) < set(T.ALL_WINDOWS)
+    shapes = T.instance_shapes(win)
+    assert shapes == [(256 - (win - 1) + 1, 65), (263, 75), (5, 4), (1, 1)]
+    for (w, h) in shapes[:2]:
+        for kind in T.INSTANCE_INPUTS:
+            img = T.make_input(kind, w, h)
+            R = T.strength(oracle, img, win)
+            for other in (win - 2, win + 2):
+                if other in T.ALL_WINDOWS:
+                    share = float((R.view(np.uint32) != T.strength(oracle, img, other).view(np.uint32)).mean())
+                    print(f"window {win} against {other}, {kind} {w}x{h}: {share:.4f} of the pixels differ")
+                    assert share > (0.75 if kind == "hard" else 0.99), (win, other, kind, w, h, share)

@@ -13,7 +13,21 @@ from cuda_optical_flow_2_amd import synth
 import iter_hard
 
 WINDOWS = (3, 9, 23)
+ALL_WINDOWS = tuple(range(3, 24, 2))                      # one instance of csrc/texture.hip's strength_kernel<R> each
 LK_FLOAT = 1
+STRIP = 64                                                # kStrip of csrc/texture.hip: the output rows of a block
+INSTANCE_INPUTS = ("noise", "checker", "hard")
+
+
+def tile_out(win):
+    """the output columns of a block of csrc/texture.hip: kTile - 2R"""
+    return 256 - 2 * (win >> 1)
+
+
+def instance_shapes(win):
+    """(w, h), the fewest that still tell an instance's constants: one column past a tile seam and one row past a strip (the ring of
+    2R + 1 rows wraps 65 / (2R + 1) times), two tiles and two strips of odd size, a field smaller than the window, one pixel"""
+    return [(tile_out(win) + 1, STRIP + 1), (263, 75), (5, 4), (1, 1)]
 
 
 # ---- the definition -----------------------------------------------------------------------------------------------------------
