@@ -155,7 +155,7 @@ int ofx_consistency_batch_launch(const ofx_consistency_batch *a, void *stream)
 {
     const char *who = "ofx_consistency_batch_launch";
     OFX_REQUIRE(a, "%s: bad arguments", who);
-    OFX_TRY(check_batch(who, a->n, a->w, a->h, {}, {a->fwd, a->bwd}, a->stats));
+    OFX_TRY(check_batch(who, a->n, a->w, a->h, 1, {}, {a->fwd, a->bwd}, a->stats));
     OFX_REQUIRE(__builtin_isfinite(a->scale), "%s: the scale must be finite", who);
     OFX_REQUIRE(__builtin_isfinite(a->alpha) && a->alpha >= 0.0f && __builtin_isfinite(a->beta) && a->beta >= 0.0f,
                 "%s: alpha and beta must be finite and >= 0", who);

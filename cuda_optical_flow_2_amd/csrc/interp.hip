@@ -23,16 +23,22 @@
 // A quad of a frame leaves as one dword where the quad is whole and every destination, dst_pitch and the time stride are 4-byte
 // aligned, else as bytes.  The counts: a thread keeps one packed counter per time (8 bits per class: at most 16 pixels a thread)
 // in its own LDS word, touched only for a quad that has a pixel of class 1, 2 or 3; at the end each time's counters go through
-// the block reduction described in quad_stage.h into the time's slot, all times under one barrier.
+// the block reduction into the time's slot, all times under one barrier.
+//
+// interp_kernel shares its first and its last part with interp3.hip's kernel, as text: interp_part_prologue.h (the resources and
+// the geometry of one side of one pixel, with the planes' bytes per pixel as this file's constant kBpp) and interp_part_reduce.h
+// (the counts); the host side of both units is interp_host.h.
 #include <string.h>
 
-#include "quad_stage.h"
+#include "interp_host.h"
 
 namespace {
 
 using namespace quad;
 
-constexpr int kVecs = 4; // displacement: 16-byte (or 8-byte) items per thread, kThreads apart
+constexpr int kBpp = 1;                                // interpolation: the planes' bytes per pixel (interp_part_prologue.h)
+constexpr InterpNames kNames = {"d_a", "d_b", "d_dst"}; // ... and their names in the entry points' messages
+constexpr int kVecs = 4;                               // displacement: 16-byte (or 8-byte) items per thread, kThreads apart
 
 __global__ __launch_bounds__(kThreads) void displacement_kernel(const ofx_displacement_batch A, const int vec16)
 {
@@ -75,40 +81,7 @@ __global__ __launch_bounds__(kThreads) void displacement_kernel(const ofx_displa
 
 __global__ __launch_bounds__(kThreads) void interp_kernel(const ofx_interp_batch A, const int dwords)
 {
-    __shared__ uint32_t cnt[OFX_INTERP_MAX_TIMES][kThreads];
-    __shared__ uint32_t red[kThreads / 64][OFX_INTERP_MAX_TIMES][3];
-    const int b = blockIdx.y;
-    const int w = A.w, h = A.h, wmax = w - 1, hmax = h - 1, nt = A.n_times;
-    const int ap = A.a_pitch[b], bp = A.b_pitch[b];
-    const __amdgpu_buffer_rsrc_t rs_a = rsrc(A.a[b], hmax * ap + w), rs_b = rsrc(A.b[b], hmax * bp + w);
-    const __amdgpu_buffer_rsrc_t rs_ab = rsrc(A.dab[b], w * h * 8), rs_ba = rsrc(A.dba[b], w * h * 8);
-    uint8_t *dst = A.dst[b];
-    unsigned long long *stats = A.stats[b];
-    const float wmaxf = (float)wmax, hmaxf = (float)hmax;
-    const uint32_t qrow = quads_per_row(w), n_quads = qrow * (uint32_t)h;
-    if (stats)
-        for (int ti = 0; ti < nt; ++ti) cnt[ti][threadIdx.x] = 0; // (a thread's own words: no barrier needed)
-
-    // a quad's two fields, Dab in f[0 .. 7] and Dba in f[8 .. 15]
-    auto load_fields = [&](bool in, int y, int x0, float *f) {
-        load_field(rs_ab, w, in, y, x0, f);
-        load_field(rs_ba, w, in, y, x0, f + 8);
-    };
-    // steps 3 to 5 of one side of one pixel, up to the taps: the offsets of the left taps of its two tap rows, whether the right
-    // taps are one byte further (x0 < w - 1) or the same byte, and the fractions.  Returns "usable".
-    auto side = [&](float px, float py, float xf, float yf, int pitch, bool live, uint32_t &o0, uint32_t &o1, uint32_t &dx, float &fx,
-                    float &fy) -> bool {
-        const bool fin = __builtin_fabsf(px) <= 1e9f && __builtin_fabsf(py) <= 1e9f; // (a NaN fails)
-        const bool usable = fin && px >= 0.0f && px <= wmaxf && py >= 0.0f && py <= hmaxf;
-        const float sx = fin ? __builtin_amdgcn_fmed3f(px, 0.0f, wmaxf) : xf;
-        const float sy = fin ? __builtin_amdgcn_fmed3f(py, 0.0f, hmaxf) : yf;
-        const int xi = (int)sx, yi = (int)sy;
-        fx = sx - (float)xi, fy = sy - (float)yi;
-        const int y1 = min(yi + 1, hmax);
-        o0 = live ? (uint32_t)(yi * pitch + xi) : kNowhere, o1 = live ? (uint32_t)(y1 * pitch + xi) : kNowhere;
-        dx = xi < wmax ? 1u : 0u;
-        return usable;
-    };
+#include "interp_part_prologue.h"
 
     int y, x0, y_next = 0, x0_next = 0;
     float f[16], f_next[16];
@@ -196,31 +169,7 @@ __global__ __launch_bounds__(kThreads) void interp_kernel(const ofx_interp_batch
 #pragma unroll
         for (int k = 0; k < 16; ++k) f[k] = f_next[k];
     }
-    if (!stats) return; // (block-uniform)
-    // the block reduction (the rule: quad_stage.h), per time and written out as in the other two kernels
-    for (int ti = 0; ti < nt; ++ti) {
-        const uint32_t pk = cnt[ti][threadIdx.x];
-        uint32_t n1 = pk & 0xffu, n2 = (pk >> 8) & 0xffu, n3 = (pk >> 16) & 0xffu;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            n1 += __shfl_xor(n1, o);
-            n2 += __shfl_xor(n2, o);
-            n3 += __shfl_xor(n3, o);
-        }
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][ti][0] = n1, red[threadIdx.x >> 6][ti][1] = n2, red[threadIdx.x >> 6][ti][2] = n3;
-    }
-    __syncthreads();
-    const int ti = threadIdx.x >> 2, c = threadIdx.x & 3; // thread 4 * ti + c: word c of time ti
-    if (ti < nt) {
-        if (c) {
-            unsigned long long s = 0;
-#pragma unroll
-            for (int i = 0; i < kThreads / 64; ++i) s += red[i][ti][c - 1];
-            if (s) atomicAdd(stats + 4 * ti + c, s);
-        } else if (blockIdx.x == 0) {
-            atomicAdd(stats + 4 * ti, (unsigned long long)w * (unsigned long long)h);
-        }
-    }
+#include "interp_part_reduce.h"
 }
 
 } // namespace
@@ -258,25 +207,7 @@ extern "C" int ofx_flow_displacement(const float *d_flow, int w, int h, const fl
 
 int ofx_interp_batch_launch(const ofx_interp_batch *a, void *stream)
 {
-    const char *who = "ofx_interp_batch_launch";
-    OFX_REQUIRE(a, "%s: bad arguments", who);
-    OFX_TRY(check_batch(who, a->n, a->w, a->h, {a->a_pitch, a->b_pitch}, {a->dab, a->dba}, a->stats));
-    OFX_REQUIRE(a->n_times >= 1 && a->n_times <= OFX_INTERP_MAX_TIMES, "%s: n_times = %d is not in 1 .. %d", who, a->n_times, OFX_INTERP_MAX_TIMES);
-    for (int k = 0; k < a->n_times; ++k)
-        OFX_REQUIRE(__builtin_isfinite(a->t[k]) && a->t[k] > 0.0f && a->t[k] < 1.0f, "%s: h_times[%d] = %g is not in (0, 1)", who, k, (double)a->t[k]);
-    OFX_REQUIRE(a->dst_pitch >= a->w, "%s: dst_pitch %d is below the width %d", who, a->dst_pitch, a->w);
-    OFX_REQUIRE(a->n_times == 1 || a->time_stride >= (size_t)a->h * (size_t)a->dst_pitch,
-                "%s: time_stride_bytes %zu is below a frame's h * dst_pitch = %zu bytes", who, a->time_stride, (size_t)a->h * (size_t)a->dst_pitch);
-    bool dwords = (a->dst_pitch & 3) == 0 && (a->n_times == 1 || (a->time_stride & 3) == 0);
-    for (int i = 0; i < a->n; ++i) {
-        OFX_REQUIRE(a->a[i] && a->b[i], "%s: pair %d: a null plane (d_a, d_b)", who, i);
-        OFX_REQUIRE(a->dst[i], "%s: pair %d: d_dst is null", who, i);
-        dwords = dwords && ((uintptr_t)a->dst[i] & 3) == 0;
-    }
-    OFX_TRY(zero_stats(a->stats, a->n, 4 * (size_t)a->n_times, stream)); // (everything is checked; a slot: four words per time)
-    hipLaunchKernelGGL(interp_kernel, grid(a->w, a->h, a->n), dim3(kThreads), 0, ofx_stream(stream), *a, (int)dwords);
-    OFX_HIP(hipGetLastError());
-    return OFX_OK;
+    return interp_launch("ofx_interp_batch_launch", interp_kernel, kBpp, kNames, a, stream);
 }
 
 extern "C" int ofx_interpolate_frames_batch(const uint8_t *const *d_a, const int *a_pitches, const uint8_t *const *d_b, const int *b_pitches, int n,
@@ -284,26 +215,9 @@ extern "C" int ofx_interpolate_frames_batch(const uint8_t *const *d_a, const int
                                             int n_times, uint8_t *const *d_dst, int dst_pitch, size_t time_stride_bytes, int64_t *const *d_stats,
                                             void *stream)
 {
-    const char *who = "ofx_interpolate_frames_batch";
-    OFX_REQUIRE(d_a && d_b && a_pitches && b_pitches, "%s: null plane or pitch array (d_a, d_b, a_pitches, b_pitches)", who);
-    OFX_REQUIRE(d_disp_ab && d_disp_ba, "%s: null field array (d_disp_ab, d_disp_ba)", who);
-    OFX_REQUIRE(d_dst, "%s: d_dst is null", who);
-    OFX_REQUIRE(h_times, "%s: h_times is null", who);
-    OFX_REQUIRE(n >= 1 && n <= OFX_STREAM_MAX_BATCH, "%s: n = %d is not in 1 .. %d", who, n, OFX_STREAM_MAX_BATCH);
-    OFX_REQUIRE(n_times >= 1 && n_times <= OFX_INTERP_MAX_TIMES, "%s: n_times = %d is not in 1 .. %d", who, n_times, OFX_INTERP_MAX_TIMES);
     static thread_local ofx_interp_batch ib;
-    memset(&ib, 0, sizeof ib);
-    ib.n = n, ib.w = w, ib.h = h, ib.n_times = n_times, ib.dst_pitch = dst_pitch, ib.time_stride = time_stride_bytes;
-    for (int k = 0; k < n_times; ++k) { // the definition's host step, in float32
-        const float t = h_times[k], omt = 1.0f - t;
-        ib.t[k] = t, ib.c00[k] = -(omt * t), ib.c01[k] = t * t, ib.c10[k] = omt * omt;
-    }
-    for (int i = 0; i < n; ++i) {
-        OFX_REQUIRE(d_a[i] && d_b[i] && d_disp_ab[i] && d_disp_ba[i] && d_dst[i] && (!d_stats || d_stats[i]), "%s: pair %d: a null entry in an array", who, i);
-        ib.a[i] = d_a[i], ib.a_pitch[i] = a_pitches[i], ib.b[i] = d_b[i], ib.b_pitch[i] = b_pitches[i];
-        ib.dab[i] = d_disp_ab[i], ib.dba[i] = d_disp_ba[i], ib.dst[i] = d_dst[i];
-        ib.stats[i] = d_stats ? reinterpret_cast<unsigned long long *>(d_stats[i]) : nullptr;
-    }
+    OFX_TRY(interp_fill_batch("ofx_interpolate_frames_batch", kNames, &ib, d_a, a_pitches, d_b, b_pitches, n, w, h, d_disp_ab, d_disp_ba, h_times,
+                              n_times, d_dst, dst_pitch, time_stride_bytes, d_stats));
     return ofx_interp_batch_launch(&ib, stream); // (checks every argument before it enqueues anything)
 }
 

@@ -35,13 +35,17 @@
 // A whole quad of a frame (12 bytes at row + 12 * (x0 / 4)) leaves as three dwords where every destination, dst_pitch and the time
 // stride are 4-byte aligned, else as bytes.  The counts are interp.hip's: a packed per-time LDS word per thread (8 bits per class:
 // at most 16 pixels a thread), one barrier, 64-bit atomics into slots the launch has zeroed on the stream.
-#include <string.h>
-
-#include "quad_stage.h"
+//
+// The kernel's first and last part are interp_kernel's, as text: interp_part_prologue.h with kBpp = 3 and interp_part_reduce.h;
+// the host side is interp_host.h's, with every pitch against 3 * w.
+#include "interp_host.h"
 
 namespace {
 
 using namespace quad;
+
+constexpr int kBpp = 3;                                    // the planes' bytes per pixel (interp_part_prologue.h)
+constexpr InterpNames kNames = {"d_a3", "d_b3", "d_dst3"}; // ... and their names in the entry points' messages
 
 typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
 typedef u32x3 u32x3_a4 __attribute__((aligned(4)));
@@ -52,40 +56,7 @@ __device__ __forceinline__ float tap_right(uint32_t d, uint32_t e, int c) { retu
 
 __global__ __launch_bounds__(kThreads) void interp3_kernel(const ofx_interp3_batch A, const int dwords)
 {
-    __shared__ uint32_t cnt[OFX_INTERP_MAX_TIMES][kThreads];
-    __shared__ uint32_t red[kThreads / 64][OFX_INTERP_MAX_TIMES][3];
-    const int b = blockIdx.y;
-    const int w = A.w, h = A.h, wmax = w - 1, hmax = h - 1, nt = A.n_times;
-    const int ap = A.a_pitch[b], bp = A.b_pitch[b];
-    const __amdgpu_buffer_rsrc_t rs_a = rsrc(A.a[b], hmax * ap + 3 * w), rs_b = rsrc(A.b[b], hmax * bp + 3 * w);
-    const __amdgpu_buffer_rsrc_t rs_ab = rsrc(A.dab[b], w * h * 8), rs_ba = rsrc(A.dba[b], w * h * 8);
-    uint8_t *dst = A.dst[b];
-    unsigned long long *stats = A.stats[b];
-    const float wmaxf = (float)wmax, hmaxf = (float)hmax;
-    const uint32_t qrow = quads_per_row(w), n_quads = qrow * (uint32_t)h;
-    if (stats)
-        for (int ti = 0; ti < nt; ++ti) cnt[ti][threadIdx.x] = 0; // (a thread's own words: no barrier needed)
-
-    // a quad's two fields, Dab in f[0 .. 7] and Dba in f[8 .. 15]
-    auto load_fields = [&](bool in, int y, int x0, float *f) {
-        load_field(rs_ab, w, in, y, x0, f);
-        load_field(rs_ba, w, in, y, x0, f + 8);
-    };
-    // steps 3 to 5 of one side of one pixel, up to the taps: the byte offsets of the left taps of its two tap rows, whether the
-    // right taps are the next pixel (x0 < w - 1) or the same one, and the fractions.  Returns "usable".
-    auto side = [&](float px, float py, float xf, float yf, int pitch, bool live, uint32_t &o0, uint32_t &o1, uint32_t &dx, float &fx,
-                    float &fy) -> bool {
-        const bool fin = __builtin_fabsf(px) <= 1e9f && __builtin_fabsf(py) <= 1e9f; // (a NaN fails)
-        const bool usable = fin && px >= 0.0f && px <= wmaxf && py >= 0.0f && py <= hmaxf;
-        const float sx = fin ? __builtin_amdgcn_fmed3f(px, 0.0f, wmaxf) : xf;
-        const float sy = fin ? __builtin_amdgcn_fmed3f(py, 0.0f, hmaxf) : yf;
-        const int xi = (int)sx, yi = (int)sy;
-        fx = sx - (float)xi, fy = sy - (float)yi;
-        const int y1 = min(yi + 1, hmax);
-        o0 = live ? (uint32_t)(yi * pitch + 3 * xi) : kNowhere, o1 = live ? (uint32_t)(y1 * pitch + 3 * xi) : kNowhere;
-        dx = xi < wmax ? 1u : 0u;
-        return usable;
-    };
+#include "interp_part_prologue.h"
     // one tap row: (the dword at o, the two bytes behind it) -- six bytes that lie inside the row when the right tap is the next pixel
     auto row_wide = [&](const __amdgpu_buffer_rsrc_t &rs, uint32_t o, uint32_t &d, uint32_t &e) {
         d = __builtin_amdgcn_raw_buffer_load_b32(rs, o, 0, 0);
@@ -200,67 +171,14 @@ __global__ __launch_bounds__(kThreads) void interp3_kernel(const ofx_interp3_bat
 #pragma unroll
         for (int k = 0; k < 16; ++k) f[k] = f_next[k];
     }
-    if (!stats) return; // (block-uniform)
-    // the block reduction (the rule: quad_stage.h), per time and written out as in interp_kernel
-    for (int ti = 0; ti < nt; ++ti) {
-        const uint32_t pk = cnt[ti][threadIdx.x];
-        uint32_t n1 = pk & 0xffu, n2 = (pk >> 8) & 0xffu, n3 = (pk >> 16) & 0xffu;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            n1 += __shfl_xor(n1, o);
-            n2 += __shfl_xor(n2, o);
-            n3 += __shfl_xor(n3, o);
-        }
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][ti][0] = n1, red[threadIdx.x >> 6][ti][1] = n2, red[threadIdx.x >> 6][ti][2] = n3;
-    }
-    __syncthreads();
-    const int ti = threadIdx.x >> 2, c = threadIdx.x & 3; // thread 4 * ti + c: word c of time ti
-    if (ti < nt) {
-        if (c) {
-            unsigned long long s = 0;
-#pragma unroll
-            for (int i = 0; i < kThreads / 64; ++i) s += red[i][ti][c - 1];
-            if (s) atomicAdd(stats + 4 * ti + c, s);
-        } else if (blockIdx.x == 0) {
-            atomicAdd(stats + 4 * ti, (unsigned long long)w * (unsigned long long)h);
-        }
-    }
+#include "interp_part_reduce.h"
 }
 
 } // namespace
 
 int ofx_interp3_batch_launch(const ofx_interp3_batch *a, void *stream)
 {
-    const char *who = "ofx_interp3_batch_launch";
-    OFX_REQUIRE(a, "%s: bad arguments", who);
-    // check_batch's rules with every pitch against 3 * w (w > 0 is asked first: 3 * w cannot overflow below 2^28 pixels)
-    OFX_REQUIRE(a->n >= 1 && a->n <= OFX_STREAM_MAX_BATCH, "%s: bad arguments: n = %d pairs is not in 1 .. %d", who, a->n, OFX_STREAM_MAX_BATCH);
-    OFX_REQUIRE(a->w > 0 && a->h > 0, "%s: w = %d, h = %d must be positive", who, a->w, a->h);
-    OFX_REQUIRE((size_t)a->w * (size_t)a->h < ((size_t)1 << 28), "%s: w * h = %d x %d is more than this build takes (2^28 pixels)", who, a->w, a->h);
-    const int w3 = 3 * a->w;
-    OFX_REQUIRE(a->n_times >= 1 && a->n_times <= OFX_INTERP_MAX_TIMES, "%s: n_times = %d is not in 1 .. %d", who, a->n_times, OFX_INTERP_MAX_TIMES);
-    for (int k = 0; k < a->n_times; ++k)
-        OFX_REQUIRE(__builtin_isfinite(a->t[k]) && a->t[k] > 0.0f && a->t[k] < 1.0f, "%s: h_times[%d] = %g is not in (0, 1)", who, k, (double)a->t[k]);
-    OFX_REQUIRE(a->dst_pitch >= w3, "%s: dst_pitch %d is below a row's 3 * w = %d bytes", who, a->dst_pitch, w3);
-    OFX_REQUIRE(a->n_times == 1 || a->time_stride >= (size_t)a->h * (size_t)a->dst_pitch,
-                "%s: time_stride_bytes %zu is below a frame's h * dst_pitch = %zu bytes", who, a->time_stride, (size_t)a->h * (size_t)a->dst_pitch);
-    bool dwords = (a->dst_pitch & 3) == 0 && (a->n_times == 1 || (a->time_stride & 3) == 0);
-    for (int i = 0; i < a->n; ++i) {
-        OFX_REQUIRE(a->a[i] && a->b[i], "%s: pair %d: a null plane (d_a3, d_b3)", who, i);
-        OFX_REQUIRE(a->dab[i] && a->dba[i], "%s: pair %d: a null field (d_disp_ab, d_disp_ba)", who, i);
-        OFX_REQUIRE(a->dst[i], "%s: pair %d: d_dst3 is null", who, i);
-        OFX_REQUIRE(a->a_pitch[i] >= w3 && a->b_pitch[i] >= w3, "%s: pair %d: a row pitch (%d, %d) below a row's 3 * w = %d bytes", who, i,
-                    a->a_pitch[i], a->b_pitch[i], w3);
-        OFX_REQUIRE((size_t)a->h * (size_t)a->a_pitch[i] < ((size_t)1 << 31) && (size_t)a->h * (size_t)a->b_pitch[i] < ((size_t)1 << 31),
-                    "%s: pair %d: a plane of 2^31 bytes or more (h * pitch)", who, i);
-        OFX_REQUIRE((((uintptr_t)a->dab[i] | (uintptr_t)a->dba[i]) & 7) == 0, "%s: pair %d: the fields (d_disp_ab, d_disp_ba) must be 8-byte aligned", who, i);
-        OFX_REQUIRE(((uintptr_t)a->stats[i] & 7) == 0, "%s: pair %d: d_stats must be 8-byte aligned", who, i);
-        dwords = dwords && ((uintptr_t)a->dst[i] & 3) == 0;
-    }
-    OFX_TRY(zero_stats(a->stats, a->n, 4 * (size_t)a->n_times, stream)); // (everything is checked; a slot: four words per time)
-    hipLaunchKernelGGL(interp3_kernel, grid(a->w, a->h, a->n), dim3(kThreads), 0, ofx_stream(stream), *a, (int)dwords);
-    OFX_HIP(hipGetLastError());
-    return OFX_OK;
+    return interp_launch("ofx_interp3_batch_launch", interp3_kernel, kBpp, kNames, a, stream);
 }
 
 extern "C" int ofx_interpolate_frames_3ch_batch(const uint8_t *const *d_a3, const int *a_pitches, const uint8_t *const *d_b3, const int *b_pitches,
@@ -268,26 +186,9 @@ extern "C" int ofx_interpolate_frames_3ch_batch(const uint8_t *const *d_a3, cons
                                                 const float *h_times, int n_times, uint8_t *const *d_dst3, int dst_pitch, size_t time_stride_bytes,
                                                 int64_t *const *d_stats, void *stream)
 {
-    const char *who = "ofx_interpolate_frames_3ch_batch";
-    OFX_REQUIRE(d_a3 && d_b3 && a_pitches && b_pitches, "%s: null plane or pitch array (d_a3, d_b3, a_pitches, b_pitches)", who);
-    OFX_REQUIRE(d_disp_ab && d_disp_ba, "%s: null field array (d_disp_ab, d_disp_ba)", who);
-    OFX_REQUIRE(d_dst3, "%s: d_dst3 is null", who);
-    OFX_REQUIRE(h_times, "%s: h_times is null", who);
-    OFX_REQUIRE(n >= 1 && n <= OFX_STREAM_MAX_BATCH, "%s: n = %d is not in 1 .. %d", who, n, OFX_STREAM_MAX_BATCH);
-    OFX_REQUIRE(n_times >= 1 && n_times <= OFX_INTERP_MAX_TIMES, "%s: n_times = %d is not in 1 .. %d", who, n_times, OFX_INTERP_MAX_TIMES);
     static thread_local ofx_interp3_batch ib;
-    memset(&ib, 0, sizeof ib);
-    ib.n = n, ib.w = w, ib.h = h, ib.n_times = n_times, ib.dst_pitch = dst_pitch, ib.time_stride = time_stride_bytes;
-    for (int k = 0; k < n_times; ++k) { // the definition's host step, in float32
-        const float t = h_times[k], omt = 1.0f - t;
-        ib.t[k] = t, ib.c00[k] = -(omt * t), ib.c01[k] = t * t, ib.c10[k] = omt * omt;
-    }
-    for (int i = 0; i < n; ++i) {
-        OFX_REQUIRE(d_a3[i] && d_b3[i] && d_disp_ab[i] && d_disp_ba[i] && d_dst3[i] && (!d_stats || d_stats[i]), "%s: pair %d: a null entry in an array", who, i);
-        ib.a[i] = d_a3[i], ib.a_pitch[i] = a_pitches[i], ib.b[i] = d_b3[i], ib.b_pitch[i] = b_pitches[i];
-        ib.dab[i] = d_disp_ab[i], ib.dba[i] = d_disp_ba[i], ib.dst[i] = d_dst3[i];
-        ib.stats[i] = d_stats ? reinterpret_cast<unsigned long long *>(d_stats[i]) : nullptr;
-    }
+    OFX_TRY(interp_fill_batch("ofx_interpolate_frames_3ch_batch", kNames, &ib, d_a3, a_pitches, d_b3, b_pitches, n, w, h, d_disp_ab, d_disp_ba,
+                              h_times, n_times, d_dst3, dst_pitch, time_stride_bytes, d_stats));
     return ofx_interp3_batch_launch(&ib, stream); // (checks every argument before it enqueues anything)
 }
 

@@ -14,9 +14,8 @@
 // so no NaN reaches v_min_f32 / v_max_f32 / v_med3_f32.  A column of the window is ordered once for all outputs that contain it;
 // the networks and the reason they select the median are in median_net.h.
 //
-// The filtered quad stays in registers: it leaves as prolong.hip's stores do (two 16-byte stores, a ragged end one 8-byte store
-// per pixel) and feeds prolong.hip's warp -- motion_ring.hip's arithmetic without the shift -- whose taps go through a buffer
-// resource of exactly the plane's (h - 1) * pitch + w bytes, at positions clamped before they become offsets.
+// The filtered quad stays in registers: it leaves by quad_part_flow_store.h and feeds the fused warp, quad_part_warp.h, the two
+// parts this kernel shares with prolong_kernel (the rules of both are stated there).
 //
 // Traffic: 8 B read and 8 B written per pixel, and with the warp 1 B of taps and 1 B written; the (2r + 1) rows x (4 + 2r) columns
 // a thread loads are its neighbours' too and come from the vector cache.
@@ -127,7 +126,7 @@ template <int R> __device__ __forceinline__ void median_march(const MedianItem &
     const float scale = P.scale;
     const int sp = P.src_pitch;
     const bool warp = P.src != nullptr;
-    const __amdgpu_buffer_rsrc_t rs_i = rsrc(P.src_flow, w * h * 8), rs_o = rsrc(P.dst_flow, w * h * 8);
+    const __amdgpu_buffer_rsrc_t rs_i = rsrc(P.src_flow, w * h * 8), rs_f = rsrc(P.dst_flow, w * h * 8);
     const __amdgpu_buffer_rsrc_t rs_s = rsrc(P.src, warp ? hmax * sp + w : 0);
     const float wmaxf = (float)wmax, hmaxf = (float)hmax;
 
@@ -138,67 +137,11 @@ template <int R> __device__ __forceinline__ void median_march(const MedianItem &
         const int npx = w - x0 < 4 ? w - x0 : 4;
         float fu[4], fv[4];
         median_quad<R>(rs_i, w, h, y, x0, npx, fu, fv);
-        const uint32_t fo = 8u * ((uint32_t)y * (uint32_t)w + (uint32_t)x0);
-        if (npx == 4) {
-            f32x4 lo4, hi4;
-            lo4[0] = fu[0], lo4[1] = fv[0], lo4[2] = fu[1], lo4[3] = fv[1];
-            hi4[0] = fu[2], hi4[1] = fv[2], hi4[2] = fu[3], hi4[3] = fv[3];
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(uint32_t)))) uint32_t, lo4), rs_o, fo, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(uint32_t)))) uint32_t, hi4), rs_o, fo, 16, 0);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                if (k < npx) {
-                    f32x2 p;
-                    p[0] = fu[k], p[1] = fv[k];
-                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(__attribute__((__vector_size__(2 * sizeof(uint32_t)))) uint32_t, p), rs_o, fo + 8u * k, 0, 0);
-                }
-        }
+        // the filtered quad leaves from registers
+#include "quad_part_flow_store.h"
         if (warp) { // (block-uniform)
-            // step 4: the warp of the quad by the vectors it holds (prolong.hip's, warp_row_prepare's operation order)
-            const float xf0 = (float)x0, yf = (float)y;
-            float fx[4], fy[4];
-            uint32_t o0[4], o1[4], dx[4];
-            bool wide = true;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float xr = xf0 + (float)k;
-                const float sxr = xr + scale * fu[k], syr = yf + scale * fv[k];
-                const bool ok = __builtin_fabsf(sxr) <= 1e9f && __builtin_fabsf(syr) <= 1e9f; // (a NaN fails: not warped)
-                const float sx = __builtin_amdgcn_fmed3f(ok ? sxr : xr, 0.0f, wmaxf);
-                const float sy = __builtin_amdgcn_fmed3f(ok ? syr : yf, 0.0f, hmaxf);
-                const int xi = (int)sx, yi = (int)sy;
-                fx[k] = __builtin_amdgcn_fractf(sx); // == sx - (float)xi: sx >= 0, the difference is exact
-                fy[k] = __builtin_amdgcn_fractf(sy);
-                const int y1 = min(yi + 1, hmax);
-                const bool live = k < npx; // (a pixel past the row's end has its clamped column: its taps read as 0, nobody looks)
-                const uint32_t a0 = (uint32_t)yi * (uint32_t)sp + (uint32_t)xi, a1 = (uint32_t)y1 * (uint32_t)sp + (uint32_t)xi;
-                o0[k] = live ? a0 : kNowhere, o1[k] = live ? a1 : kNowhere;
-                dx[k] = xi < wmax ? 1u : 0u;
-                wide = wide && (!live || dx[k]);
-            }
-            uint32_t r0[4], r1[4]; // per pixel (left, right) of the two tap rows in bytes 0 and 1
-            if (wide) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    r0[k] = __builtin_amdgcn_raw_buffer_load_b16(rs_s, o0[k], 0, 0);
-                    r1[k] = __builtin_amdgcn_raw_buffer_load_b16(rs_s, o1[k], 0, 0);
-                }
-            } else {
-                uint32_t l[2][4], r[2][4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    l[0][k] = __builtin_amdgcn_raw_buffer_load_b8(rs_s, o0[k], 0, 0);
-                    r[0][k] = __builtin_amdgcn_raw_buffer_load_b8(rs_s, o0[k] + dx[k], 0, 0);
-                    l[1][k] = __builtin_amdgcn_raw_buffer_load_b8(rs_s, o1[k], 0, 0);
-                    r[1][k] = __builtin_amdgcn_raw_buffer_load_b8(rs_s, o1[k] + dx[k], 0, 0);
-                }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) r0[k] = l[0][k] | (r[0][k] << 8), r1[k] = l[1][k] | (r[1][k] << 8);
-            }
-            uint32_t out = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) out |= round_u8(blend_u8(r0[k], r1[k], fx[k], fy[k])) << (8 * k);
+            // step 4: the warp of the quad by the vectors it holds
+#include "quad_part_warp.h"
             store_quad_u8(P.dst + (size_t)y * (size_t)P.dst_pitch + (size_t)x0, out, npx, P.dwords);
         }
     }
@@ -239,15 +182,8 @@ extern "C" int ofx_flow_median(const ofx_median_desc *items, int n, void *stream
         MedianItem &P = A.it[i];
         P = MedianItem{d.d_src_flow, d.d_dst_flow, d.d_src, d.d_dst, d.w, d.h, d.radius, 0, 0, 0, d.scale};
         if (d.d_src) {
-            OFX_REQUIRE(d.src_pitch >= d.w && d.dst_pitch >= d.w, "%s: item %d: a row pitch (src_pitch %d, dst_pitch %d) below the width %d", who, i,
-                        d.src_pitch, d.dst_pitch, d.w);
-            OFX_REQUIRE((size_t)d.h * (size_t)d.src_pitch < ((size_t)1 << 31) && (size_t)d.h * (size_t)d.dst_pitch < ((size_t)1 << 31),
-                        "%s: item %d: a plane of 2^31 bytes or more", who, i);
-            const uintptr_t s0 = (uintptr_t)d.d_src, s1 = s0 + (size_t)(d.h - 1) * (size_t)d.src_pitch + (size_t)d.w;
-            const uintptr_t t0 = (uintptr_t)d.d_dst, t1 = t0 + (size_t)(d.h - 1) * (size_t)d.dst_pitch + (size_t)d.w;
-            OFX_REQUIRE(t1 <= s0 || s1 <= t0, "%s: item %d: d_dst overlaps d_src", who, i);
+            OFX_TRY(check_warp_planes(who, "item", i, d.w, d.h, d.d_src, d.src_pitch, d.d_dst, d.dst_pitch, &P.dwords));
             P.src_pitch = d.src_pitch, P.dst_pitch = d.dst_pitch;
-            P.dwords = (((uintptr_t)d.d_dst | (uintptr_t)d.dst_pitch) & 3) == 0;
         }
         const unsigned b = tiles_across(d.w) * tiles_down(d.h);
         blocks = b > blocks ? b : blocks;

@@ -190,7 +190,7 @@ int ofx_motion_batch_launch(const ofx_motion_batch *a, void *stream)
 {
     const char *who = "ofx_motion_batch_launch";
     OFX_REQUIRE(a, "%s: bad arguments", who);
-    OFX_TRY(check_batch(who, a->n, a->w, a->h, {a->prev_pitch, a->next_pitch}, {a->flow}, a->stats));
+    OFX_TRY(check_batch(who, a->n, a->w, a->h, 1, {a->prev_pitch, a->next_pitch}, {a->flow}, a->stats));
     for (int i = 0; i < a->n; ++i) {
         OFX_REQUIRE(a->prev[i] && a->next[i], "%s: pair %d: null pointer", who, i);
         OFX_REQUIRE(a->dst[i] || a->stats[i], "%s: pair %d has neither an image nor a stats slot", who, i);

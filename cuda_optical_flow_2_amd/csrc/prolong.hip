@@ -9,12 +9,8 @@
 // sanitised as it arrives; the even positions take their tap without arithmetic, the odd ones a + 0.5f * (b - a) -- also where
 // the clamp has made a and b the same tap, as the definition does.
 //
-// The four fine vectors stay in registers: they leave as two 16-byte buffer stores (a row's ragged end: one 8-byte store per
-// pixel, because the bytes behind it are the next row's) and feed the warp -- motion_ring.hip's arithmetic without the shift,
-// warp_row_prepare's operation order -- whose taps go through a buffer resource of exactly the plane's (h - 1) * pitch + w bytes,
-// at positions clamped before they become offsets: the two taps of a tap row are one 16-bit load where the lane has proved
-// xi < w - 1 for its four pixels, else two byte loads, the right one AT column x1 (interp.hip's rule).  A pixel that is not warped
-// has its own position and zero fractions: its own byte.  The warped quad leaves as one dword where it is whole and aligned.
+// The four fine vectors stay in registers: they leave by quad_part_flow_store.h and feed the fused warp, quad_part_warp.h (the
+// rules of both are stated there).  The warped quad leaves as one dword where it is whole and aligned.
 //
 // Traffic: 8 B written and 2 B of coarse field read per fine pixel, 1 B of taps (cache-resident neighbours) and 1 B written: ~12 B.
 #include <string.h>
@@ -109,67 +105,11 @@ __global__ __launch_bounds__(kThreads) void prolong_kernel(const ProlongArgs A)
                 else fv[k] = val;
             }
         }
-        const uint32_t fo = 8u * ((uint32_t)y * (uint32_t)w + (uint32_t)x0);
-        if (npx == 4) {
-            f32x4 lo, hi;
-            lo[0] = fu[0], lo[1] = fv[0], lo[2] = fu[1], lo[3] = fv[1];
-            hi[0] = fu[2], hi[1] = fv[2], hi[2] = fu[3], hi[3] = fv[3];
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(uint32_t)))) uint32_t, lo), rs_f, fo, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(uint32_t)))) uint32_t, hi), rs_f, fo, 16, 0);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                if (k < npx) {
-                    f32x2 p;
-                    p[0] = fu[k], p[1] = fv[k];
-                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(__attribute__((__vector_size__(2 * sizeof(uint32_t)))) uint32_t, p), rs_f, fo + 8u * k, 0, 0);
-                }
-        }
+        // the four fine vectors leave from registers
+#include "quad_part_flow_store.h"
         if (warp) { // (block-uniform)
-            // 4. the warp of the quad by the vectors it holds (warp_row_prepare's operation order)
-            const float xf0 = (float)x0, yf = (float)y;
-            float fx[4], fy[4];
-            uint32_t o0[4], o1[4], dx[4];
-            bool wide = true;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float xr = xf0 + (float)k;
-                const float sxr = xr + scale * fu[k], syr = yf + scale * fv[k];
-                const bool ok = __builtin_fabsf(sxr) <= 1e9f && __builtin_fabsf(syr) <= 1e9f; // (a NaN fails: not warped)
-                const float sx = __builtin_amdgcn_fmed3f(ok ? sxr : xr, 0.0f, wmaxf);
-                const float sy = __builtin_amdgcn_fmed3f(ok ? syr : yf, 0.0f, hmaxf);
-                const int xi = (int)sx, yi = (int)sy;
-                fx[k] = __builtin_amdgcn_fractf(sx); // == sx - (float)xi: sx >= 0, the difference is exact
-                fy[k] = __builtin_amdgcn_fractf(sy);
-                const int y1 = min(yi + 1, hmax);
-                const bool live = k < npx; // (a pixel past the row's end has its clamped column: its taps read as 0, nobody looks)
-                const uint32_t a0 = (uint32_t)yi * (uint32_t)sp + (uint32_t)xi, a1 = (uint32_t)y1 * (uint32_t)sp + (uint32_t)xi;
-                o0[k] = live ? a0 : kNowhere, o1[k] = live ? a1 : kNowhere;
-                dx[k] = xi < wmax ? 1u : 0u;
-                wide = wide && (!live || dx[k]);
-            }
-            uint32_t r0[4], r1[4]; // per pixel (left, right) of the two tap rows in bytes 0 and 1
-            if (wide) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    r0[k] = __builtin_amdgcn_raw_buffer_load_b16(rs_s, o0[k], 0, 0);
-                    r1[k] = __builtin_amdgcn_raw_buffer_load_b16(rs_s, o1[k], 0, 0);
-                }
-            } else {
-                uint32_t l[2][4], r[2][4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    l[0][k] = __builtin_amdgcn_raw_buffer_load_b8(rs_s, o0[k], 0, 0);
-                    r[0][k] = __builtin_amdgcn_raw_buffer_load_b8(rs_s, o0[k] + dx[k], 0, 0);
-                    l[1][k] = __builtin_amdgcn_raw_buffer_load_b8(rs_s, o1[k], 0, 0);
-                    r[1][k] = __builtin_amdgcn_raw_buffer_load_b8(rs_s, o1[k] + dx[k], 0, 0);
-                }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) r0[k] = l[0][k] | (r[0][k] << 8), r1[k] = l[1][k] | (r[1][k] << 8);
-            }
-            uint32_t out = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) out |= round_u8(blend_u8(r0[k], r1[k], fx[k], fy[k])) << (8 * k);
+            // 4. the warp of the quad by the vectors it holds
+#include "quad_part_warp.h"
             store_quad_u8(P.dst + (size_t)y * (size_t)P.dst_pitch + (size_t)x0, out, npx, P.dwords);
         }
         have = have_next, y = y_next, x0 = x0_next;
@@ -205,15 +145,8 @@ extern "C" int ofx_flow_prolong(const ofx_prolong_desc *levels, int n, void *str
         ProlongLevel &P = A.lv[i];
         P = ProlongLevel{d.d_coarse, d.d_fine, d.d_src, d.d_dst, d.wc, d.hc, d.w, d.h, 0, 0, 0, d.scale, d.max_px};
         if (d.d_src) {
-            OFX_REQUIRE(d.src_pitch >= d.w && d.dst_pitch >= d.w, "%s: level %d: a row pitch (src_pitch %d, dst_pitch %d) below the width %d", who, i,
-                        d.src_pitch, d.dst_pitch, d.w);
-            OFX_REQUIRE((size_t)d.h * (size_t)d.src_pitch < ((size_t)1 << 31) && (size_t)d.h * (size_t)d.dst_pitch < ((size_t)1 << 31),
-                        "%s: level %d: a plane of 2^31 bytes or more", who, i);
-            const uintptr_t s0 = (uintptr_t)d.d_src, s1 = s0 + (size_t)(d.h - 1) * (size_t)d.src_pitch + (size_t)d.w;
-            const uintptr_t t0 = (uintptr_t)d.d_dst, t1 = t0 + (size_t)(d.h - 1) * (size_t)d.dst_pitch + (size_t)d.w;
-            OFX_REQUIRE(t1 <= s0 || s1 <= t0, "%s: level %d: d_dst overlaps d_src", who, i);
+            OFX_TRY(check_warp_planes(who, "level", i, d.w, d.h, d.d_src, d.src_pitch, d.d_dst, d.dst_pitch, &P.dwords));
             P.src_pitch = d.src_pitch, P.dst_pitch = d.dst_pitch;
-            P.dwords = (((uintptr_t)d.d_dst | (uintptr_t)d.dst_pitch) & 3) == 0;
         }
         const unsigned b = grid(d.w, d.h, 1).x;
         blocks = b > blocks ? b : blocks;

@@ -25,7 +25,7 @@
 // COMPACTION, one block: a ballot scan over the cells in raster order.
 #include <string.h>
 
-#include "ofx_internal.h"
+#include "quad_stage.h" // (for the buffer resource only: nothing here marches in quads)
 
 namespace {
 
@@ -65,10 +65,7 @@ __host__ __device__ inline unsigned select_groups(int w, int h, int c)
     return (unsigned)((cells_across(w, c) + g - 1) / g) * (unsigned)((cells_across(h, c) + g - 1) / g);
 }
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void *base, int bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, bytes, 0x00027000);
-}
+using quad::rsrc;
 
 // step 2 and 3 of the definition (the build has -ffp-contract=off: nothing below fuses)
 __device__ __forceinline__ float strength_of(int sxx, int syy, int sxy)
