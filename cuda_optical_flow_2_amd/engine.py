@@ -1519,3 +1519,229 @@ def video_klt(frames, points=None, levels: int = 3, window: int = 9, cell: int =
         _track_launch(chain, prm, f0 + 1, cur, status, positions[f0 + 1:f1 + 1], sad[f0:f1], None if stats is None else stats[f0:f1])
         last = chain[-1]
     return (positions, status, sad, stats) if return_stats else (positions, status, sad)
+
+
+# ---- camera motion from point matches -----------------------------------------------------------------------------------------------
+
+MOTION_MODELS = {"translation": 0, "similarity": 1, "affine": 2}      # OFX_MOTION_*
+FIT_OK, FIT_FEW, FIT_DEGENERATE = 0, 1, 2
+
+
+def _fit_params(model, hypotheses, thr, refits, seed):
+    import math
+    from .lib import FitParams
+
+    assert model in MOTION_MODELS, f"model: one of {sorted(MOTION_MODELS)}"
+    return FitParams(MOTION_MODELS[model], int(hypotheses), int(math.floor(float(thr) * 32.0)), int(refits), int(seed) & 0xFFFFFFFF)
+
+
+def _fit_launch(items, prm, models, info, work, inliers=None):
+    """ofx_fit_motion on items (p, q, status or None, n, pair, w, h) of contiguous CUDA tensors; item i writes models[i] (float64
+    [6]), info[i] (int32 [8]) and inliers[i] (uint8 [n], or None) and works in work[i]"""
+    from .lib import FitDesc
+
+    ptr = lambda t: None if t is None else t.data_ptr()
+    descs = (FitDesc * len(items))()
+    for i, (p, q, status, n, pair, w, h) in enumerate(items):
+        assert p.is_contiguous() and q.is_contiguous() and (status is None or status.is_contiguous())
+        descs[i] = FitDesc(p.data_ptr(), q.data_ptr(), ptr(status), int(n), int(pair), int(w), int(h), models[i].data_ptr(), info[i].data_ptr(),
+                           None if inliers is None else ptr(inliers[i]), work[i].data_ptr())
+    check(_lib.load().ofx_fit_motion(descs, len(items), C.byref(prm), _stream_ptr()), "ofx_fit_motion")
+
+
+def _fit_work(prm, n_items, device):
+    import torch
+
+    nbytes = int(_lib.load().ofx_fit_motion_work_bytes(C.byref(prm)))
+    if nbytes == 0:
+        check(1, "ofx_fit_motion_work_bytes")
+    return torch.empty((n_items, nbytes // 8), dtype=torch.float64, device=device)
+
+
+def fit_motion(p, q, size, status=None, pair: int = 0, model: str = "similarity", hypotheses: int = 256, thr: float = 1.0, refits: int = 2,
+               seed: int = 0, return_inliers: bool = False):
+    """The camera motion between two frames from point matches ("camera motion from point matches" in include/ofx.h;
+    ofx_fit_motion): a robust "translation", "similarity" or "affine" model by RANSAC over `hypotheses` samples and `refits`
+    least-squares refits on the inliers.  p, q: float32 [n, 2] of (x, y) in the first and in the second frame, host arrays or CUDA
+    tensors; size: (w, h) of the frames; status: int32 [n] in ofx_track_points' encoding, with which a match counts when it is
+    alive through pair number `pair`; thr: the inlier radius in pixels (in 1/32 px, rounded down).  Returns (model float64 [6] =
+    (a, b, tx, c, d, ty) with q ~ (a x + b y + tx, c x + d y + ty), info int32 [8]) and, with return_inliers, the uint8 [n] mask.
+    Host inputs give arrays, a CUDA tensor p gives CUDA tensors."""
+    import torch
+
+    on_device = isinstance(p, torch.Tensor) and p.is_cuda
+    dev = p.device if on_device else torch.device("cuda")
+    as_dev = lambda t, dt: torch.as_tensor(np.ascontiguousarray(t) if not isinstance(t, torch.Tensor) else t, device=dev).to(dt).contiguous()
+    tp, tq = as_dev(p, torch.float32).reshape(-1, 2), as_dev(q, torch.float32).reshape(-1, 2)
+    n = int(tp.shape[0])
+    assert tq.shape[0] == n, "p and q: the same number of matches"
+    ts = None if status is None else as_dev(status, torch.int32).reshape(-1)
+    assert ts is None or ts.shape[0] == n, "status: one per match"
+    prm = _fit_params(model, hypotheses, thr, refits, seed)
+    models = torch.empty((1, 6), dtype=torch.float64, device=dev)
+    info = torch.empty((1, 8), dtype=torch.int32, device=dev)
+    mask = torch.empty((1, max(n, 1)), dtype=torch.uint8, device=dev) if return_inliers else None
+    _fit_launch([(tp, tq, ts, n, pair, size[0], size[1])], prm, models, info, _fit_work(prm, 1, dev), mask)
+    out = (models[0], info[0]) + ((mask[0, :n],) if return_inliers else ())
+    if on_device:
+        return out
+    torch.cuda.synchronize()
+    return tuple(t.cpu().numpy() for t in out)
+
+
+def motion_compose(m2, m1) -> np.ndarray:
+    """m2 after m1 on float64 [6] models (ofx_motion_compose)"""
+    a, b = np.ascontiguousarray(m2, np.float64).reshape(6), np.ascontiguousarray(m1, np.float64).reshape(6)
+    out = np.empty(6, np.float64)
+    check(_lib.load().ofx_motion_compose(a.ctypes.data, b.ctypes.data, out.ctypes.data), "ofx_motion_compose")
+    return out
+
+
+def motion_invert(m) -> np.ndarray:
+    """the inverse of a float64 [6] model (ofx_motion_invert); a singular or non-finite one is an error"""
+    a = np.ascontiguousarray(m, np.float64).reshape(6)
+    out = np.empty(6, np.float64)
+    check(_lib.load().ofx_motion_invert(a.ctypes.data, out.ctypes.data), "ofx_motion_invert")
+    return out
+
+
+def smooth_path(models, radius: int) -> np.ndarray:
+    """The moving average of a camera path: models float64 [N, 6]; row f of the result is the mean of rows max(f - radius, 0) ..
+    min(f + radius, N - 1), entry by entry, summed in index order and divided once"""
+    m = np.ascontiguousarray(models, np.float64).reshape(-1, 6)
+    N, radius = m.shape[0], int(radius)
+    assert radius >= 0
+    out = np.empty_like(m)
+    for f in range(N):
+        g0, g1 = max(f - radius, 0), min(f + radius, N - 1)
+        for e in range(6):
+            s = np.float64(0.0)
+            for g in range(g0, g1 + 1):
+                s = s + m[g, e]
+            out[f, e] = s / np.float64(g1 - g0 + 1)
+    return out
+
+
+def video_camera_motion(frames, model: str = "similarity", levels: int = 3, window: int = 9, cell: int = 16, reseed: int = 16, hypotheses: int = 256,
+                        thr: float = 1.0, refits: int = 2, seed: int = 0, max_iters: int = 10, eps: float = 1 / 32, min_lambda: float = 0.0,
+                        max_sad: int = 0):
+    """The camera motion of every pair of a grey clip, on the device: frames uint8 CUDA tensor [N, H, W]; pair p (1 .. N - 1) goes
+    from frame p - 1 to frame p.  Per chain of `reseed` pairs (1 .. 16): good_features(window, cell) of the chain's first frame, ONE
+    ofx_track_points launch that keeps every pair's positions, then ONE ofx_fit_motion launch whose items read those rows and the
+    chain's status array in place; nothing returns to the host between the launches beyond what good_features does.  Returns
+    (models float64 [N - 1, 6], info int32 [N - 1, 8]) as CUDA tensors, row p - 1 for pair p; a pair of a chain without a feature
+    gets the identity and status FIT_FEW."""
+    import torch
+
+    N, H, W = _clip_shape(frames)
+    assert frames.dim() == 3, "video_camera_motion: a grey clip [N, H, W]"
+    assert 1 <= reseed <= 16, "reseed: 1 .. 16"
+    dev = frames.device
+    prm, tprm = _fit_params(model, hypotheses, thr, refits, seed), _track_params(window, max_iters, eps, min_lambda, max_sad)
+    models = torch.empty((max(N - 1, 0), 6), dtype=torch.float64, device=dev)
+    info = torch.empty((max(N - 1, 0), 8), dtype=torch.int32, device=dev)
+    work = _fit_work(prm, reseed, dev)
+    last = _KltPyramid(frames[0], levels)
+    for f0 in range(0, N - 1, reseed):
+        f1 = min(f0 + reseed, N - 1)                      # the pairs f0 + 1 .. f1
+        pairs = f1 - f0
+        chain = [last] + [_KltPyramid(frames[f], levels) for f in range(f0 + 1, f1 + 1)]
+        last = chain[-1]
+        seeds, _ = _good_features_device(chain[0].ptrs[0], chain[0].pitches[0], W, H, int(window), int(cell), None, 0.0, None, dev)
+        n = int(seeds.shape[0])
+        if n == 0:
+            models[f0:f1] = torch.tensor([1.0, 0.0, 0.0, 0.0, 1.0, 0.0], dtype=torch.float64, device=dev)
+            info[f0:f1] = torch.tensor([FIT_FEW, 0, 0, -1, 0, 0, 0, 0], dtype=torch.int32, device=dev)
+            continue
+        pos = torch.empty((pairs + 1, n, 2), dtype=torch.float32, device=dev)
+        pos[0] = seeds
+        cur, status = pos[0].clone(), torch.zeros(n, dtype=torch.int32, device=dev)
+        _track_launch(chain, tprm, f0 + 1, cur, status, pos[1:])
+        _fit_launch([(pos[b], pos[b + 1], status, n, f0 + 1 + b, W, H) for b in range(pairs)], prm, models[f0:f1], info[f0:f1], work)
+    return models, info
+
+
+# ---- affine frame warp and the clip stabiliser --------------------------------------------------------------------------------------
+
+BORDERS = {"constant": 0, "replicate": 1}      # OFX_BORDER_*
+
+
+def _warp_affine_launch(items):
+    """ofx_warp_affine on items (src, dst, model, border, fill, outside): src and dst uint8 CUDA tensors [h, w] or [h, w, 3] whose
+    pixels are contiguous (rows any distance apart), model six floats, outside a one-element int64 CUDA tensor or None"""
+    from .lib import WarpAffineDesc
+
+    descs = (WarpAffineDesc * len(items))()
+    for i, (src, dst, model, border, fill, outside) in enumerate(items):
+        ch = 3 if src.dim() == 3 else 1
+        assert dst.dim() == src.dim() and (ch == 1 or (src.shape[2] == 3 and dst.shape[2] == 3 and src.stride(2) == 1 and dst.stride(2) == 1))
+        assert (src.stride(1) == ch or src.shape[1] == 1) and (dst.stride(1) == ch or dst.shape[1] == 1), "pixels must be contiguous"
+        descs[i] = WarpAffineDesc(src.data_ptr(), int(src.stride(0)), int(src.shape[1]), int(src.shape[0]), dst.data_ptr(), int(dst.stride(0)),
+                                  int(dst.shape[1]), int(dst.shape[0]), ch, int(border), int(fill), (C.c_double * 6)(*[float(v) for v in model]),
+                                  None if outside is None else outside.data_ptr())
+    check(_lib.load().ofx_warp_affine(descs, len(items), _stream_ptr()), "ofx_warp_affine")
+
+
+def warp_affine(img, model, out_size=None, border: str = "replicate", fill: int = 0, return_outside: bool = False):
+    """A frame seen through a parametric motion ("affine frame warp" in include/ofx.h; ofx_warp_affine).  img: uint8 [H, W] or
+    [H, W, 3], host array or CUDA tensor; model: float64 [6] = (a, b, tx, c, d, ty), the INVERSE map -- output pixel (x, y) shows the
+    source at (a x + b y + tx, c x + d y + ty); out_size: (w, h) of the result (None: the source's); border: "replicate", or
+    "constant" with `fill` in every channel of a pixel whose source position is out of range.  Positions are on the 1/32 px lattice
+    and the result is the same bits everywhere.  Returns the warped frame and, with return_outside, the number of output pixels out
+    of range.  A host array gives an array, a CUDA tensor a CUDA tensor."""
+    import torch
+
+    assert border in BORDERS, f"border: one of {sorted(BORDERS)}"
+    on_device = isinstance(img, torch.Tensor) and img.is_cuda
+    src = (img if on_device else torch.from_numpy(np.ascontiguousarray(img)).cuda()).contiguous()
+    assert src.dtype == torch.uint8 and (src.dim() == 2 or (src.dim() == 3 and src.shape[2] == 3)), "img: uint8 [H, W] or [H, W, 3]"
+    w, h = (int(src.shape[1]), int(src.shape[0])) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    dst = torch.empty((h, w) + tuple(src.shape[2:]), dtype=torch.uint8, device=src.device)
+    outside = torch.empty(1, dtype=torch.int64, device=src.device) if return_outside else None
+    _warp_affine_launch([(src, dst, np.asarray(model, np.float64).reshape(6), BORDERS[border], fill, outside)])
+    if not on_device:
+        torch.cuda.synchronize()
+        dst = dst.cpu().numpy()
+    return (dst, int(outside.item())) if return_outside else dst
+
+
+def stabilising_maps(models, info, smooth) -> np.ndarray:
+    """The inverse maps W_f, float64 [N, 6], that video_stabilize warps frame f with, from the N - 1 pair models and their info rows
+    (host arrays):  C_0 = I, C_f = M_f after C_{f-1} with M_f the identity where the pair's status is not FIT_OK;  S_f = the mean of
+    C_g over g in [f - smooth, f + smooth] clipped to the clip (smooth_path), or I for smooth None;  W_f = C_f after the inverse of
+    S_f."""
+    models, info = np.asarray(models, np.float64).reshape(-1, 6), np.asarray(info).reshape(-1, 8)
+    ident = np.array([1.0, 0.0, 0.0, 0.0, 1.0, 0.0])
+    path = [ident]
+    for f in range(models.shape[0]):
+        path.append(motion_compose(models[f] if info[f, 0] == FIT_OK else ident, path[-1]))
+    path = np.stack(path)
+    if smooth is None:
+        return path
+    smoothed = smooth_path(path, smooth)
+    return np.stack([motion_compose(path[f], motion_invert(smoothed[f])) for f in range(path.shape[0])])
+
+
+def video_stabilize(frames, model: str = "similarity", smooth: Optional[int] = 15, border: str = "replicate", fill: int = 0, **motion):
+    """A clip with the camera's shake taken out: video_camera_motion (its other arguments in `motion`) on the clip -- for a colour
+    clip [N, H, W, 3] on the integer channel average of its frames --, the camera path C_f composed from the pair models, its moving
+    average S_f over `smooth` frames on either side, and every frame f warped with the inverse map C_f after the inverse of S_f
+    (ofx_warp_affine, up to 16 frames per launch).  smooth None locks the clip to frame 0; smooth 0 returns the clip unchanged.
+    frames: uint8 CUDA tensor [N, H, W] or [N, H, W, 3].  Returns (the stabilised clip, models float64 [N - 1, 6], info int32
+    [N - 1, 8], outside int64 [N]: the pixels of each frame whose source position was out of range) as CUDA tensors."""
+    import torch
+
+    N, H, W = _clip_shape(frames)
+    assert border in BORDERS, f"border: one of {sorted(BORDERS)}"
+    assert smooth is None or smooth >= 0
+    grey = frames if frames.dim() == 3 else _grey_clip(frames)
+    models, info = video_camera_motion(grey, model=model, **motion)
+    outside = torch.zeros(N, dtype=torch.int64, device=frames.device)
+    if smooth == 0:
+        return frames.clone(), models, info, outside
+    maps = stabilising_maps(models.cpu().numpy(), info.cpu().numpy(), smooth)
+    src = frames.contiguous()
+    out = torch.empty_like(src)
+    for f0 in range(0, N, 16):
+        _warp_affine_launch([(src[f], out[f], maps[f], BORDERS[border], fill, outside[f:f + 1]) for f in range(f0, min(f0 + 16, N))])
+    return out, models, info, outside

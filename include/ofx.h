@@ -675,6 +675,128 @@ typedef struct ofx_track_params {
 int ofx_track_points(const ofx_track_clip *clip, const ofx_track_params *prm, int pair0, float *d_points, int32_t *d_status, int n_points,
                      float *d_history, int32_t *d_sad, int64_t *d_stats, void *stream);
 
+/* ---- camera motion from point matches ---------------------------------------------
+ * The trackers hand back per-point displacements, some of them wrong or on moving objects.  This block answers what they were
+ * gathered for: how did the camera move between two frames?  A robust translation / similarity / affine model per pair: RANSAC
+ * (Fischler, Bolles 1981) over a counter-based sampler, integer inlier counts, and a least-squares refit whose sums are exact
+ * integers up to a small float64 solve.  THE definition (tests/fit_motion_ref.py restates it in NumPy):
+ *
+ * INPUTS per item (a pair): n matches, 1 <= n <= 2^20; p[i] and q[i] float32 (x, y), p the position in the first frame, q in the
+ * second; optionally status[i] and a pair number `pair`; the frame size w, h, each in 1 .. 2^16.
+ * PARAMETERS per call: model OFX_MOTION_TRANSLATION (K = 1 sampled match), OFX_MOTION_SIMILARITY (K = 2) or OFX_MOTION_AFFINE
+ * (K = 3); hypotheses H in 1 .. 4096; thr_q in 0 .. 2^15, the inlier radius in 1/32 px; refits in 0 .. 3; seed, a uint32.
+ *
+ * LATTICE  P = (lrintf(ldexpf(px, 5)), lrintf(ldexpf(py, 5))), the tracker's lattice (tracked points sit on it exactly), Q likewise;
+ *          u = P - o, v = Q - o with o = (16 (w - 1), 16 (h - 1)): relative to the frame's centre, so that the refit stays well
+ *          conditioned.  |u| <= 2^20: products are at most 2^40 and sums over 2^20 matches at most 2^60, exact in int64 in any order.
+ * USABLE   match i is usable when all four floats are finite, p and q lie inside [0, w-1] x [0, h-1] and, with a status array,
+ *          status[i] == 0 || (status[i] >> 8) > pair: alive through this pair in ofx_track_points' encoding, so that a chain's
+ *          d_history rows and its single status array can be passed as they are.
+ * SAMPLER  mix(seed, j, k, a) in uint32 arithmetic:
+ *            h = seed ^ j*0x9E3779B1 ^ k*0x85EBCA77 ^ a*0xC2B2AE3D;  h ^= h>>16;  h *= 0x7FEB352D;  h ^= h>>15;  h *= 0x846CA68B;  h ^= h>>16
+ *          and the index i = (uint64(h) * n) >> 32.  Sample k = 0 .. K-1 of hypothesis j: attempts a = 0 .. 7 in order, the first i
+ *          that is usable and differs from the hypothesis's earlier indices; if all eight fail the hypothesis is INVALID.
+ * MODEL of a hypothesis: six float64 (a, b, tx, c, d, ty) that map u to v; every floating operation is float64 and rounded once,
+ *          nothing fused; integer expressions are exact int64 and converted once.
+ *            translation  (1, 0, v0x - u0x, 0, 1, v0y - u0y)
+ *            similarity   dp = u1 - u0, dq = v1 - v0;  den = dpx^2 + dpy^2, INVALID when 0;  sa = (dpx dqx + dpy dqy) / den;
+ *                         sb = (dpx dqy - dpy dqx) / den;  (a, b, c, d) = (sa, -sb, sb, sa)
+ *            affine       d1 = u1 - u0, d2 = u2 - u0, e1 = v1 - v0, e2 = v2 - v0;  det = d1x d2y - d1y d2x, INVALID when 0;
+ *                         a = (e1x d2y - e2x d1y) / det;  b = (e2x d1x - e1x d2x) / det;  c = (e1y d2y - e2y d1y) / det;
+ *                         d = (e2y d1x - e1y d2x) / det
+ *          and for the last two  tx = v0x - (a u0x + b u0y),  ty = v0y - (c u0x + d u0y): two products, one sum, one difference.
+ * SCORE    rx = (a ux + b uy) + (tx - vx), ry likewise;  e2 = rx rx + ry ry;  an INLIER is a usable match with e2 <= (double)thr_q *
+ *          thr_q.  count_j = the inliers, an integer.  The best hypothesis is the valid j with the largest count, among equal
+ *          counts the smallest j: an integer comparison, so any order of reduction gives it.
+ * REFIT    `refits` times: over the inliers of the current model the int64 sums m, Sx = sum ux, Sy, Sxx = sum ux^2, Sxy, Syy, Vx = sum
+ *          vx, Vy, Sxvx = sum ux vx, Syvx, Sxvy, Syvy, each converted to float64 (to nearest even); n = (double)m;
+ *            Cxx = n Sxx - Sx Sx;  Cyy = n Syy - Sy Sy;  Cxy = n Sxy - Sx Sy;  Cxvx = n Sxvx - Sx Vx;  Cyvx, Cxvy, Cyvy likewise;
+ *            translation  t = ((Vx - Sx) / n, (Vy - Sy) / n);  skipped when m == 0
+ *            similarity   den = Cxx + Cyy, skipped when !(den > 0);  sa = (Cxvx + Cyvy) / den;  sb = (Cxvy - Cyvx) / den
+ *            affine       D = Cxx Cyy - Cxy Cxy, skipped when !(D > 0);  a = (Cyy Cxvx - Cxy Cyvx) / D;  b = (Cxx Cyvx - Cxy Cxvx) / D;
+ *                         c, d the same on Cxvy, Cyvy
+ *          and for the last two  tx = (Vx - (a Sx + b Sy)) / n,  ty = (Vy - (c Sx + d Sy)) / n.  A skipped refit keeps the model.
+ * OUTPUTS per item:  d_model float64 [6] in pixels about the image origin: the linear part unchanged, tx_px = ((tx + ox) - (a ox +
+ *          b oy)) / 32, ty_px likewise.  d_info int32 [8]: [0] OFX_FIT_OK, OFX_FIT_FEW (fewer than K usable matches) or
+ *          OFX_FIT_DEGENERATE (no valid hypothesis); [1] usable matches; [2] valid hypotheses; [3] the best j, or -1; [4] its count;
+ *          [5] inliers of the final model; [6] refits that were not skipped; [7] 0.  d_inlier (may be NULL) uint8 [n]: 1 or 0 under
+ *          the final model.  On a status other than OK the model is (1, 0, 0, 0, 1, 0), [3] = -1, [4 .. 6] = 0 and the mask zeros.
+ *
+ * ofx_fit_motion: 1 <= n_items <= OFX_STREAM_MAX_BATCH items that may differ in n, w and h, 5 + refits launches on the stream (the
+ * hypotheses' models into d_work, the H x n scores, the choice, a pass over the matches per refit and one for the mask, the
+ * outputs), nothing returns to the host between them.  d_work: ofx_fit_motion_work_bytes(prm) bytes
+ * per item (host arithmetic; 0 for parameters that would be refused), 8-byte aligned, the caller's, its contents undefined
+ * afterwards; items must not share it.  Refused with OFX_E_INVALID and a message naming the item and the argument, before anything
+ * is enqueued: null pointers (d_status and d_inlier may be NULL), any range above, d_p, d_q, d_model or d_work not 8-byte aligned,
+ * d_info or d_status not 4-byte aligned.
+ *
+ * Host only, in the manner of ofx_generate_gaussian_kernel, on float64 [6] models (a, b, tx, c, d, ty); out may be an input:
+ *   ofx_motion_compose  out = m2 after m1:  a = a2 a1 + b2 c1;  b = a2 b1 + b2 d1;  tx = (a2 tx1 + b2 ty1) + tx2;  c, d, ty likewise
+ *                       with (c2, d2, ty2): products, then sums left to right.
+ *   ofx_motion_invert   det = a d - b c, OFX_E_INVALID when it is 0 or not finite;  ia = d / det;  ib = -b / det;  ic = -c / det;
+ *                       id = a / det;  itx = -(ia tx + ib ty);  ity = -(ic tx + id ty). */
+#define OFX_MOTION_TRANSLATION 0
+#define OFX_MOTION_SIMILARITY 1
+#define OFX_MOTION_AFFINE 2
+#define OFX_FIT_OK 0
+#define OFX_FIT_FEW 1
+#define OFX_FIT_DEGENERATE 2
+typedef struct ofx_fit_desc {
+    const float *d_p, *d_q;  /* [n][2], 8-byte aligned */
+    const int32_t *d_status; /* [n]; NULL = every match alive */
+    int n, pair, w, h;
+    double *d_model;         /* [6] */
+    int32_t *d_info;         /* [8] */
+    uint8_t *d_inlier;       /* [n]; may be NULL */
+    void *d_work;            /* ofx_fit_motion_work_bytes(prm) bytes, 8-byte aligned */
+} ofx_fit_desc;
+typedef struct ofx_fit_params {
+    int model, hypotheses, thr_q, refits;
+    uint32_t seed;
+} ofx_fit_params;
+size_t ofx_fit_motion_work_bytes(const ofx_fit_params *prm);
+int ofx_fit_motion(const ofx_fit_desc *items, int n_items, const ofx_fit_params *prm, void *stream);
+int ofx_motion_compose(const double *m2, const double *m1, double *out);
+int ofx_motion_invert(const double *m, double *out);
+
+/* ---- affine frame warp ------------------------------------------------------------
+ * Every other warp of this library takes a dense 8 B/px field.  This one applies a parametric motion -- a model of the block above,
+ * or any float64 [6] -- to a u8 frame of 1 or 3 interleaved channels: fixed point, on the tracker's 1/32 px lattice, the same bits
+ * everywhere.  THE definition (tests/warp_affine_ref.py restates it in NumPy):
+ *
+ * INPUTS: a destination of w x h pixels and a source of sw x sh pixels, both u8, `channels` C in {1, 3} interleaved; m = (a, b, tx,
+ * c, d, ty) float64, the INVERSE map: output pixel (x, y) shows the source at (a x + b y + tx, c x + d y + ty), in pixels.
+ * QUANTISATION, on the host:  A = llrint(a * 2^21), likewise B, C, D, Tx, Ty; ties to even.  Refused: an entry that is not finite,
+ *   |a|, |b|, |c|, |d| > 16, |tx|, |ty| > 2^20;  w, h, sw, sh in 1 .. 2^16.
+ * POSITION  qx = (A x + B y + Tx + 2^15) >> 16,  qy = (C x + D y + Ty + 2^15) >> 16: int64, arithmetic shift; the source position
+ *   in 1/32 px.  It is IN RANGE when 0 <= qx <= 32 (sw - 1) and 0 <= qy <= 32 (sh - 1).
+ * BORDER    OFX_BORDER_REPLICATE: qx and qy are clamped to the range.  OFX_BORDER_CONSTANT: a pixel out of range gets `fill`
+ *   (0 .. 255) in every channel.
+ * VALUE     (ix, fa) = (qx >> 5, qx & 31), (iy, fb) = (qy >> 5, qy & 31), the tracker's LATTICE; per channel s = (32-fa)(32-fb)
+ *   P(ix, iy) + fa(32-fb) P(ix+1, iy) + (32-fa)fb P(ix, iy+1) + fa fb P(ix+1, iy+1), the tracker's bilinear sum, the taps clamped to
+ *   the plane;  out = (s + 512) >> 10.
+ * d_outside (may be NULL; 8-byte aligned): one int64 per item, the output pixels out of range, under either border mode; the call
+ *   zeroes it on the stream first.
+ * The identity copies the source; a whole-pixel translation gives a shifted copy exactly.
+ *
+ * ofx_warp_affine: 1 <= n <= OFX_STREAM_MAX_BATCH items of any sizes, channels, borders and models in ONE launch.  Any pitch of at
+ * least C w (C sw) and any alignment; d_src and d_dst must not overlap; the bytes of a destination row beyond column C w - 1 stay
+ * untouched; no tap reads outside the (sh - 1) src_pitch + C sw bytes of the source, whatever the model.  Refused with
+ * OFX_E_INVALID and a message naming the item and the argument, before anything is enqueued: null pointers, n, channels, border,
+ * fill, a size or a model entry outside its range, a pitch below its row, planes that overlap, d_outside not 8-byte aligned. */
+#define OFX_BORDER_CONSTANT 0
+#define OFX_BORDER_REPLICATE 1
+typedef struct ofx_warp_affine_desc {
+    const uint8_t *d_src;
+    int src_pitch, sw, sh;
+    uint8_t *d_dst;
+    int dst_pitch, w, h;
+    int channels, border, fill;
+    double model[6];
+    int64_t *d_outside;
+} ofx_warp_affine_desc;
+int ofx_warp_affine(const ofx_warp_affine_desc *items, int n, void *stream);
+
 /* ---- layout helpers ------------------------------------------------------ */
 int ofx_extract_ch0(const uint8_t *d_src3, uint8_t *d_dst1, int w, int h, int dst_pitch, void *stream);
 int ofx_replicate_3ch(const uint8_t *d_src1, int src_pitch, uint8_t *d_dst3, int w, int h, void *stream);
