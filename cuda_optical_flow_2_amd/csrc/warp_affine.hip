@@ -9,10 +9,11 @@
 #include <string.h>
 
 #include "ofx_internal.h"
+#include "warp_pixel.h"
 
 namespace {
 
-constexpr int kThreads = 256, kQuad = 4;
+constexpr int kThreads = 256, kQuad = kWarpQuad;
 constexpr int kMaxSize = 1 << 16;
 constexpr int kShift = 21; // the model's fixed point; a position in 1/32 px is (.. + 2^15) >> 16
 
@@ -32,42 +33,12 @@ template <int C> __device__ __forceinline__ unsigned warp_quad(const WarpItem &i
 {
     const int y = (int)(g / it.quads_per_row), x0 = kQuad * (int)(g - (unsigned)y * it.quads_per_row);
     long long px = it.a * x0 + it.b * y + it.tx + 32768, py = it.c * x0 + it.d * y + it.ty + 32768;
-    const int xmax = 32 * (it.sw - 1), ymax = 32 * (it.sh - 1);
-    const bool constant = it.border == OFX_BORDER_CONSTANT;
-    unsigned out = 0;
-    uint8_t v[kQuad][C];
-#pragma unroll
-    for (int k = 0; k < kQuad; ++k) {
-        const long long qx = px >> 16, qy = py >> 16;
+    auto pos = [&it, px, py](int, long long &qx, long long &qy) mutable {
+        qx = px >> 16, qy = py >> 16;
         px += it.a, py += it.c;
-        const bool in = qx >= 0 && qx <= xmax && qy >= 0 && qy <= ymax;
-        out += (x0 + k < it.w && !in) ? 1u : 0u;
-        const int cx = (int)(qx < 0 ? 0 : qx > xmax ? xmax : qx), cy = (int)(qy < 0 ? 0 : qy > ymax ? ymax : qy); // (clamped: in 0 .. 32 (size - 1))
-        const int ix = cx >> 5, fa = cx & 31, iy = cy >> 5, fb = cy & 31;
-        const int ix1 = ix + 1 < it.sw ? ix + 1 : it.sw - 1, iy1 = iy + 1 < it.sh ? iy + 1 : it.sh - 1;
-        const uint8_t *r0 = it.src + (size_t)iy * (size_t)it.src_pitch, *r1 = it.src + (size_t)iy1 * (size_t)it.src_pitch;
-        const int w00 = (32 - fa) * (32 - fb), w10 = fa * (32 - fb), w01 = (32 - fa) * fb, w11 = fa * fb;
-#pragma unroll
-        for (int ch = 0; ch < C; ++ch) {
-            const int s = w00 * r0[C * ix + ch] + w10 * r0[C * ix1 + ch] + w01 * r1[C * ix + ch] + w11 * r1[C * ix1 + ch];
-            v[k][ch] = (constant && !in) ? (uint8_t)it.fill : (uint8_t)((s + 512) >> 10);
-        }
-    }
-    uint8_t *d = it.dst + (size_t)y * (size_t)it.dst_pitch + (size_t)(C * x0);
-    if (x0 + kQuad <= it.w && ((uintptr_t)d & 3) == 0) {
-        const uint8_t *b = &v[0][0];
-#pragma unroll
-        for (int k = 0; k < C; ++k)
-            reinterpret_cast<uint32_t *>(d)[k] = (uint32_t)b[4 * k] | ((uint32_t)b[4 * k + 1] << 8) | ((uint32_t)b[4 * k + 2] << 16) | ((uint32_t)b[4 * k + 3] << 24);
-    } else {
-#pragma unroll
-        for (int k = 0; k < kQuad; ++k)
-            if (x0 + k < it.w) {
-#pragma unroll
-                for (int ch = 0; ch < C; ++ch) d[C * k + ch] = v[k][ch];
-            }
-    }
-    return out;
+        return true;
+    };
+    return warp_quad_at<C>(it, y, x0, pos);
 }
 
 __global__ __launch_bounds__(kThreads) void warp_affine_kernel(const WarpArgs A)

@@ -1535,7 +1535,7 @@ def _fit_params(model, hypotheses, thr, refits, seed):
     return FitParams(MOTION_MODELS[model], int(hypotheses), int(math.floor(float(thr) * 32.0)), int(refits), int(seed) & 0xFFFFFFFF)
 
 
-def _fit_launch(items, prm, models, info, work, inliers=None):
+def _fit_launch(items, prm, models, info, work, inliers=None, call="ofx_fit_motion"):
     """ofx_fit_motion on items (p, q, status or None, n, pair, w, h) of contiguous CUDA tensors; item i writes models[i] (float64
     [6]), info[i] (int32 [8]) and inliers[i] (uint8 [n], or None) and works in work[i]"""
     from .lib import FitDesc
@@ -1546,16 +1546,39 @@ def _fit_launch(items, prm, models, info, work, inliers=None):
         assert p.is_contiguous() and q.is_contiguous() and (status is None or status.is_contiguous())
         descs[i] = FitDesc(p.data_ptr(), q.data_ptr(), ptr(status), int(n), int(pair), int(w), int(h), models[i].data_ptr(), info[i].data_ptr(),
                            None if inliers is None else ptr(inliers[i]), work[i].data_ptr())
-    check(_lib.load().ofx_fit_motion(descs, len(items), C.byref(prm), _stream_ptr()), "ofx_fit_motion")
+    check(getattr(_lib.load(), call)(descs, len(items), C.byref(prm), _stream_ptr()), call)
 
 
-def _fit_work(prm, n_items, device):
+def _fit_work(prm, n_items, device, call="ofx_fit_motion_work_bytes"):
     import torch
 
-    nbytes = int(_lib.load().ofx_fit_motion_work_bytes(C.byref(prm)))
+    nbytes = int(getattr(_lib.load(), call)(C.byref(prm)))
     if nbytes == 0:
-        check(1, "ofx_fit_motion_work_bytes")
+        check(1, call)
     return torch.empty((n_items, nbytes // 8), dtype=torch.float64, device=device)
+
+
+def _fit_pair(p, q, size, status, pair, prm, n_model, launch, work, return_inliers):
+    """fit_motion and fit_homography behind their parameters: one item, host or device"""
+    import torch
+
+    on_device = isinstance(p, torch.Tensor) and p.is_cuda
+    dev = p.device if on_device else torch.device("cuda")
+    as_dev = lambda t, dt: torch.as_tensor(np.ascontiguousarray(t) if not isinstance(t, torch.Tensor) else t, device=dev).to(dt).contiguous()
+    tp, tq = as_dev(p, torch.float32).reshape(-1, 2), as_dev(q, torch.float32).reshape(-1, 2)
+    n = int(tp.shape[0])
+    assert tq.shape[0] == n, "p and q: the same number of matches"
+    ts = None if status is None else as_dev(status, torch.int32).reshape(-1)
+    assert ts is None or ts.shape[0] == n, "status: one per match"
+    models = torch.empty((1, n_model), dtype=torch.float64, device=dev)
+    info = torch.empty((1, 8), dtype=torch.int32, device=dev)
+    mask = torch.empty((1, max(n, 1)), dtype=torch.uint8, device=dev) if return_inliers else None
+    launch([(tp, tq, ts, n, pair, size[0], size[1])], prm, models, info, work(prm, 1, dev), mask)
+    out = (models[0], info[0]) + ((mask[0, :n],) if return_inliers else ())
+    if on_device:
+        return out
+    torch.cuda.synchronize()
+    return tuple(t.cpu().numpy() for t in out)
 
 
 def fit_motion(p, q, size, status=None, pair: int = 0, model: str = "similarity", hypotheses: int = 256, thr: float = 1.0, refits: int = 2,
@@ -1567,26 +1590,7 @@ def fit_motion(p, q, size, status=None, pair: int = 0, model: str = "similarity"
     alive through pair number `pair`; thr: the inlier radius in pixels (in 1/32 px, rounded down).  Returns (model float64 [6] =
     (a, b, tx, c, d, ty) with q ~ (a x + b y + tx, c x + d y + ty), info int32 [8]) and, with return_inliers, the uint8 [n] mask.
     Host inputs give arrays, a CUDA tensor p gives CUDA tensors."""
-    import torch
-
-    on_device = isinstance(p, torch.Tensor) and p.is_cuda
-    dev = p.device if on_device else torch.device("cuda")
-    as_dev = lambda t, dt: torch.as_tensor(np.ascontiguousarray(t) if not isinstance(t, torch.Tensor) else t, device=dev).to(dt).contiguous()
-    tp, tq = as_dev(p, torch.float32).reshape(-1, 2), as_dev(q, torch.float32).reshape(-1, 2)
-    n = int(tp.shape[0])
-    assert tq.shape[0] == n, "p and q: the same number of matches"
-    ts = None if status is None else as_dev(status, torch.int32).reshape(-1)
-    assert ts is None or ts.shape[0] == n, "status: one per match"
-    prm = _fit_params(model, hypotheses, thr, refits, seed)
-    models = torch.empty((1, 6), dtype=torch.float64, device=dev)
-    info = torch.empty((1, 8), dtype=torch.int32, device=dev)
-    mask = torch.empty((1, max(n, 1)), dtype=torch.uint8, device=dev) if return_inliers else None
-    _fit_launch([(tp, tq, ts, n, pair, size[0], size[1])], prm, models, info, _fit_work(prm, 1, dev), mask)
-    out = (models[0], info[0]) + ((mask[0, :n],) if return_inliers else ())
-    if on_device:
-        return out
-    torch.cuda.synchronize()
-    return tuple(t.cpu().numpy() for t in out)
+    return _fit_pair(p, q, size, status, pair, _fit_params(model, hypotheses, thr, refits, seed), 6, _fit_launch, _fit_work, return_inliers)
 
 
 def motion_compose(m2, m1) -> np.ndarray:
@@ -1602,6 +1606,85 @@ def motion_invert(m) -> np.ndarray:
     a = np.ascontiguousarray(m, np.float64).reshape(6)
     out = np.empty(6, np.float64)
     check(_lib.load().ofx_motion_invert(a.ctypes.data, out.ctypes.data), "ofx_motion_invert")
+    return out
+
+
+# ---- planar homography from point matches --------------------------------------------------------------------------------------------
+
+MOTION_HOMOGRAPHY = 3                                  # OFX_MOTION_HOMOGRAPHY
+CLIP_MOTION_MODELS = dict(MOTION_MODELS, homography=MOTION_HOMOGRAPHY)      # what video_camera_motion and video_stabilize accept
+IDENTITY9 = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0)
+
+
+def _homography_params(hypotheses, thr, refits, seed):
+    import math
+    from .lib import FitParams
+
+    return FitParams(MOTION_HOMOGRAPHY, int(hypotheses), int(math.floor(float(thr) * 32.0)), int(refits), int(seed) & 0xFFFFFFFF)
+
+
+def _homography_launch(items, prm, models, info, work, inliers=None):
+    """ofx_fit_homography on _fit_launch's items; item i writes models[i] (float64 [9])"""
+    _fit_launch(items, prm, models, info, work, inliers, call="ofx_fit_homography")
+
+
+def _homography_work(prm, n_items, device):
+    return _fit_work(prm, n_items, device, call="ofx_fit_homography_work_bytes")
+
+
+def fit_homography(p, q, size, status=None, pair: int = 0, hypotheses: int = 256, thr: float = 1.0, refits: int = 2, seed: int = 0,
+                   return_inliers: bool = False):
+    """The planar homography between two frames from point matches ("planar homography from point matches" in include/ofx.h;
+    ofx_fit_homography): RANSAC over `hypotheses` four-point samples and `refits` least-squares refits on the inliers.  The
+    arguments are fit_motion's.  Returns (model float64 [9], row-major 3 x 3 with entry 8 = 1 and q ~ ((m0 x + m1 y + m2) / W,
+    (m3 x + m4 y + m5) / W), W = m6 x + m7 y + 1, info int32 [8]) and, with return_inliers, the uint8 [n] mask.  Host inputs give
+    arrays, a CUDA tensor p gives CUDA tensors."""
+    return _fit_pair(p, q, size, status, pair, _homography_params(hypotheses, thr, refits, seed), 9, _homography_launch, _homography_work, return_inliers)
+
+
+def _homography_call(name, *models):
+    ins = [np.ascontiguousarray(m, np.float64).reshape(-1) for m in models]
+    out = np.empty(9, np.float64)
+    check(getattr(_lib.load(), name)(*[a.ctypes.data for a in ins], out.ctypes.data), name)
+    return out
+
+
+def homography_compose(m2, m1) -> np.ndarray:
+    """m2 after m1 on float64 [9] models, the 3 x 3 product, not renormalised (ofx_homography_compose)"""
+    return _homography_call("ofx_homography_compose", np.asarray(m2, np.float64).reshape(9), np.asarray(m1, np.float64).reshape(9))
+
+
+def homography_invert(m) -> np.ndarray:
+    """the inverse of a float64 [9] model (ofx_homography_invert); a singular or non-finite one is an error"""
+    return _homography_call("ofx_homography_invert", np.asarray(m, np.float64).reshape(9))
+
+
+def homography_normalize(m) -> np.ndarray:
+    """a float64 [9] model divided by its entry 8 (ofx_homography_normalize); an entry 8 that is 0 or not finite is an error"""
+    return _homography_call("ofx_homography_normalize", np.asarray(m, np.float64).reshape(9))
+
+
+def homography_from_affine(m6) -> np.ndarray:
+    """(a, b, tx, c, d, ty) as the float64 [9] model (a, b, tx, c, d, ty, 0, 0, 1) (ofx_homography_from_affine)"""
+    return _homography_call("ofx_homography_from_affine", np.asarray(m6, np.float64).reshape(6))
+
+
+def smooth_homography_path(models, radius: int) -> np.ndarray:
+    """The moving average of a homography path: models float64 [N, 9]; every row is normalised (homography_normalize), and row f of
+    the result is the mean of the normalised rows max(f - radius, 0) .. min(f + radius, N - 1), entry by entry, summed in index
+    order and divided once"""
+    m = np.ascontiguousarray(models, np.float64).reshape(-1, 9)
+    m = np.stack([homography_normalize(r) for r in m]) if m.shape[0] else m
+    N, radius = m.shape[0], int(radius)
+    assert radius >= 0
+    out = np.empty_like(m)
+    for f in range(N):
+        g0, g1 = max(f - radius, 0), min(f + radius, N - 1)
+        for e in range(9):
+            s = np.float64(0.0)
+            for g in range(g0, g1 + 1):
+                s = s + m[g, e]
+            out[f, e] = s / np.float64(g1 - g0 + 1)
     return out
 
 
@@ -1630,17 +1713,22 @@ def video_camera_motion(frames, model: str = "similarity", levels: int = 3, wind
     ofx_track_points launch that keeps every pair's positions, then ONE ofx_fit_motion launch whose items read those rows and the
     chain's status array in place; nothing returns to the host between the launches beyond what good_features does.  Returns
     (models float64 [N - 1, 6], info int32 [N - 1, 8]) as CUDA tensors, row p - 1 for pair p; a pair of a chain without a feature
-    gets the identity and status FIT_FEW."""
+    gets the identity and status FIT_FEW.  model "homography": the fit is ofx_fit_homography and the models are float64 [N - 1, 9]."""
     import torch
 
     N, H, W = _clip_shape(frames)
     assert frames.dim() == 3, "video_camera_motion: a grey clip [N, H, W]"
     assert 1 <= reseed <= 16, "reseed: 1 .. 16"
     dev = frames.device
-    prm, tprm = _fit_params(model, hypotheses, thr, refits, seed), _track_params(window, max_iters, eps, min_lambda, max_sad)
-    models = torch.empty((max(N - 1, 0), 6), dtype=torch.float64, device=dev)
+    assert model in CLIP_MOTION_MODELS, f"model: one of {sorted(CLIP_MOTION_MODELS)}"
+    homography = model == "homography"
+    tprm = _track_params(window, max_iters, eps, min_lambda, max_sad)
+    prm = _homography_params(hypotheses, thr, refits, seed) if homography else _fit_params(model, hypotheses, thr, refits, seed)
+    ident = IDENTITY9 if homography else (1.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+    launch = _homography_launch if homography else _fit_launch
+    models = torch.empty((max(N - 1, 0), len(ident)), dtype=torch.float64, device=dev)
     info = torch.empty((max(N - 1, 0), 8), dtype=torch.int32, device=dev)
-    work = _fit_work(prm, reseed, dev)
+    work = (_homography_work if homography else _fit_work)(prm, reseed, dev)
     last = _KltPyramid(frames[0], levels)
     for f0 in range(0, N - 1, reseed):
         f1 = min(f0 + reseed, N - 1)                      # the pairs f0 + 1 .. f1
@@ -1650,14 +1738,14 @@ def video_camera_motion(frames, model: str = "similarity", levels: int = 3, wind
         seeds, _ = _good_features_device(chain[0].ptrs[0], chain[0].pitches[0], W, H, int(window), int(cell), None, 0.0, None, dev)
         n = int(seeds.shape[0])
         if n == 0:
-            models[f0:f1] = torch.tensor([1.0, 0.0, 0.0, 0.0, 1.0, 0.0], dtype=torch.float64, device=dev)
+            models[f0:f1] = torch.tensor(ident, dtype=torch.float64, device=dev)
             info[f0:f1] = torch.tensor([FIT_FEW, 0, 0, -1, 0, 0, 0, 0], dtype=torch.int32, device=dev)
             continue
         pos = torch.empty((pairs + 1, n, 2), dtype=torch.float32, device=dev)
         pos[0] = seeds
         cur, status = pos[0].clone(), torch.zeros(n, dtype=torch.int32, device=dev)
         _track_launch(chain, tprm, f0 + 1, cur, status, pos[1:])
-        _fit_launch([(pos[b], pos[b + 1], status, n, f0 + 1 + b, W, H) for b in range(pairs)], prm, models[f0:f1], info[f0:f1], work)
+        launch([(pos[b], pos[b + 1], status, n, f0 + 1 + b, W, H) for b in range(pairs)], prm, models[f0:f1], info[f0:f1], work)
     return models, info
 
 
@@ -1666,29 +1754,29 @@ def video_camera_motion(frames, model: str = "similarity", levels: int = 3, wind
 BORDERS = {"constant": 0, "replicate": 1}      # OFX_BORDER_*
 
 
-def _warp_affine_launch(items):
-    """ofx_warp_affine on items (src, dst, model, border, fill, outside): src and dst uint8 CUDA tensors [h, w] or [h, w, 3] whose
-    pixels are contiguous (rows any distance apart), model six floats, outside a one-element int64 CUDA tensor or None"""
-    from .lib import WarpAffineDesc
+def _warp_launch(items, perspective=False):
+    """ofx_warp_affine (or, perspective, ofx_warp_perspective) on items (src, dst, model, border, fill, outside): src and dst uint8
+    CUDA tensors [h, w] or [h, w, 3] whose pixels are contiguous (rows any distance apart), model six (nine) floats, outside a
+    one-element int64 CUDA tensor or None"""
+    from .lib import WarpAffineDesc, WarpPerspDesc
 
-    descs = (WarpAffineDesc * len(items))()
+    Desc, n_model, name = (WarpPerspDesc, 9, "ofx_warp_perspective") if perspective else (WarpAffineDesc, 6, "ofx_warp_affine")
+    descs = (Desc * len(items))()
     for i, (src, dst, model, border, fill, outside) in enumerate(items):
         ch = 3 if src.dim() == 3 else 1
         assert dst.dim() == src.dim() and (ch == 1 or (src.shape[2] == 3 and dst.shape[2] == 3 and src.stride(2) == 1 and dst.stride(2) == 1))
         assert (src.stride(1) == ch or src.shape[1] == 1) and (dst.stride(1) == ch or dst.shape[1] == 1), "pixels must be contiguous"
-        descs[i] = WarpAffineDesc(src.data_ptr(), int(src.stride(0)), int(src.shape[1]), int(src.shape[0]), dst.data_ptr(), int(dst.stride(0)),
-                                  int(dst.shape[1]), int(dst.shape[0]), ch, int(border), int(fill), (C.c_double * 6)(*[float(v) for v in model]),
-                                  None if outside is None else outside.data_ptr())
-    check(_lib.load().ofx_warp_affine(descs, len(items), _stream_ptr()), "ofx_warp_affine")
+        descs[i] = Desc(src.data_ptr(), int(src.stride(0)), int(src.shape[1]), int(src.shape[0]), dst.data_ptr(), int(dst.stride(0)),
+                        int(dst.shape[1]), int(dst.shape[0]), ch, int(border), int(fill), (C.c_double * n_model)(*[float(v) for v in model]),
+                        None if outside is None else outside.data_ptr())
+    check(getattr(_lib.load(), name)(descs, len(items), _stream_ptr()), name)
 
 
-def warp_affine(img, model, out_size=None, border: str = "replicate", fill: int = 0, return_outside: bool = False):
-    """A frame seen through a parametric motion ("affine frame warp" in include/ofx.h; ofx_warp_affine).  img: uint8 [H, W] or
-    [H, W, 3], host array or CUDA tensor; model: float64 [6] = (a, b, tx, c, d, ty), the INVERSE map -- output pixel (x, y) shows the
-    source at (a x + b y + tx, c x + d y + ty); out_size: (w, h) of the result (None: the source's); border: "replicate", or
-    "constant" with `fill` in every channel of a pixel whose source position is out of range.  Positions are on the 1/32 px lattice
-    and the result is the same bits everywhere.  Returns the warped frame and, with return_outside, the number of output pixels out
-    of range.  A host array gives an array, a CUDA tensor a CUDA tensor."""
+def _warp_affine_launch(items):
+    _warp_launch(items)
+
+
+def _warp_frame(img, model, n_model, out_size, border, fill, return_outside):
     import torch
 
     assert border in BORDERS, f"border: one of {sorted(BORDERS)}"
@@ -1698,11 +1786,29 @@ def warp_affine(img, model, out_size=None, border: str = "replicate", fill: int 
     w, h = (int(src.shape[1]), int(src.shape[0])) if out_size is None else (int(out_size[0]), int(out_size[1]))
     dst = torch.empty((h, w) + tuple(src.shape[2:]), dtype=torch.uint8, device=src.device)
     outside = torch.empty(1, dtype=torch.int64, device=src.device) if return_outside else None
-    _warp_affine_launch([(src, dst, np.asarray(model, np.float64).reshape(6), BORDERS[border], fill, outside)])
+    _warp_launch([(src, dst, np.asarray(model, np.float64).reshape(n_model), BORDERS[border], fill, outside)], perspective=n_model == 9)
     if not on_device:
         torch.cuda.synchronize()
         dst = dst.cpu().numpy()
     return (dst, int(outside.item())) if return_outside else dst
+
+
+def warp_affine(img, model, out_size=None, border: str = "replicate", fill: int = 0, return_outside: bool = False):
+    """A frame seen through a parametric motion ("affine frame warp" in include/ofx.h; ofx_warp_affine).  img: uint8 [H, W] or
+    [H, W, 3], host array or CUDA tensor; model: float64 [6] = (a, b, tx, c, d, ty), the INVERSE map -- output pixel (x, y) shows the
+    source at (a x + b y + tx, c x + d y + ty); out_size: (w, h) of the result (None: the source's); border: "replicate", or
+    "constant" with `fill` in every channel of a pixel whose source position is out of range.  Positions are on the 1/32 px lattice
+    and the result is the same bits everywhere.  Returns the warped frame and, with return_outside, the number of output pixels out
+    of range.  A host array gives an array, a CUDA tensor a CUDA tensor."""
+    return _warp_frame(img, model, 6, out_size, border, fill, return_outside)
+
+
+def warp_perspective(img, model9, out_size=None, border: str = "replicate", fill: int = 0, return_outside: bool = False):
+    """A frame seen through a planar homography ("perspective frame warp" in include/ofx.h; ofx_warp_perspective).  The arguments
+    and the result are warp_affine's, with model9 float64 [9], row-major 3 x 3, the INVERSE map -- output pixel (x, y) shows the
+    source at ((m0 x + m1 y + m2) / W, (m3 x + m4 y + m5) / W), W = m6 x + m7 y + m8.  A pixel with W <= 0 or a position beyond
+    2^35 px gets `fill` under either border mode and counts as outside."""
+    return _warp_frame(img, model9, 9, out_size, border, fill, return_outside)
 
 
 def stabilising_maps(models, info, smooth) -> np.ndarray:
@@ -1710,7 +1816,10 @@ def stabilising_maps(models, info, smooth) -> np.ndarray:
     (host arrays):  C_0 = I, C_f = M_f after C_{f-1} with M_f the identity where the pair's status is not FIT_OK;  S_f = the mean of
     C_g over g in [f - smooth, f + smooth] clipped to the clip (smooth_path), or I for smooth None;  W_f = C_f after the inverse of
     S_f."""
-    models, info = np.asarray(models, np.float64).reshape(-1, 6), np.asarray(info).reshape(-1, 8)
+    models, info = np.asarray(models, np.float64), np.asarray(info).reshape(-1, 8)
+    if models.ndim == 2 and models.shape[1] == 9:
+        return _stabilising_homographies(models, info, smooth)
+    models = models.reshape(-1, 6)
     ident = np.array([1.0, 0.0, 0.0, 0.0, 1.0, 0.0])
     path = [ident]
     for f in range(models.shape[0]):
@@ -1722,13 +1831,29 @@ def stabilising_maps(models, info, smooth) -> np.ndarray:
     return np.stack([motion_compose(path[f], motion_invert(smoothed[f])) for f in range(path.shape[0])])
 
 
+def _stabilising_homographies(models, info, smooth) -> np.ndarray:
+    """stabilising_maps for float64 [N - 1, 9] pair models, float64 [N, 9]:  C_0 = I, C_f = normalize(M_f after C_{f-1});  S_f from
+    smooth_homography_path;  W_f = normalize(C_f after the inverse of S_f)"""
+    ident = np.array(IDENTITY9)
+    path = [ident]
+    for f in range(models.shape[0]):
+        path.append(homography_normalize(homography_compose(models[f] if info[f, 0] == FIT_OK else ident, path[-1])))
+    path = np.stack(path)
+    if smooth is None:
+        return path
+    smoothed = smooth_homography_path(path, smooth)
+    return np.stack([homography_normalize(homography_compose(path[f], homography_invert(smoothed[f]))) for f in range(path.shape[0])])
+
+
 def video_stabilize(frames, model: str = "similarity", smooth: Optional[int] = 15, border: str = "replicate", fill: int = 0, **motion):
     """A clip with the camera's shake taken out: video_camera_motion (its other arguments in `motion`) on the clip -- for a colour
     clip [N, H, W, 3] on the integer channel average of its frames --, the camera path C_f composed from the pair models, its moving
     average S_f over `smooth` frames on either side, and every frame f warped with the inverse map C_f after the inverse of S_f
     (ofx_warp_affine, up to 16 frames per launch).  smooth None locks the clip to frame 0; smooth 0 returns the clip unchanged.
-    frames: uint8 CUDA tensor [N, H, W] or [N, H, W, 3].  Returns (the stabilised clip, models float64 [N - 1, 6], info int32
-    [N - 1, 8], outside int64 [N]: the pixels of each frame whose source position was out of range) as CUDA tensors."""
+    model "homography": the pair models are float64 [9], the path is composed, normalised and smoothed entry by entry
+    (smooth_homography_path) and the frames go through ofx_warp_perspective.
+    frames: uint8 CUDA tensor [N, H, W] or [N, H, W, 3].  Returns (the stabilised clip, models float64 [N - 1, 6] (or [N - 1, 9]), info
+    int32 [N - 1, 8], outside int64 [N]: the pixels of each frame whose source position was out of range) as CUDA tensors."""
     import torch
 
     N, H, W = _clip_shape(frames)
@@ -1743,5 +1868,6 @@ def video_stabilize(frames, model: str = "similarity", smooth: Optional[int] = 1
     src = frames.contiguous()
     out = torch.empty_like(src)
     for f0 in range(0, N, 16):
-        _warp_affine_launch([(src[f], out[f], maps[f], BORDERS[border], fill, outside[f:f + 1]) for f in range(f0, min(f0 + 16, N))])
+        _warp_launch([(src[f], out[f], maps[f], BORDERS[border], fill, outside[f:f + 1]) for f in range(f0, min(f0 + 16, N))],
+                     perspective=maps.shape[1] == 9)
     return out, models, info, outside

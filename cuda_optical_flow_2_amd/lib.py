@@ -73,7 +73,7 @@ class TrackParams(C.Structure):
 
 
 class FitDesc(C.Structure):
-    """ofx_fit_desc (include/ofx.h, "camera motion from point matches")"""
+    """ofx_fit_desc (include/ofx.h, "camera motion from point matches"; d_model is float64 [9] for ofx_fit_homography)"""
     _fields_ = [("d_p", C.c_void_p), ("d_q", C.c_void_p), ("d_status", C.c_void_p), ("n", C.c_int), ("pair", C.c_int), ("w", C.c_int),
                 ("h", C.c_int), ("d_model", C.c_void_p), ("d_info", C.c_void_p), ("d_inlier", C.c_void_p), ("d_work", C.c_void_p)]
 
@@ -87,6 +87,13 @@ class WarpAffineDesc(C.Structure):
     """ofx_warp_affine_desc (include/ofx.h, "affine frame warp")"""
     _fields_ = [("d_src", C.c_void_p), ("src_pitch", C.c_int), ("sw", C.c_int), ("sh", C.c_int), ("d_dst", C.c_void_p), ("dst_pitch", C.c_int),
                 ("w", C.c_int), ("h", C.c_int), ("channels", C.c_int), ("border", C.c_int), ("fill", C.c_int), ("model", C.c_double * 6),
+                ("d_outside", C.c_void_p)]
+
+
+class WarpPerspDesc(C.Structure):
+    """ofx_warp_persp_desc (include/ofx.h, "perspective frame warp")"""
+    _fields_ = [("d_src", C.c_void_p), ("src_pitch", C.c_int), ("sw", C.c_int), ("sh", C.c_int), ("d_dst", C.c_void_p), ("dst_pitch", C.c_int),
+                ("w", C.c_int), ("h", C.c_int), ("channels", C.c_int), ("border", C.c_int), ("fill", C.c_int), ("model", C.c_double * 9),
                 ("d_outside", C.c_void_p)]
 
 
@@ -194,9 +201,16 @@ _SIGS = {
     "ofx_track_points": [C.POINTER(TrackClip), C.POINTER(TrackParams), _i, _vp, _vp, _i, _vp, _vp, _vp, _vp],
     "ofx_fit_motion_work_bytes": [C.POINTER(FitParams)],
     "ofx_fit_motion": [C.POINTER(FitDesc), _i, C.POINTER(FitParams), _vp],
+    "ofx_fit_homography_work_bytes": [C.POINTER(FitParams)],
+    "ofx_fit_homography": [C.POINTER(FitDesc), _i, C.POINTER(FitParams), _vp],
     "ofx_motion_compose": [_vp, _vp, _vp],
     "ofx_motion_invert": [_vp, _vp],
     "ofx_warp_affine": [C.POINTER(WarpAffineDesc), _i, _vp],
+    "ofx_warp_perspective": [C.POINTER(WarpPerspDesc), _i, _vp],
+    "ofx_homography_compose": [_vp, _vp, _vp],
+    "ofx_homography_invert": [_vp, _vp],
+    "ofx_homography_normalize": [_vp, _vp],
+    "ofx_homography_from_affine": [_vp, _vp],
     "ofx_interpolate_frames": [_vp, _i, _vp, _i, _i, _i, _vp, _vp, C.POINTER(C.c_float), _i, _vp, _i, C.c_size_t, _vp, _vp],
     "ofx_interpolate_frames_batch": [C.POINTER(_vp), C.POINTER(_i), C.POINTER(_vp), C.POINTER(_i), _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp),
                                      C.POINTER(C.c_float), _i, C.POINTER(_vp), _i, C.c_size_t, C.POINTER(_vp), _vp],
@@ -225,7 +239,7 @@ _SIGS = {
     "ofx_compose_flow_host": [C.POINTER(_vp), _i, _i, _i, _i, _vp],
     "ofx_calc_opt_flow_host": [_vp, _vp, _i, _i, C.POINTER(_vp), _i, _i, _i, _i],
 }
-_RESTYPE = {"ofx_generate_gaussian_kernel": None, "ofx_fit_motion_work_bytes": C.c_size_t}
+_RESTYPE = {"ofx_generate_gaussian_kernel": None, "ofx_fit_motion_work_bytes": C.c_size_t, "ofx_fit_homography_work_bytes": C.c_size_t}
 
 EXPORTS = sorted(list(_SIGS) + ["ofx_last_error"])
 

@@ -759,6 +759,68 @@ int ofx_fit_motion(const ofx_fit_desc *items, int n_items, const ofx_fit_params 
 int ofx_motion_compose(const double *m2, const double *m1, double *out);
 int ofx_motion_invert(const double *m, double *out);
 
+/* ---- planar homography from point matches -----------------------------------------
+ * The block above stops at six parameters, exact only for a camera that does not rotate out of the image plane.  A camera that
+ * pans or tilts in front of a plane or a distant scene moves the image by a planar homography: the fourth model, fitted the same
+ * way -- RANSAC over the same sampler, integer inlier counts, a least-squares refit on exact integer sums -- with an 8 x 8 solve, a
+ * division-free rational residual and 128-bit sums.  THE definition (tests/homography_ref.py restates it in NumPy and Python ints):
+ *
+ * INPUTS, PARAMETERS, LATTICE, USABLE, SAMPLER: those of "camera motion from point matches", with model = OFX_MOTION_HOMOGRAPHY and
+ *          K = 4 samples per hypothesis.  Every floating operation below is float64 and rounded once, nothing fused; every integer
+ *          expression is exact.
+ * SCALE    e = the smallest integer >= 0 with 2^e >= max(16 (w - 1), 16 (h - 1), 1).  A lattice value u becomes the normalised
+ *          x = ldexp((double)u, -e): exact, |x| <= 1.  Below (x, y) is the normalised u of a match and (X, Y) its normalised v.
+ * SOLVE    of an 8 x 9 augmented system M (8 equations, the right-hand side in column 8), Gaussian elimination with partial pivoting:
+ *          for c = 0 .. 7:  the pivot row p starts as c, and each r = c + 1 .. 7 in order replaces it when |M[r][c]| > |M[p][c]|
+ *          (the largest magnitude, the smallest row among equals);  INVALID when M[p][c] is 0 or not finite;  rows p and c are
+ *          swapped;  for each r = c + 1 .. 7:  f = M[r][c] / M[c][c], then for k = c + 1 .. 8:  M[r][k] = M[r][k] - f M[c][k].
+ *          Back substitution for c = 7 .. 0:  s = M[c][8], then for k = c + 1 .. 7 in order  s = s - M[c][k] h[k];  h[c] = s / M[c][c].
+ *          INVALID when any h[c] is not finite.
+ * MODEL of a hypothesis: (h0 .. h7, 1), row-major 3 x 3, maps normalised u to normalised v.  From its four samples in order, k = 0 .. 3:
+ *            row 2k     = [x  y  1  0  0  0  -(x X)  -(y X) | X]
+ *            row 2k + 1 = [0  0  0  x  y  1  -(x Y)  -(y Y) | Y]
+ *          then SOLVE.  The hypothesis is INVALID when the sampler or the solve says so, or when (h6 x + h7 y) + 1 is not > 0 at any
+ *          of its four samples.
+ * SCORE    W = (h6 x + h7 y) + 1;  rx = ((h0 x + h1 y) + h2) - X W;  ry = ((h3 x + h4 y) + h5) - Y W;  t = ldexp((double)thr_q, -e).
+ *          An INLIER is a usable match with W > 0 and rx rx + ry ry <= (t W) (t W): the transfer error against the radius, without
+ *          a division.  count_j = the inliers, an integer; the best hypothesis is the valid j with the largest count, among equal
+ *          counts the smallest j.
+ * REFIT    `refits` times, over the inliers of the current model: the normal equations of min sum (h0 x + h1 y + h2 - X (h6 x + h7 y
+ *          + 1))^2 + (h3 x + h4 y + h5 - Y (h6 x + h7 y + 1))^2.  In the lattice integers (ux, uy) -> (x, y), (vx, vy) -> (X, Y), with
+ *          R = X X + Y Y, the 23 exact sums
+ *            degree 0  m (the count)                      degree 1  Sx, Sy, SX, SY
+ *            degree 2  Sxx, Sxy, Syy, SxX, SyX, SxY, SyY    degree 3  SxxX, SxyX, SyyX, SxxY, SxyY, SyyY, SxR, SyR
+ *            degree 4  SxxR, SxyR, SyyR
+ *          (SxyX = sum ux uy vx, SxR = sum ux (vx vx + vy vy), ...).  Those of degree 3 and 4 reach 2^101 in magnitude: 128-bit
+ *          two's-complement integers, exact in any order.  Each sum of degree d is converted to float64 ONCE, to nearest even,
+ *          then scaled by ldexp(., -d e) (exact).  The system, in the scaled sums (a minus sign is exact):
+ *            row 0 = [ Sxx    Sxy    Sx    0      0      0     -SxxX  -SxyX |  SxX ]
+ *            row 1 = [ Sxy    Syy    Sy    0      0      0     -SxyX  -SyyX |  SyX ]
+ *            row 2 = [ Sx     Sy     m     0      0      0     -SxX   -SyX  |  SX  ]
+ *            row 3 = [ 0      0      0     Sxx    Sxy    Sx    -SxxY  -SxyY |  SxY ]
+ *            row 4 = [ 0      0      0     Sxy    Syy    Sy    -SxyY  -SyyY |  SyY ]
+ *            row 5 = [ 0      0      0     Sx     Sy     m     -SxY   -SyY  |  SY  ]
+ *            row 6 = [-SxxX  -SxyX  -SxX  -SxxY  -SxyY  -SxY    SxxR   SxyR | -SxR ]
+ *            row 7 = [-SxyX  -SyyX  -SyX  -SxyY  -SyyY  -SyY    SxyR   SyyR | -SyR ]
+ *          then SOLVE.  The refit is skipped, and the model kept, when m < 4 or the solve is INVALID.
+ * OUTPUTS  d_model float64 [9], row-major, in pixels about the image origin (q ~ ((g0 px + g1 py + g2) / W, (g3 px + g4 py + g5) / W),
+ *          W = g6 px + g7 py + 1): the final (h0 .. h7, h8 = 1) conjugated with the map pixels -> normalised, x = s px - cx.  With
+ *          s = ldexp(1.0, 5 - e), cx = ldexp((double)(16 (w - 1)), -e), cy = ldexp((double)(16 (h - 1)), -e), for each row i = 0, 1, 2:
+ *            A[i][0] = h[3i] s;  A[i][1] = h[3i+1] s;  A[i][2] = h[3i+2] - (h[3i] cx + h[3i+1] cy)
+ *          and for each column j:  B[0][j] = A[0][j] + cx A[2][j];  B[1][j] = A[1][j] + cy A[2][j];  B[2][j] = s A[2][j];
+ *          g[3i+j] = B[i][j] / B[2][2].  When B[2][2] is 0 or not finite the item ends OFX_FIT_DEGENERATE.
+ *          d_info and d_inlier as in "camera motion from point matches" (OFX_FIT_FEW: fewer than 4 usable matches); on a status
+ *          other than OK the model is the identity (1, 0, 0, 0, 1, 0, 0, 0, 1), [3] = -1, [4 .. 6] = 0 and the mask zeros.
+ *
+ * ofx_fit_homography: ofx_fit_motion's descriptors (d_model float64 [9] here), parameters (model must be OFX_MOTION_HOMOGRAPHY),
+ * ranges, alignments and refusals; 1 <= n_items <= OFX_STREAM_MAX_BATCH items that may differ in n, w and h; 5 + 2 refits launches
+ * on the stream (hypotheses, scores, the choice, per refit the sums and a one-block solve, the mask, the outputs), nothing returns
+ * to the host between them.  d_work: ofx_fit_homography_work_bytes(prm) bytes per item (0 for parameters that would be refused),
+ * 8-byte aligned, the caller's, undefined afterwards; items must not share it. */
+#define OFX_MOTION_HOMOGRAPHY 3
+size_t ofx_fit_homography_work_bytes(const ofx_fit_params *prm);
+int ofx_fit_homography(const ofx_fit_desc *items, int n_items, const ofx_fit_params *prm, void *stream);
+
 /* ---- affine frame warp ------------------------------------------------------------
  * Every other warp of this library takes a dense 8 B/px field.  This one applies a parametric motion -- a model of the block above,
  * or any float64 [6] -- to a u8 frame of 1 or 3 interleaved channels: fixed point, on the tracker's 1/32 px lattice, the same bits
@@ -796,6 +858,53 @@ typedef struct ofx_warp_affine_desc {
     int64_t *d_outside;
 } ofx_warp_affine_desc;
 int ofx_warp_affine(const ofx_warp_affine_desc *items, int n, void *stream);
+
+/* ---- perspective frame warp -------------------------------------------------------
+ * A camera that pans or tilts in front of a plane or a distant scene moves the image by a planar homography, which no six
+ * parameters hold.  This block applies one: ofx_warp_affine with a float64 [9] model and a division per pixel.  THE definition
+ * (tests/warp_persp_ref.py restates it in NumPy):
+ *
+ * INPUTS: those of "affine frame warp", with m = (m0 .. m8) float64, the INVERSE map, row-major 3 x 3: output pixel (x, y) shows the
+ *   source at ((m0 x + m1 y + m2) / (m6 x + m7 y + m8), (m3 x + m4 y + m5) / (m6 x + m7 y + m8)), in pixels.  The model is used
+ *   as it is, not quantised.  Refused: an entry that is not finite, |m0|, |m1|, |m3|, |m4| > 16, |m2|, |m5| > 2^20, |m6|, |m7| > 1,
+ *   |m8| > 16;  w, h, sw, sh in 1 .. 2^16.
+ * POSITION for integer output (x, y), every operation float64 and rounded once, nothing fused, x and y converted exactly:
+ *   X = (m0 x + m1 y) + m2;  Y = (m3 x + m4 y) + m5;  W = (m6 x + m7 y) + m8;  r = 1.0 / W;  fx = ldexp(X r, 5);  fy = ldexp(Y r, 5).
+ *   Every pixel from its own x and y: nothing is accumulated along a row.
+ * UNDEFINED when W is not > 0 (behind the horizon, on it, or NaN), or fx or fy is not finite or exceeds 2^40 in magnitude.  An
+ *   undefined pixel gets `fill` in every channel under EITHER border mode and counts in d_outside.
+ * Otherwise qx = llrint(fx), qy = llrint(fy), ties to even: the source position in 1/32 px, and the pixel follows IN RANGE, BORDER
+ *   and VALUE of "affine frame warp" from there on; d_outside counts the pixels undefined or out of range.
+ * The identity (1, 0, 0, 0, 1, 0, 0, 0, 1) copies the source; a whole-pixel translation gives a shifted copy exactly; a model
+ * whose bottom row is (0, 0, 1) and whose other entries are multiples of 1/32 gives ofx_warp_affine's bytes for (m0 .. m5), because
+ * nothing rounds in either.
+ *
+ * ofx_warp_perspective: 1 <= n <= OFX_STREAM_MAX_BATCH items of any sizes, channels, borders and models in ONE launch.  Pitches,
+ * alignment, the no-overlap rule, the untouched tail of a destination row, "no tap reads outside the source", d_outside and the
+ * refusals are ofx_warp_affine's.
+ *
+ * Host only, on float64 [9] row-major models; out may be an input:
+ *   ofx_homography_compose      out = m2 after m1, the 3 x 3 product:  out[3i+j] = (m2[3i] m1[j] + m2[3i+1] m1[3+j]) + m2[3i+2] m1[6+j]:
+ *                               products, then sums left to right; NOT renormalised.
+ *   ofx_homography_invert       c0 = m4 m8 - m5 m7;  c1 = m5 m6 - m3 m8;  c2 = m3 m7 - m4 m6;  det = (m0 c0 + m1 c1) + m2 c2,
+ *                               OFX_E_INVALID when it is 0 or not finite;  out = the adjugate (c0, m2 m7 - m1 m8, m1 m5 - m2 m4;
+ *                               c1, m0 m8 - m2 m6, m2 m3 - m0 m5;  c2, m1 m6 - m0 m7, m0 m4 - m1 m3), each entry divided by det.
+ *   ofx_homography_normalize    out[k] = m[k] / m[8];  OFX_E_INVALID when m[8] is 0 or not finite.
+ *   ofx_homography_from_affine  (a, b, tx, c, d, ty) -> (a, b, tx, c, d, ty, 0, 0, 1). */
+typedef struct ofx_warp_persp_desc {
+    const uint8_t *d_src;
+    int src_pitch, sw, sh;
+    uint8_t *d_dst;
+    int dst_pitch, w, h;
+    int channels, border, fill;
+    double model[9];
+    int64_t *d_outside;
+} ofx_warp_persp_desc;
+int ofx_warp_perspective(const ofx_warp_persp_desc *items, int n, void *stream);
+int ofx_homography_compose(const double *m2, const double *m1, double *out);
+int ofx_homography_invert(const double *m, double *out);
+int ofx_homography_normalize(const double *m, double *out);
+int ofx_homography_from_affine(const double *m6, double *out);
 
 /* ---- layout helpers ------------------------------------------------------ */
 int ofx_extract_ch0(const uint8_t *d_src3, uint8_t *d_dst1, int w, int h, int dst_pitch, void *stream);
