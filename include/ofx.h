@@ -312,7 +312,8 @@ int ofx_warp_levels(const ofx_warp_desc *levels, int n, void *stream);
  * ofx_motion_compensate: one level, stateless, one launch with the shift fused (no shifted plane is written).  Pitches >= w;
  * d_flow and d_stats 8-byte aligned; otherwise OFX_E_INVALID.  d_dst (rows dst_pitch apart; bytes beyond column w - 1 are
  * left untouched) or d_stats (4 values, overwritten) may be NULL on its own.  No tap reads outside the h x pitch bytes of
- * d_prev / d_next, whatever the flow holds. */
+ * d_prev / d_next, whatever the flow holds.  d_stats needs no initialisation (the call zeroes it on the stream first) and carries
+ * nothing from one call to the next. */
 int ofx_motion_compensate(const uint8_t *d_prev, int prev_pitch, const uint8_t *d_next, int next_pitch, int w, int h,
                           const float *d_flow, const float *d_uv /* NULL = no shift */, float scale,
                           uint8_t *d_dst /* may be NULL */, int dst_pitch, int64_t *d_stats /* may be NULL; 4 values, overwritten */,
@@ -374,7 +375,8 @@ int ofx_advect_points(const float *const *d_flow_levels, int w, int h, int level
  * ONE launch; an output array may be NULL (that output is then off for all pairs), the entries of a non-NULL array must be
  * non-NULL, at least one output array is required; the host arrays are read before the call returns.  w*h < 2^28; fwd and bwd
  * 8-byte, err 4-byte, stats 8-byte aligned; mask_pitch >= w; scale, alpha and beta as above; otherwise OFX_E_INVALID, before
- * anything is enqueued.  No tap reads outside the w*h*8 bytes of a field, whatever the fields hold. */
+ * anything is enqueued.  No tap reads outside the w*h*8 bytes of a field, whatever the fields hold.  A stats slot needs no
+ * initialisation (the call zeroes it on the stream first) and carries nothing from one call to the next. */
 #define OFX_FB_CONSISTENT 0
 #define OFX_FB_INCONSISTENT 1
 #define OFX_FB_LEAVES 2
@@ -437,7 +439,8 @@ int ofx_flow_displacement(const float *d_flow, int w, int h, const float *d_uv /
  * Null inputs, w, h <= 0 or w*h >= 2^28, a pitch below w, fields or stats not 8-byte aligned, n_times outside
  * 1 .. OFX_INTERP_MAX_TIMES, a time that is not finite or not in (0, 1), time_stride_bytes < h*dst_pitch when n_times > 1, a
  * NULL entry in a non-NULL array, n outside 1 .. OFX_STREAM_MAX_BATCH: OFX_E_INVALID, before anything is enqueued.  The host
- * arrays are read before the call returns. */
+ * arrays are read before the call returns.  The stats slots need no initialisation (the call zeroes them on the stream first) and
+ * carry nothing from one call to the next. */
 #define OFX_INTERP_MAX_TIMES 8
 int ofx_interpolate_frames(const uint8_t *d_a, int a_pitch, const uint8_t *d_b, int b_pitch, int w, int h,
                            const float *d_disp_ab, const float *d_disp_ba, const float *h_times, int n_times,
@@ -460,7 +463,8 @@ int ofx_interpolate_frames_batch(const uint8_t *const *d_a, const int *a_pitches
  *
  * ofx_interpolate_frames_3ch / ofx_interpolate_frames_3ch_batch: as ofx_interpolate_frames / ofx_interpolate_frames_batch, frame k
  * at d_dst3 + k*time_stride_bytes, rows dst_pitch >= 3*w apart.  The refusals are theirs, every pitch compared against 3*w, and a
- * plane of 2^31 bytes or more: OFX_E_INVALID, before anything is enqueued.  The host arrays are read before the call returns. */
+ * plane of 2^31 bytes or more: OFX_E_INVALID, before anything is enqueued.  The host arrays are read before the call returns; the
+ * stats slots need no initialisation and carry nothing from one call to the next, as there. */
 int ofx_interpolate_frames_3ch(const uint8_t *d_a3, int a_pitch, const uint8_t *d_b3, int b_pitch, int w, int h,
                                const float *d_disp_ab, const float *d_disp_ba, const float *h_times, int n_times,
                                uint8_t *d_dst3, int dst_pitch, size_t time_stride_bytes, int64_t *d_stats /* may be NULL */, void *stream);
@@ -591,7 +595,9 @@ int ofx_flow_median(const ofx_median_desc *items, int n, void *stream);
  * n outside 1 .. OFX_STREAM_MAX_BATCH, an even window or one outside 3 .. 23, w or h <= 0, w * h >= 2^28, a pitch below w or no
  * multiple of 4 or a plane of 2^31 bytes, a pointer that is not 4-byte (d_stats: 8-byte) aligned, strength_pitch < w, a cell
  * outside 4 .. 256, a negative border, a min_strength that is negative or not finite, only one of d_cells and d_cell_strength, or
- * d_stats without cells.  The points for ofx_session_stream_tracks at `level`: these two calls on ofx_session_plane(s, 0, level). */
+ * d_stats without cells.  The points for ofx_session_stream_tracks at `level`: these two calls on ofx_session_plane(s, 0, level).
+ * d_stats needs no initialisation (the call zeroes it on the stream first); every output is written in full for the item's own extent
+ * and nothing is carried from one call to the next. */
 typedef struct ofx_texture_desc {
     const uint8_t *d_plane;
     int pitch, w, h;         /* pitch a multiple of 4, plane 4-byte aligned: what ofx_geom asks */
@@ -657,7 +663,8 @@ int ofx_compact_features(const int32_t *d_cells, int n_cells, int max_points, fl
  * among them), levels outside 1 .. 8 or a coarsest level of width or height 0, w or h above 2^19, n_frames outside 2 .. 17, an
  * even window or one outside 3 .. 23, max_iters outside 1 .. 32, eps_q < 0, min_lambda negative or not finite, max_sad < 0,
  * pair0 < 1 or pair0 + pairs >= 2^23, n_points < 1, a pitch below the level's width or a plane of 2^31 bytes or more, d_points or
- * d_history not 8-byte aligned, d_status or d_sad not 4-byte aligned, d_stats not 8-byte aligned. */
+ * d_history not 8-byte aligned, d_status or d_sad not 4-byte aligned, d_stats not 8-byte aligned.  d_history, d_sad and d_stats need
+ * no initialisation and carry nothing from one call to the next: d_points and d_status alone hold the chain's state. */
 #define OFX_TRACK_START 1
 #define OFX_TRACK_SINGULAR 2
 #define OFX_TRACK_OUT 3
@@ -728,7 +735,8 @@ int ofx_track_points(const ofx_track_clip *clip, const ofx_track_params *prm, in
  * per item (host arithmetic; 0 for parameters that would be refused), 8-byte aligned, the caller's, its contents undefined
  * afterwards; items must not share it.  Refused with OFX_E_INVALID and a message naming the item and the argument, before anything
  * is enqueued: null pointers (d_status and d_inlier may be NULL), any range above, d_p, d_q, d_model or d_work not 8-byte aligned,
- * d_info or d_status not 4-byte aligned.
+ * d_info or d_status not 4-byte aligned.  d_work needs no initialisation (the first launch resets every word a later one adds to)
+ * and carries nothing from one call to the next: calls with other parameters may follow each other in the same buffer.
  *
  * Host only, in the manner of ofx_generate_gaussian_kernel, on float64 [6] models (a, b, tx, c, d, ty); out may be an input:
  *   ofx_motion_compose  out = m2 after m1:  a = a2 a1 + b2 c1;  b = a2 b1 + b2 d1;  tx = (a2 tx1 + b2 ty1) + tx2;  c, d, ty likewise
@@ -816,7 +824,8 @@ int ofx_motion_invert(const double *m, double *out);
  * ranges, alignments and refusals; 1 <= n_items <= OFX_STREAM_MAX_BATCH items that may differ in n, w and h; 5 + 2 refits launches
  * on the stream (hypotheses, scores, the choice, per refit the sums and a one-block solve, the mask, the outputs), nothing returns
  * to the host between them.  d_work: ofx_fit_homography_work_bytes(prm) bytes per item (0 for parameters that would be refused),
- * 8-byte aligned, the caller's, undefined afterwards; items must not share it. */
+ * 8-byte aligned, the caller's, undefined afterwards; items must not share it.  It needs no initialisation and carries nothing from
+ * one call to the next, as there. */
 #define OFX_MOTION_HOMOGRAPHY 3
 size_t ofx_fit_homography_work_bytes(const ofx_fit_params *prm);
 int ofx_fit_homography(const ofx_fit_desc *items, int n_items, const ofx_fit_params *prm, void *stream);

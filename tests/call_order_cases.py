@@ -1,0 +1,893 @@
+"""One recipe per stateless entry point, for the stream contract of include/ofx.h ("Device entry points only enqueue work; they never
+synchronise or allocate", host arrays read before the call returns, work buffers that need nothing and keep nothing).  A recipe is
+host-only until stage(): its inputs are NumPy arrays and its `want` comes from the referee that the entry point's own GPU test uses.
+tests/test_call_order_cases.py checks the recipes on the CPU, tests/test_gpu_call_order.py runs them the hard way.
+
+A recipe has
+    want            {name: array} by the referee, in the layout read() returns
+    reach           facts about the case that the referee established (tiles, groups, counts), for the CPU test
+    stage(torch)    device copies of the clean inputs (`ins`), the buffers the call reads, the outputs (`outs`, test_gpu_interp.Guarded:
+                    0x5A all around) and the work / stats / scratch buffers (`works`); share=<a staged recipe> reuses that recipe's
+                    work, stats, counter and in-place buffers
+    launch(stream)  builds descriptors and tables afresh, calls the library and overwrites every host array it passed with 0xFF
+    outputs()       {name: tensor} to snapshot;  read(snapshot) -> {name: array}, having checked the bytes around every output"""
+import copy
+import ctypes as C
+import functools
+
+import numpy as np
+
+import consistency_ref as CR
+import dense_ref as D
+import fit_motion_ref as FR
+import homography_cases as HC
+import homography_ref as HR
+import interp3_ref as I3
+import interp_ref as IR
+import klt_ref as K
+import lk_abi_cases as LK
+import median_ref as M
+import motion_ref as MR
+import sampled_ref as SR
+import texture_ref as T
+import warp_affine_ref as WA
+import warp_persp_ref as WP
+from cuda_optical_flow_2_amd import lib as L
+from cuda_optical_flow_2_amd import synth
+from test_gpu_fit_motion import matches as motion_matches
+from test_gpu_interp import FILL, Guarded, Plane
+from test_gpu_warp_affine import image
+
+F32 = np.float32
+NAN = float("nan")
+POISON = {np.dtype(np.uint8): 0xEE, np.dtype(np.float32): NAN, np.dtype(np.int32): -1}     # what an input buffer holds outside its window
+WORK_FILL = 0xA5
+# the tiles of csrc/fit_motion.hip and csrc/fit_homography.hip: matches per score block, hypotheses per score block
+FIT_TILE, FIT_GROUP = 1024, 32
+
+
+@functools.lru_cache(maxsize=None)
+def oracle():
+    import oracle as orc
+
+    orc.build()
+    return orc.Oracle()
+
+
+def wipe(*host):
+    """0xFF over every host array a call was given: a library that reads one after it has returned reads this"""
+    for a in host:
+        if a is None:
+            continue
+        if isinstance(a, np.ndarray):
+            a.reshape(-1).view(np.uint8)[...] = 0xFF
+        else:
+            C.memset(C.addressof(a), 0xFF, C.sizeof(a))
+
+
+def same(got, want, what):
+    """by the bits: float32 through dense_ref.same_bits, float64 as int64, integers as they are"""
+    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.dtype}{got.shape} vs {want.dtype}{want.shape}"
+    if got.dtype == np.float32:
+        ok = D.same_bits(got, want)
+    elif got.dtype == np.float64:
+        ok = got.view(np.int64) == want.view(np.int64)
+    else:
+        ok = got == want
+    if not ok.all():
+        bad = np.argwhere(~ok)
+        raise AssertionError(f"{what}: {len(bad)}/{got.size} differ, first at {bad[:3].tolist()}: {got[tuple(bad[0])]!r} vs {want[tuple(bad[0])]!r}")
+
+
+def differs(a, b):
+    """whether two referee results (dicts of arrays) differ anywhere"""
+    for k in a:
+        if k in b and (a[k].shape != b[k].shape or a[k].tobytes() != b[k].tobytes()):
+            return True
+    return False
+
+
+class In:
+    """An input on the device: `clean` holds its bytes, `buf` is the buffer the call reads (ptr: the input inside it)."""
+
+    def __init__(self, torch, host, lead=0, tail=16):
+        host = np.ascontiguousarray(host).reshape(-1)
+        pad = np.frombuffer(b"\xEE" * host.itemsize, host.dtype)[0]
+        whole = np.concatenate([np.full(lead, pad, host.dtype), host, np.full(tail, pad, host.dtype)])
+        self.clean = torch.from_numpy(whole).cuda()
+        self.buf = torch.empty_like(self.clean)
+        self.ptr = self.buf.data_ptr() + lead * host.itemsize
+        self.poison = POISON[host.dtype]
+
+    @classmethod
+    def plane(cls, torch, arr, pitch, lead, around):
+        """a u8 plane [h, w] with rows `pitch` apart, `lead` bytes in (test_gpu_interp.Plane's layout)"""
+        p = Plane(np.ascontiguousarray(arr), pitch, lead, around)
+        self = cls.__new__(cls)
+        self.clean, self.buf, self.pitch, self.poison = p.t, torch.empty_like(p.t), pitch, 0xEE
+        self.ptr = self.buf.data_ptr() + lead
+        return self
+
+    def fill(self):
+        self.buf.fill_(self.poison)
+
+    def load(self):
+        self.buf.copy_(self.clean)
+
+
+class InOut:
+    """A buffer the call reads and writes in place: a Guarded of one tightly packed slot, loaded with the clean input."""
+
+    def __init__(self, torch, g, host):
+        raw = torch.from_numpy(np.ascontiguousarray(host).reshape(-1).view(np.uint8).copy()).cuda()
+        o = g.lead * g.size
+        self.clean, self.dst = raw, g.flat[o:o + raw.numel()]
+
+    def fill(self):
+        pass
+
+    def load(self):
+        self.dst.copy_(self.clean)
+
+
+def host_of(g, flat):
+    """Guarded.host() of a snapshot of g.flat"""
+    c = copy.copy(g)
+    c.flat = flat
+    return c.host()
+
+
+class Recipe:
+    name = entry = ""
+
+    def __init__(self):
+        self.want, self.reach = {}, {}
+        self.ins, self.loads, self.outs, self.works = [], [], {}, []
+
+    def lib(self):
+        return L.load()
+
+    def outputs(self):
+        return {k: g.flat for k, g in self.outs.items()}
+
+    def read(self, snap):
+        out = {}
+        for k, g in self.outs.items():
+            got, clean = host_of(g, snap[k])
+            assert clean, f"{self.name}: bytes around {k} were written"
+            out[k] = got.reshape(self.want[k].shape) if k in self.want else got
+        return out
+
+    def check(self, snap, what=""):
+        got = self.read(snap)
+        for k, w in self.want.items():
+            same(got[k], w, f"{what or self.name}: {k}")
+
+
+def work(torch, nbytes):
+    return torch.full(((nbytes + 7) // 8 * 8 + 256,), WORK_FILL, dtype=torch.uint8, device="cuda")
+
+
+# ---- camera motion and homography from point matches --------------------------------------------------------------------------------
+class Fit(Recipe):
+    """ofx_fit_motion (model 0 .. 2) or ofx_fit_homography (model 3) on items (p, q, status or None, pair, (w, h))"""
+
+    def __init__(self, name, model, items, H, thr_q, refits, seed):
+        super().__init__()
+        self.name, self.model, self.items, self.prm = name, model, items, (H, thr_q, refits, seed)
+        self.homography = model == HR.HOMOGRAPHY
+        self.entry = "ofx_fit_homography" if self.homography else "ofx_fit_motion"
+        self.dim = 9 if self.homography else 6
+        res = []
+        for p, q, st, pair, size in items:
+            if self.homography:
+                res.append(HR.fit_homography(p, q, size, st, pair, H, thr_q, refits, seed))
+            else:
+                res.append(FR.fit_motion(p, q, size, st, pair, model, H, thr_q, refits, seed))
+        self.want["model"] = np.stack([r[0] for r in res]).reshape(len(items), 1, self.dim)
+        self.want["info"] = np.stack([r[1] for r in res]).reshape(len(items), 1, 8)
+        for i, r in enumerate(res):
+            self.want[f"mask{i}"] = r[2].reshape(1, 1, -1)
+        self.reach = dict(tiles=max(-(-len(it[0]) // FIT_TILE) for it in items), groups=-(-H // FIT_GROUP),
+                          info=[r[1].tolist() for r in res], n=[len(it[0]) for it in items], status=[it[2] is not None for it in items])
+
+    def work_bytes(self):
+        prm = L.FitParams(self.model, *self.prm)
+        fn = self.lib().ofx_fit_homography_work_bytes if self.homography else self.lib().ofx_fit_motion_work_bytes
+        return int(fn(C.byref(prm)))
+
+    def stage(self, torch, share=None):
+        self.ins, self.ptrs = [], []
+        for i, (p, q, st, pair, size) in enumerate(self.items):
+            tp, tq = In(torch, np.asarray(p, F32), 2 * (i % 2)), In(torch, np.asarray(q, F32), 2)
+            ts = None if st is None else In(torch, np.asarray(st, np.int32), 1)
+            self.ins += [t for t in (tp, tq, ts) if t is not None]
+            self.ptrs.append((tp.ptr, tq.ptr, None if ts is None else ts.ptr))
+        n = len(self.items)
+        self.outs = {"model": Guarded(np.float64, n, 1, self.dim, self.dim, 1), "info": Guarded(np.int32, n, 1, 8, 8, 3)}
+        for i, it in enumerate(self.items):
+            self.outs[f"mask{i}"] = Guarded(np.uint8, 1, 1, len(it[0]), len(it[0]), 1 + i)          # (odd addresses)
+        nbytes = self.work_bytes()
+        assert nbytes > 0
+        if share is None:
+            self.works = [work(torch, nbytes) for _ in self.items]
+        else:
+            self.works = share.works[:n]
+            assert len(self.works) == n and all(w.numel() >= nbytes for w in self.works)
+
+    def launch(self, stream):
+        prm = L.FitParams(self.model, *self.prm)
+        descs = (L.FitDesc * len(self.items))()
+        for i, (p, q, st, pair, (w, h)) in enumerate(self.items):
+            dp, dq, ds = self.ptrs[i]
+            descs[i] = L.FitDesc(dp, dq, ds, len(p), pair, w, h, self.outs["model"].slot(i), self.outs["info"].slot(i), self.outs[f"mask{i}"].ptr,
+                                 self.works[i].data_ptr())
+        fn = self.lib().ofx_fit_homography if self.homography else self.lib().ofx_fit_motion
+        rc = fn(descs, len(self.items), C.byref(prm), stream)
+        wipe(descs, prm)
+        return rc
+
+
+FIT_SIZE = (192, 128)
+
+
+def fit_items(homography, seed):
+    """the table's two items: n = 1025 (two score tiles) and n = 65 with a status array around pair 5"""
+    mk = HC.matches if homography else motion_matches
+    a, b = mk(1025, FIT_SIZE, seed), mk(65, (67, 45), seed + 1, status=True)
+    return [(a[0], a[1], None, 0, FIT_SIZE), (b[0], b[1], b[2], 5, (67, 45))]
+
+
+def few_item(usable, n=9, size=(67, 45)):
+    """n matches of which `usable` are usable: the others hold a NaN"""
+    rng = np.random.RandomState(40 + usable)
+    p = np.stack([rng.randint(0, 32 * (size[0] - 1), n), rng.randint(0, 32 * (size[1] - 1), n)], axis=1).astype(F32) / F32(32)
+    q = p[::-1].copy()
+    p[usable:, 0] = NAN
+    return (p, q, None, 0, size)
+
+
+# ---- affine and perspective warp ----------------------------------------------------------------------------------------------------
+WARP_SHAPE = (67, 45, 64, 48)         # (w, h, sw, sh)
+
+
+def _rot(sw, sh, tail=()):
+    c, s = 1.1 * np.cos(0.3), 1.1 * np.sin(0.3)
+    return (c, -s, 0.3 * sw, s, c, -0.2 * sh) + tail
+
+
+class Warp(Recipe):
+    """ofx_warp_affine (6 entries per model) or ofx_warp_perspective (9): items (src, (w, h), model, border, fill), each with d_outside"""
+
+    def __init__(self, name, items):
+        super().__init__()
+        self.name, self.items = name, items
+        self.persp = len(items[0][2]) == 9
+        self.entry = "ofx_warp_perspective" if self.persp else "ofx_warp_affine"
+        outside = []
+        for i, (src, size, m, border, fill) in enumerate(items):
+            dst, n = (WP.warp_perspective if self.persp else WA.warp_affine)(src, m, size, border, fill)
+            self.want[f"dst{i}"] = dst.reshape(1, size[1], -1)
+            outside.append(n)
+        self.want["outside"] = np.array(outside, np.int64).reshape(len(items), 1, 1)
+        self.reach = dict(outside=outside, pixels=[it[1][0] * it[1][1] for it in items], channels=[1 if it[0].ndim == 2 else 3 for it in items])
+
+    def stage(self, torch, share=None):
+        self.ins, self.outs = [], {}
+        for i, (src, (w, h), m, border, fill) in enumerate(self.items):
+            ch = 3 if src.ndim == 3 else 1
+            sh, sw = src.shape[:2]
+            self.ins.append(In.plane(torch, src.reshape(sh, ch * sw), ch * sw + 2 * i + 5, 1 + 2 * i, 0xEE))
+            self.outs[f"dst{i}"] = Guarded(np.uint8, 1, h, ch * w, ch * w + 3 * i + 7, 1 + 2 * i)
+        self.outs["outside"] = Guarded(np.int64, len(self.items), 1, 1, 1, 1) if share is None else share.outs["outside"]
+        self.works = []        # (d_outside is an output: it is compared.  Nothing else is kept.)
+
+    def launch(self, stream):
+        Desc = L.WarpPerspDesc if self.persp else L.WarpAffineDesc
+        descs = (Desc * len(self.items))()
+        for i, (src, (w, h), m, border, fill) in enumerate(self.items):
+            ch = 3 if src.ndim == 3 else 1
+            sh, sw = src.shape[:2]
+            dst = self.outs[f"dst{i}"]
+            descs[i] = Desc(self.ins[i].ptr, self.ins[i].pitch, sw, sh, dst.ptr, dst.pitch, w, h, ch, WA.BORDERS[border], fill,
+                            (C.c_double * len(m))(*m), self.outs["outside"].slot(i))
+        fn = self.lib().ofx_warp_perspective if self.persp else self.lib().ofx_warp_affine
+        rc = fn(descs, len(self.items), stream)
+        wipe(descs)
+        return rc
+
+
+def warp_items(persp, model_c3, model_c1, seed=0):
+    w, h, sw, sh = WARP_SHAPE
+    tail = lambda m: tuple(m) + ((0.0, 0.0, 1.0) if persp and len(m) == 6 else ())      # noqa: E731
+    return [(image(sw, sh, 3, seed), (w, h), tail(model_c3), "constant", 37), (image(sw, sh, 1, seed), (w, h), tail(model_c1), "constant", 201)]
+
+
+INSIDE = (0.9, 0.0, 0.25, 0.0, 0.9, 0.5)                        # 67 x 45 lands inside 64 x 48: nothing is outside
+INSIDE_P = (0.9, 0.0, 0.25, 0.0, 0.9, 0.5, 1e-4, 2e-4, 1.0)
+FAR = (1.0, 0.0, 40.0, 0.0, 1.0, 20.0)                          # most of the output is outside
+
+
+# ---- flow median, prolongation --------------------------------------------------------------------------------------------------------
+class Median(Recipe):
+    entry = "ofx_flow_median"
+
+    def __init__(self, name, items):
+        """items: (kind, w, h, radius)"""
+        super().__init__()
+        self.name, self.items = name, items
+        for i, (kind, w, h, r) in enumerate(items):
+            self.want[f"field{i}"] = np.array(M.want(kind, w, h, r))
+        self.reach = dict(tiles=[(-(-w // 256), -(-h // 16)) for _, w, h, _ in items])
+
+    def stage(self, torch, share=None):
+        self.ins = [In(torch, M.field_case(kind, w, h), 2 + 2 * i, 64) for i, (kind, w, h, r) in enumerate(self.items)]
+        self.outs = {f"field{i}": Guarded(np.float32, 1, h, 2 * w, 2 * w, 4 - 2 * i) for i, (kind, w, h, r) in enumerate(self.items)}
+
+    def launch(self, stream):
+        descs = (L.MedianDesc * len(self.items))()
+        for i, (kind, w, h, r) in enumerate(self.items):
+            descs[i] = L.MedianDesc(self.ins[i].ptr, self.outs[f"field{i}"].ptr, w, h, r, float(D.P_SCALE), None, 0, None, 0)
+        rc = self.lib().ofx_flow_median(descs, len(self.items), stream)
+        wipe(descs)
+        return rc
+
+
+class Prolong(Recipe):
+    entry = "ofx_flow_prolong"
+
+    def __init__(self, name, kind, coarse, fine):
+        super().__init__()
+        self.name, self.kind, self.coarse, self.fine = name, kind, coarse, fine
+        self.field = D.coarse_case(kind, *coarse)
+        self.want["fine"] = D.prolong(self.field, fine[0], fine[1], D.P_SCALE, D.P_MAX_PX)
+
+    def stage(self, torch, share=None):
+        self.ins = [In(torch, self.field, 2, 64)]
+        self.outs = {"fine": Guarded(np.float32, 1, self.fine[1], 2 * self.fine[0], 2 * self.fine[0], 2)}
+
+    def launch(self, stream):
+        d = (L.ProlongDesc * 1)(L.ProlongDesc(self.ins[0].ptr, self.coarse[0], self.coarse[1], self.outs["fine"].ptr, self.fine[0], self.fine[1],
+                                              float(D.P_SCALE), float(D.P_MAX_PX), None, 0, None, 0))
+        rc = self.lib().ofx_flow_prolong(d, 1, stream)
+        wipe(d)
+        return rc
+
+
+# ---- tracker: ofx_pyramid_1ch per frame, then ofx_track_points ----------------------------------------------------------------------
+TRACK_SHAPE = (96, 64, 2)              # (w, h, levels)
+TRACK_PRM = K.Params(9, 10, 1, K.lam_for(9), 200 * 81)
+
+
+def pad4(w):
+    return (w + 3) & ~3
+
+
+class Track(Recipe):
+    """frames[f0 : f0 + n_frames] of a clip: their pyramids by ofx_pyramid_1ch, then one ofx_track_points over them, pairs numbered
+    from pair0.  start: (points, status) on entry."""
+    entry = "ofx_track_points"
+
+    def __init__(self, name, frames, start, pair0, f0=0, n_frames=None):
+        super().__init__()
+        w, h, self.levels = TRACK_SHAPE
+        self.name, self.pair0 = name, pair0
+        self.frames = frames[f0:f0 + (n_frames or len(frames))]
+        self.start = start
+        orc = oracle()
+        self.pyr = [[np.ascontiguousarray(x[:, :, 0]) for x in orc.gauss_pyramid(synth.to_3ch(f), self.levels)] for f in self.frames]
+        pts, status, hist, sad, stats = K.track_chain(self.pyr, start[0], start[1], pair0, TRACK_PRM)
+        self.end = (pts, status)
+        self.want = dict(points=pts, status=status, history=hist, sad=sad, stats=stats)
+        for f in range(len(self.frames)):
+            for k in range(1, self.levels):
+                self.want[f"plane{f}_{k}"] = self.pyr[f][k]
+        alive = start[1] == 0
+        self.reach = dict(tracked=int((status[alive] == 0).sum()), lost=int((status[alive] != 0).sum()), n=len(pts))
+
+    def stage(self, torch, share=None):
+        w, h, levels = TRACK_SHAPE
+        n, pairs = len(self.start[0]), len(self.frames) - 1
+        self.ins = [In.plane(torch, f, pad4(w) + 4, 4 + 4 * i, 0xEE) for i, f in enumerate(self.frames)]      # (one pitch per level for the clip)
+        if share is None:
+            self.outs = dict(points=Guarded(np.float32, 1, 1, 2 * n, 2 * n, 2), status=Guarded(np.int32, 1, 1, n, n, 1),
+                             history=Guarded(np.float32, 1, pairs, 2 * n, 2 * n, 4), sad=Guarded(np.int32, 1, pairs, n, n, 3),
+                             stats=Guarded(np.int64, 1, pairs, 7, 7, 1))
+            self.loads = [InOut(torch, self.outs["points"], self.start[0]), InOut(torch, self.outs["status"], self.start[1])]
+        else:      # the chain goes on in place: nothing is loaded, the first call's buffers hold the state
+            self.outs = {k: share.outs[k] for k in ("points", "status", "history", "sad", "stats")}
+            self.loads = []
+        for f in range(len(self.frames)):
+            for k in range(1, levels):
+                self.outs[f"plane{f}_{k}"] = Guarded(np.uint8, 1, h >> k, w >> k, pad4(w >> k) + 4, 4 * (1 + k + f))
+
+    def launch(self, stream):
+        w, h, levels = TRACK_SHAPE
+        lib = self.lib()
+        nf = len(self.frames)
+        for f in range(nf):
+            planes = (C.c_void_p * levels)(None, *[self.outs[f"plane{f}_{k}"].ptr for k in range(1, levels)])
+            pitches = (C.c_int * levels)(0, *[self.outs[f"plane{f}_{k}"].pitch for k in range(1, levels)])
+            rc = lib.ofx_pyramid_1ch(self.ins[f].ptr, self.ins[f].pitch, w, h, planes, pitches, levels, stream)
+            wipe(planes, pitches)
+            if rc:
+                return rc
+        table = (C.c_void_p * (nf * levels))(*[self.ins[f].ptr if k == 0 else self.outs[f"plane{f}_{k}"].ptr for f in range(nf) for k in range(levels)])
+        pitches = (C.c_int * levels)(self.ins[0].pitch, *[self.outs[f"plane0_{k}"].pitch for k in range(1, levels)])
+        clip = L.TrackClip(w, h, levels, nf, table, pitches)
+        prm = L.TrackParams(TRACK_PRM.window, TRACK_PRM.max_iters, TRACK_PRM.eps_q, TRACK_PRM.max_sad, TRACK_PRM.min_lambda)
+        o = self.outs
+        rc = lib.ofx_track_points(C.byref(clip), C.byref(prm), self.pair0, o["points"].ptr, o["status"].ptr, len(self.start[0]), o["history"].ptr,
+                                  o["sad"].ptr, o["stats"].ptr, stream)
+        wipe(table, pitches, clip, prm)
+        return rc
+
+
+# ---- texture strength, selection, compaction ------------------------------------------------------------------------------------------
+FEAT_WIN, FEAT_CELL = 5, 16
+FILL_F32 = np.frombuffer(bytes([FILL]) * 4, F32)[0]
+
+
+class Features(Recipe):
+    """ofx_texture_features (strength, cells, cell strengths, stats) then ofx_compact_features of its cells.  over=<a Features>: this
+    call writes into that one's buffers, which are larger: what lies past this image's extent keeps that call's values."""
+    entry = "ofx_texture_features"
+
+    def __init__(self, name, img, over=None):
+        super().__init__()
+        self.name, self.img, self.over = name, img, over
+        h, w = img.shape
+        self.w, self.h = w, h
+        self.ncx, self.ncy = T.grid(w, h, FEAT_CELL)
+        self.border = T.default_border(FEAT_WIN)
+        R = T.strength(oracle(), img, FEAT_WIN)
+        cells, cs, stats = T.select(R, FEAT_CELL, self.border, 0.0)
+        pts, occupied = T.compact(cells)
+        first = over or self
+        self.max_points = first.ncx * first.ncy
+        if over is None:
+            points = np.full((self.max_points, 2), FILL_F32, F32)
+            want = dict(strength=R, cells=cells, cell_strength=cs)
+        else:
+            points = over.want["points"].copy()
+            want = {k: over.want[k].copy() for k in ("strength", "cells", "cell_strength")}
+            want["strength"][:h, :w] = R
+            want["cells"].reshape(-1)[:cells.size] = cells.reshape(-1)
+            want["cell_strength"].reshape(-1)[:cs.size] = cs.reshape(-1)
+        points[:occupied] = pts
+        self.want = dict(want, stats=stats, points=points, count=np.array([occupied], np.int32))
+        self.reach = dict(cells=int(stats[0]), occupied=int(stats[1]), blocks=(-(-w // (256 - 2 * (FEAT_WIN // 2))), -(-h // T.STRIP)))
+
+    def stage(self, torch, share=None):
+        assert (share is None) == (self.over is None)
+        self.ins = [In.plane(torch, self.img, pad4(self.w) + 4, 8, 0xEE)]
+        if share is None:
+            w, h = self.w, self.h
+            self.sp = w + 3
+            self.outs = dict(strength=Guarded(np.float32, 1, h, w, self.sp, 4), cells=Guarded(np.int32, 1, self.ncy, 2 * self.ncx, 2 * self.ncx, 2),
+                             cell_strength=Guarded(np.float32, 1, self.ncy, self.ncx, self.ncx, 3), stats=Guarded(np.int64, 1, 1, 4, 4, 1),
+                             points=Guarded(np.float32, 1, 1, 2 * self.max_points, 2 * self.max_points, 2), count=Guarded(np.int32, 1, 1, 1, 1, 1))
+        else:
+            self.sp, self.outs = share.sp, dict(share.outs)
+
+    def launch(self, stream):
+        o = self.outs
+        d = (L.TextureDesc * 1)(L.TextureDesc(self.ins[0].ptr, self.ins[0].pitch, self.w, self.h, o["strength"].ptr, self.sp, o["cells"].ptr,
+                                              o["cell_strength"].ptr, o["stats"].ptr, FEAT_CELL, self.border, 0.0))
+        rc = self.lib().ofx_texture_features(d, 1, FEAT_WIN, stream)
+        wipe(d)
+        if rc:
+            return rc
+        return self.lib().ofx_compact_features(o["cells"].ptr, self.ncx * self.ncy, self.max_points, o["points"].ptr, o["count"].ptr, stream)
+
+
+# ---- pixel displacement, frame interpolation, consistency, motion compensation --------------------------------------------------------
+UV = (3.7, -2.2)
+
+
+class Displacement(Recipe):
+    entry = "ofx_flow_displacement"
+
+    def __init__(self, name, w, h, kind="nonfinite"):
+        super().__init__()
+        self.name, self.w, self.h = name, w, h
+        self.flow = IR.flow_case(kind, w, h)
+        self.want["disp"] = IR.displacement(self.flow, UV, IR.ITER_SCALE)
+
+    def stage(self, torch, share=None):
+        self.ins = [In(torch, self.flow, 2, 64), In(torch, np.array(UV, F32), 1)]
+        self.outs = {"disp": Guarded(np.float32, 1, self.h, 2 * self.w, 2 * self.w, 2)}
+
+    def launch(self, stream):
+        return self.lib().ofx_flow_displacement(self.ins[0].ptr, self.w, self.h, self.ins[1].ptr, float(IR.ITER_SCALE), self.outs["disp"].ptr, stream)
+
+
+class Interp(Recipe):
+    """ofx_interpolate_frames_batch, or with colour ofx_interpolate_frames_3ch_batch: pairs (kind, seed) at TIME_SETS[1], stats given"""
+
+    def __init__(self, name, w, h, pairs, colour):
+        super().__init__()
+        self.name, self.w, self.h, self.pairs, self.colour = name, w, h, pairs, colour
+        self.entry = "ofx_interpolate_frames_3ch_batch" if colour else "ofx_interpolate_frames_batch"
+        self.times = np.array(IR.TIME_SETS[1], F32)
+        ref = [(I3.reference3 if colour else IR.reference)(kind, w, h, 1, seed) for kind, seed in pairs]
+        self.want["frames"] = np.concatenate([r[0] for r in ref]).reshape(len(pairs) * len(self.times), h, -1)
+        self.want["stats"] = np.stack([r[1] for r in ref]).reshape(len(pairs), 1, -1)
+        self.reach = dict(classes=self.want["stats"].reshape(-1, 4)[:, 1:].sum(0).tolist())
+
+    def stage(self, torch, share=None):
+        w, h, c = self.w, self.h, 3 if self.colour else 1
+        n, T_ = len(self.pairs), len(self.times)
+        self.ins, self.table = [], []
+        for i, (kind, seed) in enumerate(self.pairs):
+            a, b = (I3.planes3 if self.colour else IR.planes)(w, h, seed)
+            dab, dba = IR.field_case(kind, w, h, seed)
+            row = [In.plane(torch, a.reshape(h, c * w), c * w + 5 + i, 3 + i, 0xEE), In.plane(torch, b.reshape(h, c * w), c * w + 2 * i, 1, 0xEE),
+                   In(torch, dab, 2, 64), In(torch, dba, 4, 64)]
+            self.ins += row
+            self.table.append(row)
+        self.outs = {"frames": Guarded(np.uint8, n * T_, h, c * w, c * w + 9, 3)}
+        self.outs["stats"] = Guarded(np.int64, n, 1, 4 * T_, 4 * T_, 1) if share is None else share.outs["stats"]
+
+    def launch(self, stream):
+        n, T_ = len(self.pairs), len(self.times)
+        ptrs = lambda f: (C.c_void_p * n)(*[f(i) for i in range(n)])            # noqa: E731
+        ints = lambda f: (C.c_int * n)(*[f(i) for i in range(n)])               # noqa: E731
+        t = self.times.copy()
+        fr, st = self.outs["frames"], self.outs["stats"]
+        host = [ptrs(lambda i: self.table[i][0].ptr), ints(lambda i: self.table[i][0].pitch), ptrs(lambda i: self.table[i][1].ptr),
+                ints(lambda i: self.table[i][1].pitch), ptrs(lambda i: self.table[i][2].ptr), ptrs(lambda i: self.table[i][3].ptr),
+                ptrs(lambda i: fr.slot(i * T_)), ptrs(lambda i: st.slot(i))]
+        fn = self.lib().ofx_interpolate_frames_3ch_batch if self.colour else self.lib().ofx_interpolate_frames_batch
+        rc = fn(host[0], host[1], host[2], host[3], n, self.w, self.h, host[4], host[5], t.ctypes.data_as(C.POINTER(C.c_float)), T_, host[6], fr.pitch,
+                fr.stride, host[7], stream)
+        wipe(t, *host)
+        return rc
+
+
+class Consistency(Recipe):
+    entry = "ofx_flow_consistency_batch"
+
+    def __init__(self, name, w, h, pairs):
+        super().__init__()
+        self.name, self.w, self.h, self.pairs = name, w, h, pairs
+        self.fields = [CR.field_case(kind, w, h, seed) for kind, seed in pairs]
+        self.scale = self.fields[0][2]
+        assert all(f[2] == self.scale for f in self.fields)
+        self.alpha, self.beta = CR.tolerances(self.scale)[0]
+        ref = [CR.reference(kind, w, h, 0, seed) for kind, seed in pairs]
+        self.want = dict(mask=np.stack([r[0] for r in ref]), err=np.stack([r[1] for r in ref]), stats=np.stack([r[2] for r in ref]).reshape(len(pairs), 1, 4))
+        self.reach = dict(classes=self.want["stats"].reshape(-1, 4)[:, 1:].sum(0).tolist())
+
+    def stage(self, torch, share=None):
+        n, w, h = len(self.pairs), self.w, self.h
+        self.ins = [In(torch, f[j], 2 + 2 * j, 64) for f in self.fields for j in (0, 1)]
+        self.outs = dict(mask=Guarded(np.uint8, n, h, w, w + 6, 3), err=Guarded(np.float32, n, h, w, w, 1))
+        self.outs["stats"] = Guarded(np.int64, n, 1, 4, 4, 1) if share is None else share.outs["stats"]
+
+    def launch(self, stream):
+        n = len(self.pairs)
+        o = self.outs
+        host = [(C.c_void_p * n)(*[self.ins[2 * i].ptr for i in range(n)]), (C.c_void_p * n)(*[self.ins[2 * i + 1].ptr for i in range(n)])]
+        host += [(C.c_void_p * n)(*[o[k].slot(i) for i in range(n)]) for k in ("mask", "err", "stats")]
+        rc = self.lib().ofx_flow_consistency_batch(host[0], host[1], n, self.w, self.h, float(self.scale), float(self.alpha), float(self.beta), host[2],
+                                                   o["mask"].pitch, host[3], host[4], stream)
+        wipe(*host)
+        return rc
+
+
+class Motion(Recipe):
+    entry = "ofx_motion_compensate"
+
+    def __init__(self, name, w, h, seed, kind="nonfinite"):
+        super().__init__()
+        self.name, self.w, self.h = name, w, h
+        self.prev, self.next = MR.planes(w, h, seed)
+        self.flow, self.scale = MR.flow_case(kind, w, h, seed)
+        mc, stats = MR.motion(self.prev, self.next, self.flow, UV, self.scale)
+        self.want = dict(mc=mc.reshape(1, h, w), stats=stats.reshape(1, 1, 4))
+        self.reach = dict(not_warped=int(stats[3]))
+
+    def stage(self, torch, share=None):
+        w, h = self.w, self.h
+        self.ins = [In.plane(torch, self.prev, w + 11, 5, 0xEE), In.plane(torch, self.next, w + 22, 3, 0xEE), In(torch, self.flow, 2, 64),
+                    In(torch, np.array(UV, F32), 1)]
+        self.outs = {"mc": Guarded(np.uint8, 1, h, w, w + 9, 61)}
+        self.outs["stats"] = Guarded(np.int64, 1, 1, 4, 4, 1) if share is None else share.outs["stats"]
+
+    def launch(self, stream):
+        i, o = self.ins, self.outs
+        return self.lib().ofx_motion_compensate(i[0].ptr, i[0].pitch, i[1].ptr, i[1].pitch, self.w, self.h, i[2].ptr, i[3].ptr, float(self.scale), o["mc"].ptr,
+                                                o["mc"].pitch, o["stats"].ptr, stream)
+
+
+# ---- the composed field, its arrows, points moved through it --------------------------------------------------------------------------
+SAMPLED = (96, 64, 3, 0)           # (W, H, levels, level)
+ARROW_RES = 12
+
+
+class Sampled(Recipe):
+    """ofx_compose_flow, ofx_sample_arrows and ofx_advect_points on one flow pyramid; start: (points, status) on entry"""
+    entry = "ofx_advect_points"
+
+    def __init__(self, name, seed, start, pair):
+        super().__init__()
+        W, H, Lv, lv = SAMPLED
+        self.name, self.pair, self.start = name, pair, start
+        self.pyr = SR.synth_pyramid(W, H, Lv, lv, seed, 0.04 * W)
+        Cf = SR.compose(self.pyr, Lv, lv)
+        pts, st = SR.advect(Cf, start[0], start[1], pair)
+        self.end = (pts, st)
+        self.want = dict(composed=Cf, arrows=SR.arrows(Cf, ARROW_RES), points=pts, status=st)
+        alive = start[1] == 0
+        self.reach = dict(moved=int((st[alive] == 0).sum()), lost=int((st[alive] != 0).sum()))
+
+    def stage(self, torch, share=None):
+        W, H, Lv, lv = SAMPLED
+        n = len(self.start[0])
+        _, ny, nx = SR.arrow_grid(W, H, ARROW_RES)
+        self.ins = [In(torch, f, 2, 64) for f in self.pyr]
+        self.outs = dict(composed=Guarded(np.float32, 1, H, 2 * W, 2 * W, 2), arrows=Guarded(np.int32, 1, ny, 4 * nx, 4 * nx, 4))
+        if share is None:
+            self.outs.update(points=Guarded(np.float32, 1, 1, 2 * n, 2 * n, 2), status=Guarded(np.int32, 1, 1, n, n, 1))
+            self.loads = [InOut(torch, self.outs["points"], self.start[0]), InOut(torch, self.outs["status"], self.start[1])]
+        else:
+            self.outs.update(points=share.outs["points"], status=share.outs["status"])
+            self.loads = []
+
+    def launch(self, stream):
+        W, H, Lv, lv = SAMPLED
+        lib, o = self.lib(), self.outs
+        table = lambda: (C.c_void_p * Lv)(*[i.ptr for i in self.ins])          # noqa: E731
+        for call in (lambda t: lib.ofx_compose_flow(t, W, H, Lv, lv, o["composed"].ptr, stream),
+                     lambda t: lib.ofx_sample_arrows(t, W, H, Lv, lv, ARROW_RES, o["arrows"].ptr, stream),
+                     lambda t: lib.ofx_advect_points(t, W, H, Lv, lv, self.pair, o["points"].ptr, o["status"].ptr, len(self.start[0]), stream)):
+            t = table()
+            rc = call(t)
+            wipe(t)
+            if rc:
+                return rc
+        return 0
+
+
+def sampled_start(n=40, seed=5):
+    W, H, _, _ = SAMPLED
+    pts = SR.synth_points(W, H, n, seed)
+    st = np.zeros(n, np.int32)
+    st[[n // 2, n - 1]] = (7, -3)
+    return pts, st
+
+
+# ---- a whole pair by the LK calls (tests/test_gpu_lk_abi.py: test_a_whole_pair_by_stateless_calls) -------------------------------------
+class LkPair(Recipe):
+    """lk_float: two ofx_pyramid_1ch, ofx_corner_flows, ofx_lk_levels with d_uv, then ofx_shift_levels, ofx_warp_levels, ofx_lk_levels with
+    accumulate and d_warp_out, ofx_lk_levels with accumulate (three iterations, against Oracle.flow_pair_iter).  compat_cpu has no
+    refinement iterations: the chain ends after the first ofx_lk_levels (against Oracle.flow_pair)."""
+    entry = "ofx_lk_levels"
+
+    def __init__(self, name, mode, swap=False):
+        super().__init__()
+        c = LK.PAIR
+        self.name, self.mode = name, mode
+        self.w, self.h, self.L, self.win = c["w"], c["h"], c["levels"], c["win"]
+        p, n = LK.pair_frames()
+        self.frames = (n, p) if swap else (p, n)
+        orc = oracle()
+        if mode == "lk_float":
+            flows = orc.flow_pair_iter(self.frames[0], self.frames[1], self.L, self.win, c["iters"])
+        else:
+            flows = orc.flow_pair(synth.to_3ch(self.frames[0]), synth.to_3ch(self.frames[1]), self.L, self.win, mode, exact_sums=True)[0]
+        self.want = {f"flow{k}": np.ascontiguousarray(flows[k], F32) for k in range(self.L)}
+        self.reach = dict(nonfinite=int(sum((~np.isfinite(f)).sum() for f in flows)))
+
+    def stage(self, torch, share=None):
+        w, h, Lv = self.w, self.h, self.L
+        self.ins = [In.plane(torch, f, pad4(w), 4, 0xEE) for f in self.frames]
+        self.outs = {f"flow{k}": Guarded(np.float32, 1, h >> k, 2 * (w >> k), 2 * (w >> k), 2) for k in range(Lv)}
+        if share is None:
+            plane = lambda k: work(torch, (h >> k) * pad4(w >> k))               # noqa: E731
+            self.pyr = [[None] + [plane(k) for k in range(1, Lv)] for _ in (0, 1)]
+            self.uv = work(torch, 8 * Lv)
+            self.shifted = [plane(k) for k in range(Lv)]
+            self.warped = [[plane(k) for k in range(Lv)] for _ in (0, 1)]
+            self.works = [t for fr in self.pyr for t in fr[1:]] + [self.uv] + self.shifted + self.warped[0] + self.warped[1]
+        else:
+            self.pyr, self.uv, self.shifted, self.warped, self.works = share.pyr, share.uv, share.shifted, share.warped, share.works
+
+    def launch(self, stream):
+        w, h, Lv, win = self.w, self.h, self.L, self.win
+        lib, mode = self.lib(), L.MODES[self.mode]
+        scale = float(LK.ITER_SCALE)
+        for f in (0, 1):
+            planes = (C.c_void_p * Lv)(None, *[t.data_ptr() for t in self.pyr[f][1:]])
+            pitches = (C.c_int * Lv)(0, *[pad4(w >> k) for k in range(1, Lv)])
+            rc = lib.ofx_pyramid_1ch(self.ins[f].ptr, self.ins[f].pitch, w, h, planes, pitches, Lv, stream)
+            wipe(planes, pitches)
+            if rc:
+                return rc
+        pl = [[self.ins[f].ptr] + [t.data_ptr() for t in self.pyr[f][1:]] for f in (0, 1)]
+        geom = lambda k: L.Geom.full(w >> k, h >> k, pad4(w >> k))              # noqa: E731
+        flow = [self.outs[f"flow{k}"].ptr for k in range(Lv)]
+        uvp = lambda k: None if k == Lv - 1 else self.uv.data_ptr() + 8 * k      # noqa: E731
+
+        def lk(nxt, acc, wsrc=None, wout=None, with_uv=False):
+            d = (L.LkDesc * Lv)(*[L.LkDesc(pl[0][k], nxt[k], geom(k), flow[k], 0, uvp(k) if with_uv else None, acc, 0.0, wsrc and wsrc[k], wout and wout[k],
+                                           scale, None, 0) for k in range(Lv - 1, -1, -1)])
+            rc = lib.ofx_lk_levels(d, Lv, win, mode, stream)
+            wipe(d)
+            return rc
+
+        d = (L.LkDesc * Lv)(*[L.LkDesc(pl[0][k], pl[1][k], geom(k), flow[k], 0, None, 0, 0.0, None, None, 0.0, None, 0) for k in range(Lv)])
+        rc = lib.ofx_corner_flows(d, Lv, win, mode, self.uv.data_ptr(), stream)
+        wipe(d)
+        rc = rc or lk(pl[1], 0, with_uv=True)
+        if rc or self.mode != "lk_float":
+            return rc
+        sd = (L.ShiftDesc * (Lv - 1))(*[L.ShiftDesc(pl[1][k], self.shifted[k].data_ptr(), geom(k), uvp(k)) for k in range(Lv - 1)])
+        rc = lib.ofx_shift_levels(sd, Lv - 1, stream)
+        wipe(sd)
+        if rc:
+            return rc
+        wsrc = [self.shifted[k].data_ptr() for k in range(Lv - 1)] + [pl[1][Lv - 1]]
+        w0, w1 = ([t.data_ptr() for t in self.warped[j]] for j in (0, 1))
+        wd = (L.WarpDesc * Lv)(*[L.WarpDesc(wsrc[k], w0[k], geom(k), flow[k], 0, scale, None, 0) for k in range(Lv)])
+        rc = lib.ofx_warp_levels(wd, Lv, stream)
+        wipe(wd)
+        return rc or lk(w0, 1, wsrc, w1) or lk(w1, 1)
+
+
+# ---- the colour front end -------------------------------------------------------------------------------------------------------------
+GREY, BILATERAL = 1, 2
+
+
+class Frontend(Recipe):
+    entry = "ofx_frontend_1ch"
+
+    def __init__(self, name, w, h, seed):
+        super().__init__()
+        self.name, self.w, self.h, self.win = name, w, h, 5
+        rng = np.random.default_rng(seed)
+        self.imgs = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for _ in (0, 1)]
+        self.modes = [GREY, BILATERAL]
+        orc = oracle()
+        for i, (img, mode) in enumerate(zip(self.imgs, self.modes)):
+            g = orc.grayscale_avg(img)
+            self.want[f"plane{i}"] = np.ascontiguousarray((g if mode == GREY else orc.bilateral_3ch(g, g, self.win, self.win, 2.0, 10.0))[:, :, 0]).reshape(1, h, w)
+
+    def stage(self, torch, share=None):
+        w, h = self.w, self.h
+        self.ins = [In.plane(torch, img.reshape(h, 3 * w), 3 * w + 4 * i + 3, 4 + 4 * i, 0xEE) for i, img in enumerate(self.imgs)]
+        self.outs = {f"plane{i}": Guarded(np.uint8, 1, h, w, w + 7 * i, 1 + i) for i in range(2)}
+
+    def launch(self, stream):
+        n = 2
+        host = [(C.c_void_p * n)(*[i.ptr for i in self.ins]), (C.c_int * n)(*[i.pitch for i in self.ins]),
+                (C.c_void_p * n)(*[self.outs[f"plane{i}"].ptr for i in range(n)]), (C.c_int * n)(*[self.outs[f"plane{i}"].pitch for i in range(n)]),
+                (C.c_int * n)(*self.modes)]
+        rc = self.lib().ofx_frontend_1ch(host[0], host[1], 0, host[2], host[3], 0, n, self.w, self.h, host[4], 0, self.win, 2.0, 10.0, stream)
+        wipe(*host)
+        return rc
+
+
+# ---- the registry -----------------------------------------------------------------------------------------------------------------------
+SIZE = (67, 45)
+MODELS = ("translation", "similarity", "affine")
+
+
+def track_frames(seed=17):
+    w, h, _ = TRACK_SHAPE
+    return [K.cosine_texture(w, h, sx, sy, seed=seed) for sx, sy in ((0.0, 0.0), (1.4, -0.8), (2.1, 0.3))]
+
+
+def track_start(seed=0):
+    w, h, _ = TRACK_SHAPE
+    return K.points_for(w, h, 40, seed=seed)
+
+
+def _fit(model, seed=9, H=33, refits=2, item_seed=1):
+    hom = model == "homography"
+    return Fit(f"fit-{model}", HR.HOMOGRAPHY if hom else FR.MODELS[model], fit_items(hom, item_seed), H, 32, refits, seed)
+
+
+MAKERS = {
+    "fit-translation": lambda: _fit("translation"),
+    "fit-similarity": lambda: _fit("similarity"),
+    "fit-affine": lambda: _fit("affine"),
+    "fit-homography": lambda: _fit("homography"),
+    "warp-affine": lambda: Warp("warp-affine", warp_items(False, _rot(64, 48), (1.0, 0.0, -33 / 32, 0.0, 1.0, -31 / 32))),
+    "warp-perspective": lambda: Warp("warp-perspective", warp_items(True, _rot(64, 48, (1e-3, -5e-4, 1.0)), (1.0, 0.0, -33 / 32, 0.0, 1.0, -31 / 32))),
+    "tracker": lambda: Track("tracker", track_frames(), track_start(), 1),
+    "features": lambda: Features("features", T.make_input("hard", 97, 61)),
+    "median": lambda: Median("median", [("salted", 67, 45, 2), ("ties", 67, 45, 2)]),
+    "prolong": lambda: Prolong("prolong", "salted", (33, 17), (67, 35)),
+    "displacement": lambda: Displacement("displacement", *SIZE),
+    "interp": lambda: Interp("interp", *SIZE, [("borders", 0), ("nonfinite", 1)], False),
+    "interp-colour": lambda: Interp("interp-colour", *SIZE, [("borders", 0), ("nonfinite", 1)], True),
+    "consistency": lambda: Consistency("consistency", *SIZE, [("borders", 0), ("nonfinite", 1)]),
+    "motion": lambda: Motion("motion", *SIZE, 3),
+    "sampled": lambda: Sampled("sampled", 11, sampled_start(), 3),
+    "lk-pair-lk_float": lambda: LkPair("lk-pair-lk_float", "lk_float"),
+    "lk-pair-compat_cpu": lambda: LkPair("lk-pair-compat_cpu", "compat_cpu"),
+    "frontend": lambda: Frontend("frontend", *SIZE, 21),
+}
+NAMES = list(MAKERS)
+
+
+@functools.lru_cache(maxsize=None)
+def recipe(name):
+    """the recipe of the table's row, its referee's answer computed once"""
+    return MAKERS[name]()
+
+
+# a second instance of the same entry point, for two calls in flight (the first is recipe(name))
+OTHERS = {
+    "fit-similarity": lambda: Fit("fit-similarity-b", FR.MODELS["similarity"], fit_items(False, 7), 40, 16, 1, 77),
+    "fit-homography": lambda: Fit("fit-homography-b", HR.HOMOGRAPHY, fit_items(True, 7), 40, 16, 1, 77),
+    "warp-affine": lambda: Warp("warp-affine-b", warp_items(False, (0.9, 0.35, -1.7, -0.2, 1.05, 0.6), _rot(64, 48), seed=3)),
+    "warp-perspective": lambda: Warp("warp-perspective-b", warp_items(True, (0.9, 0.35, -1.7, -0.2, 1.05, 0.6, -2e-3, 1e-3, 1.0), _rot(64, 48), seed=3)),
+    "tracker": lambda: Track("tracker-b", track_frames(seed=5)[::-1], track_start(seed=3), 4),
+    "median": lambda: Median("median-b", [("noise", 67, 45, 1), ("smooth", 67, 45, 2)]),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def other(name):
+    return OTHERS[name]()
+
+
+# ---- buffers reused: calls back to back that share their work, stats, counter or in-place buffers ----------------------------------------
+def _fit_chain(model):
+    hom = model == "homography"
+    code = HR.HOMOGRAPHY if hom else FR.MODELS[model]
+    mk = HC.matches if hom else motion_matches
+    a, b = mk(4099, FIT_SIZE, 2), mk(65, (67, 45), 3, status=True)
+    K_ = code + 1
+    chain = [Fit(f"reuse-{model}-1", code, [(a[0], a[1], None, 0, FIT_SIZE)], 256, 32, 3, 9),
+             Fit(f"reuse-{model}-2", code, [(b[0], b[1], b[2], 5, (67, 45))], 33, 32, 0, 1234),
+             Fit(f"reuse-{model}-3", code, [few_item(3)], 33, 32, 2, 5)]
+    if K_ <= 3:       # (three usable matches are few for a homography only: the other models get an item that is few for them as well)
+        chain.append(Fit(f"reuse-{model}-4", code, [few_item(K_ - 1)], 33, 32, 2, 5))
+    return chain
+
+
+def _track_chain():
+    frames, start = track_frames(), track_start()
+    first = Track("reuse-tracker-1", frames, start, 1, 0, 2)
+    return [first, Track("reuse-tracker-2", frames, first.end, 2, 1, 2)]
+
+
+def _sampled_chain():
+    first = Sampled("reuse-sampled-1", 11, sampled_start(), 3)
+    return [first, Sampled("reuse-sampled-2", 12, first.end, 4)]
+
+
+def _features_chain():
+    first = Features("reuse-features-1", T.make_input("hard", 97, 61))
+    return [first, Features("reuse-features-2", T.make_input("noise", 49, 33), over=first)]
+
+
+CHAINS = {
+    "fit-translation": lambda: _fit_chain("translation"),
+    "fit-similarity": lambda: _fit_chain("similarity"),
+    "fit-affine": lambda: _fit_chain("affine"),
+    "fit-homography": lambda: _fit_chain("homography"),
+    "warp-affine": lambda: [Warp("reuse-warp-affine-1", warp_items(False, FAR, FAR)), Warp("reuse-warp-affine-2", warp_items(False, INSIDE, INSIDE, seed=3))],
+    "warp-perspective": lambda: [Warp("reuse-warp-perspective-1", warp_items(True, FAR, FAR)),
+                                 Warp("reuse-warp-perspective-2", warp_items(True, INSIDE_P, INSIDE_P, seed=3))],
+    "tracker": _track_chain,
+    "features": _features_chain,
+    "interp": lambda: [Interp("reuse-interp-1", *SIZE, [("borders", 0), ("nonfinite", 1)], False), Interp("reuse-interp-2", *SIZE, [("inverse", 2), ("borders", 3)], False)],
+    "interp-colour": lambda: [Interp("reuse-interp-colour-1", *SIZE, [("borders", 0), ("nonfinite", 1)], True),
+                              Interp("reuse-interp-colour-2", *SIZE, [("inverse", 2), ("borders", 3)], True)],
+    "consistency": lambda: [Consistency("reuse-consistency-1", *SIZE, [("borders", 0), ("nonfinite", 1)]),
+                            Consistency("reuse-consistency-2", *SIZE, [("inverse", 2), ("borders", 3)])],
+    "motion": lambda: [Motion("reuse-motion-1", *SIZE, 3), Motion("reuse-motion-2", *SIZE, 4, "borders")],
+    "sampled": _sampled_chain,
+    "lk-pair-lk_float": lambda: [LkPair("reuse-lk-pair-1", "lk_float"), LkPair("reuse-lk-pair-2", "lk_float", swap=True)],
+}
+
+
+@functools.lru_cache(maxsize=None)
+def chain(name):
+    return CHAINS[name]()
