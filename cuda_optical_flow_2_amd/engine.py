@@ -1871,3 +1871,145 @@ def video_stabilize(frames, model: str = "similarity", smooth: Optional[int] = 1
         _warp_launch([(src[f], out[f], maps[f], BORDERS[border], fill, outside[f:f + 1]) for f in range(f0, min(f0 + 16, N))],
                      perspective=maps.shape[1] == 9)
     return out, models, info, outside
+
+
+# ---- frame mosaic and the filled stabiliser ------------------------------------------------------------------------------------------
+
+MOSAIC_MAX_SOURCES = 9                                 # OFX_MOSAIC_MAX_SOURCES
+
+
+def _mosaic_launch(items):
+    """ofx_warp_mosaic on items (srcs, models, dst, border, fill, which, counts): srcs 1 .. 9 uint8 CUDA tensors [h, w] or [h, w, 3]
+    whose pixels are contiguous (rows any distance apart), models nine floats each, dst like a source, which a uint8 CUDA tensor
+    [h, w] or None, counts an int64 CUDA tensor of ten entries or None"""
+    from .lib import MosaicDesc
+
+    descs = (MosaicDesc * len(items))()
+    for i, (srcs, models, dst, border, fill, which, counts) in enumerate(items):
+        d = descs[i]
+        ch = 3 if dst.dim() == 3 else 1
+        assert 1 <= len(srcs) <= MOSAIC_MAX_SOURCES and len(models) == len(srcs), "1 .. 9 sources, a model each"
+        for k, (src, model) in enumerate(zip(srcs, models)):
+            assert src.dim() == dst.dim() and (ch == 1 or (src.shape[2] == 3 and src.stride(2) == 1)), "sources and destination: the same channels"
+            assert src.stride(1) == ch or src.shape[1] == 1, "pixels must be contiguous"
+            s = d.source[k]
+            s.d_src, s.src_pitch, s.sw, s.sh = src.data_ptr(), int(src.stride(0)), int(src.shape[1]), int(src.shape[0])
+            s.model = (C.c_double * 9)(*[float(v) for v in model])
+        assert (dst.stride(1) == ch or dst.shape[1] == 1) and (ch == 1 or (dst.shape[2] == 3 and dst.stride(2) == 1)), "pixels must be contiguous"
+        d.n_sources, d.d_dst, d.dst_pitch, d.w, d.h = len(srcs), dst.data_ptr(), int(dst.stride(0)), int(dst.shape[1]), int(dst.shape[0])
+        d.channels, d.border, d.fill = ch, int(border), int(fill)
+        if which is not None:
+            assert which.stride(1) == 1 or which.shape[1] == 1
+            d.d_which, d.which_pitch = which.data_ptr(), int(which.stride(0))
+        if counts is not None:
+            assert counts.numel() == MOSAIC_MAX_SOURCES + 1 and counts.is_contiguous()
+            d.d_counts = counts.data_ptr()
+    check(_lib.load().ofx_warp_mosaic(descs, len(items), _stream_ptr()), "ofx_warp_mosaic")
+
+
+def warp_mosaic(srcs, models, out_size=None, border: str = "replicate", fill: int = 0, return_which: bool = False, return_counts: bool = False):
+    """Several frames seen through a planar homography each, the first that holds a pixel shown there ("frame mosaic" in
+    include/ofx.h; ofx_warp_mosaic, one launch).  srcs: a list of 1 .. 9 uint8 images, each [H, W] or [H, W, 3], all host arrays or
+    all CUDA tensors, of any sizes, in priority order; models: float64 [S, 9], the INVERSE map of each source as in warp_perspective;
+    out_size: (w, h) of the result (None: source 0's); border: "constant" gives `fill` where no source covers a pixel, "replicate"
+    what warp_perspective gives for source 0 there.  Returns the frame and, with return_which, the uint8 [h, w] index of the source
+    shown at each pixel (255: none) and, with return_counts, int64 [10]: the pixels per source, entry 9 those that no source covers.
+    Arrays in give arrays out, CUDA tensors give CUDA tensors.  A seam between two sources is not blended."""
+    import torch
+
+    assert border in BORDERS, f"border: one of {sorted(BORDERS)}"
+    srcs = list(srcs)
+    assert 1 <= len(srcs) <= MOSAIC_MAX_SOURCES, "srcs: 1 .. 9 images"
+    on_device = all(isinstance(s, torch.Tensor) and s.is_cuda for s in srcs)
+    assert on_device or not any(isinstance(s, torch.Tensor) for s in srcs), "srcs: all host arrays or all CUDA tensors"
+    planes = [(s if on_device else torch.from_numpy(np.ascontiguousarray(s)).cuda()).contiguous() for s in srcs]
+    for p in planes:
+        assert p.dtype == torch.uint8 and p.dim() == planes[0].dim() and (p.dim() == 2 or (p.dim() == 3 and p.shape[2] == 3)), \
+            "srcs: uint8 [H, W] or [H, W, 3], all alike"
+    models = np.ascontiguousarray(models, np.float64).reshape(len(planes), 9)
+    w, h = (int(planes[0].shape[1]), int(planes[0].shape[0])) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    dev = planes[0].device
+    dst = torch.empty((h, w) + tuple(planes[0].shape[2:]), dtype=torch.uint8, device=dev)
+    which = torch.empty((h, w), dtype=torch.uint8, device=dev) if return_which else None
+    counts = torch.empty(MOSAIC_MAX_SOURCES + 1, dtype=torch.int64, device=dev) if return_counts else None
+    _mosaic_launch([(planes, models, dst, BORDERS[border], fill, which, counts)])
+    res = [dst] + ([which] if return_which else []) + ([counts] if return_counts else [])
+    if not on_device:
+        torch.cuda.synchronize()
+        res = [t.cpu().numpy() for t in res]
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+def stabilising_source_maps(models, info, smooth, reach: int):
+    """The sources of the filled stabiliser, from the N - 1 pair models and their info rows (host arrays), with C_f and S_f of
+    stabilising_maps: (maps float64 [N, 1 + 2 reach, 9], frames int32 [N, 1 + 2 reach]).  Row f lists the source frames in the order
+    f, f - 1, f + 1, f - 2, f + 2, .. up to `reach` (0 .. 4) frames away; frames outside the clip are left out, the rest packed to
+    the front, and the tail holds -1 and zeros.  The map of source g in output f is normalize(C_g after the inverse of S_f) for
+    float64 [9] models (C_g for smooth None) and homography_from_affine(C_g after the inverse of S_f) for float64 [6] models
+    (homography_from_affine(C_g) for smooth None); the entry for g = f is stabilising_maps' row f."""
+    reach = int(reach)
+    assert 0 <= reach <= 4, "reach: 0 .. 4"
+    assert smooth is None or smooth >= 0
+    models, info = np.asarray(models, np.float64), np.asarray(info).reshape(-1, 8)
+    nine = models.ndim == 2 and models.shape[1] == 9
+    models = models.reshape(-1, 9 if nine else 6)
+    ident = np.array(IDENTITY9 if nine else (1.0, 0.0, 0.0, 0.0, 1.0, 0.0))
+    path = [ident]
+    for f in range(models.shape[0]):
+        m = models[f] if info[f, 0] == FIT_OK else ident
+        path.append(homography_normalize(homography_compose(m, path[-1])) if nine else motion_compose(m, path[-1]))
+    path = np.stack(path)
+    N = path.shape[0]
+    back = None
+    if smooth is not None:
+        smoothed = smooth_homography_path(path, smooth) if nine else smooth_path(path, smooth)
+        back = [homography_invert(s) if nine else motion_invert(s) for s in smoothed]
+    maps = np.zeros((N, 1 + 2 * reach, 9), np.float64)
+    frames = np.full((N, 1 + 2 * reach), -1, np.int32)
+    for f in range(N):
+        order = [f] + [g for r in range(1, reach + 1) for g in (f - r, f + r)]
+        for k, g in enumerate([g for g in order if 0 <= g < N]):
+            if nine:
+                m = path[g] if back is None else homography_normalize(homography_compose(path[g], back[f]))
+            else:
+                m = homography_from_affine(path[g] if back is None else motion_compose(path[g], back[f]))
+            maps[f, k], frames[f, k] = m, g
+    return maps, frames
+
+
+def video_stabilize_filled(frames, model: str = "similarity", smooth: Optional[int] = 15, reach: int = 2, border: str = "replicate", fill: int = 0,
+                           **motion):
+    """video_stabilize with the border of every frame filled from its neighbours: frame f is ONE mosaic item (ofx_warp_mosaic, 16
+    frames per launch) whose sources are the frames f, f - 1, f + 1, .. up to `reach` (0 .. 4) away, read in place out of the clip,
+    each through its map of stabilising_source_maps; a pixel shows the first of them that holds it, and `border` / `fill` act only
+    where none does.  The other arguments are video_stabilize's; smooth 0 returns the clip unchanged.
+    frames: uint8 CUDA tensor [N, H, W] or [N, H, W, 3].  Returns (the stabilised clip, models, info, outside int64 [N]: the pixels of
+    each frame that no source covers, borrowed int64 [N]: the pixels taken from a neighbour) as CUDA tensors.
+    For the float64 [6] models the frame's own pixels go through the perspective warp's position rule (float64, rounded to the 1/32 px
+    lattice), not ofx_warp_affine's quantised model: they can differ from video_stabilize's by one lattice step, except where nothing
+    rounds (whole-pixel motion).  A seam between two sources is not blended."""
+    import torch
+
+    N, H, W = _clip_shape(frames)
+    assert border in BORDERS, f"border: one of {sorted(BORDERS)}"
+    assert smooth is None or smooth >= 0
+    assert 0 <= int(reach) <= 4, "reach: 0 .. 4"
+    grey = frames if frames.dim() == 3 else _grey_clip(frames)
+    models, info = video_camera_motion(grey, model=model, **motion)
+    outside = torch.zeros(N, dtype=torch.int64, device=frames.device)
+    borrowed = torch.zeros(N, dtype=torch.int64, device=frames.device)
+    if smooth == 0:
+        return frames.clone(), models, info, outside, borrowed
+    maps, index = stabilising_source_maps(models.cpu().numpy(), info.cpu().numpy(), smooth, reach)
+    src = frames.contiguous()
+    out = torch.empty_like(src)
+    counts = torch.empty((N, MOSAIC_MAX_SOURCES + 1), dtype=torch.int64, device=frames.device)
+    for f0 in range(0, N, 16):
+        items = []
+        for f in range(f0, min(f0 + 16, N)):
+            S = int((index[f] >= 0).sum())
+            items.append(([src[int(g)] for g in index[f, :S]], maps[f, :S], out[f], BORDERS[border], fill, None, counts[f]))
+        _mosaic_launch(items)
+    if N:
+        outside, borrowed = counts[:, MOSAIC_MAX_SOURCES].clone(), counts[:, 1:MOSAIC_MAX_SOURCES].sum(dim=1)
+    return out, models, info, outside, borrowed

@@ -97,6 +97,21 @@ class WarpPerspDesc(C.Structure):
                 ("d_outside", C.c_void_p)]
 
 
+OFX_MOSAIC_MAX_SOURCES = 9
+
+
+class MosaicSource(C.Structure):
+    """ofx_mosaic_source (include/ofx.h, "frame mosaic")"""
+    _fields_ = [("d_src", C.c_void_p), ("src_pitch", C.c_int), ("sw", C.c_int), ("sh", C.c_int), ("model", C.c_double * 9)]
+
+
+class MosaicDesc(C.Structure):
+    """ofx_mosaic_desc (include/ofx.h, "frame mosaic")"""
+    _fields_ = [("source", MosaicSource * OFX_MOSAIC_MAX_SOURCES), ("n_sources", C.c_int), ("d_dst", C.c_void_p), ("dst_pitch", C.c_int),
+                ("w", C.c_int), ("h", C.c_int), ("channels", C.c_int), ("border", C.c_int), ("fill", C.c_int), ("d_which", C.c_void_p),
+                ("which_pitch", C.c_int), ("d_counts", C.c_void_p)]
+
+
 class LkDesc(C.Structure):
     """ofx_lk_desc (include/ofx.h): one level of an ofx_lk_levels / ofx_corner_flows launch"""
     _fields_ = [("d_prev", C.c_void_p), ("d_next", C.c_void_p), ("geom", Geom), ("d_flow", C.c_void_p), ("flow_row0", C.c_int),
@@ -207,6 +222,7 @@ _SIGS = {
     "ofx_motion_invert": [_vp, _vp],
     "ofx_warp_affine": [C.POINTER(WarpAffineDesc), _i, _vp],
     "ofx_warp_perspective": [C.POINTER(WarpPerspDesc), _i, _vp],
+    "ofx_warp_mosaic": [C.POINTER(MosaicDesc), _i, _vp],
     "ofx_homography_compose": [_vp, _vp, _vp],
     "ofx_homography_invert": [_vp, _vp],
     "ofx_homography_normalize": [_vp, _vp],

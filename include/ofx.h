@@ -915,6 +915,55 @@ int ofx_homography_invert(const double *m, double *out);
 int ofx_homography_normalize(const double *m, double *out);
 int ofx_homography_from_affine(const double *m6, double *out);
 
+/* ---- frame mosaic -------------------------------------------------------------------
+ * A stabilised frame warped alone shows `fill`, or smeared edge pixels, wherever the smoothed camera looks past the edge of the
+ * shaky frame; the neighbouring frames, placed in the same plane by their own maps, saw what it missed.  This block looks through
+ * several sources per output pixel, in priority order, and shows the first that holds the pixel; panoramas and background plates
+ * are the same launch.  THE definition (tests/mosaic_ref.py restates it in NumPy), on top of "perspective frame warp":
+ *
+ * INPUTS: a destination of w x h pixels, u8, `channels` C in {1, 3} interleaved; n_sources S in 1 .. OFX_MOSAIC_MAX_SOURCES sources;
+ *   source k a u8 plane of sw_k x sh_k pixels with the same C, a pitch of its own and a float64 [9] INVERSE map m_k as in
+ *   "perspective frame warp": used as it is, with the same ranges and refusals per entry.  Sources may differ in size, may be the
+ *   same plane and may overlap each other; none may overlap the destination or the d_which plane.
+ * PER SOURCE k and output pixel (x, y): POSITION and UNDEFINED are those of "perspective frame warp" with m_k, from the pixel's own
+ *   x and y; IN RANGE is that of "affine frame warp" with (sw_k, sh_k).  Source k COVERS the pixel when its position is defined and
+ *   in range; its value there is VALUE of "affine frame warp".
+ * CHOICE    k* = the smallest k that covers the pixel: the output is source k*'s value and which = k*.  When no source covers the
+ *   pixel, which = 255 and the output is: under OFX_BORDER_CONSTANT `fill` in every channel; under OFX_BORDER_REPLICATE exactly
+ *   what ofx_warp_perspective gives for source 0 under replicate -- the value at its clamped position, or `fill` where source 0 is
+ *   undefined there.
+ * OUTPUTS   d_dst.  d_which (may be NULL): a u8 plane of w x h with a pitch of its own >= w, at any alignment, holding k* or 255;
+ *   the bytes of a row beyond column w - 1 stay untouched, as in d_dst.  d_counts (may be NULL; 8-byte aligned): int64
+ *   [OFX_MOSAIC_MAX_SOURCES + 1]; entry k < S the pixels with k* = k, entries S .. 8 zero, entry 9 the pixels no source covers; the
+ *   entries sum to w h; the call zeroes all ten on the stream first.
+ * With S = 1 the destination is ofx_warp_perspective's, byte for byte under either border, and entry 9 equals its d_outside.
+ * Appending a source never changes a pixel that an earlier source covers.  A seam between two sources is not blended.
+ *
+ * ofx_warp_mosaic: 1 <= n <= OFX_STREAM_MAX_BATCH items of any sizes, channels, borders and source counts in ONE launch (plus the
+ * memsets of the counts).  Pitches, alignment and the untouched tail of a row are ofx_warp_affine's; no tap reads outside a source,
+ * whether it covers the pixel or not.  The descriptors embed everything: no host pointer has to stay alive.  Sources k >= S are not
+ * looked at.  Refused with OFX_E_INVALID and a message naming the call, the item and, for a source, the source, before anything is
+ * enqueued: null items, n, n_sources outside 1 .. 9, a null d_src among the first S or a null d_dst, channels, border, fill, a size
+ * or a model entry outside its range, a pitch below its row (which_pitch included, when d_which is given), a source that overlaps
+ * d_dst or d_which, d_which overlapping d_dst, d_counts not 8-byte aligned. */
+#define OFX_MOSAIC_MAX_SOURCES 9
+typedef struct ofx_mosaic_source {
+    const uint8_t *d_src;
+    int src_pitch, sw, sh;
+    double model[9];
+} ofx_mosaic_source;
+typedef struct ofx_mosaic_desc {
+    ofx_mosaic_source source[OFX_MOSAIC_MAX_SOURCES];
+    int n_sources;
+    uint8_t *d_dst;
+    int dst_pitch, w, h;
+    int channels, border, fill;
+    uint8_t *d_which; /* may be NULL */
+    int which_pitch;
+    int64_t *d_counts; /* may be NULL */
+} ofx_mosaic_desc;
+int ofx_warp_mosaic(const ofx_mosaic_desc *items, int n, void *stream);
+
 /* ---- layout helpers ------------------------------------------------------ */
 int ofx_extract_ch0(const uint8_t *d_src3, uint8_t *d_dst1, int w, int h, int dst_pitch, void *stream);
 int ofx_replicate_3ch(const uint8_t *d_src1, int src_pitch, uint8_t *d_dst3, int w, int h, void *stream);
