@@ -302,7 +302,7 @@ extern "C" int ofx_track_points(const ofx_track_clip *clip, const ofx_track_para
     A.points = d_points, A.status = d_status, A.history = d_history, A.sad = d_sad, A.stats = reinterpret_cast<unsigned long long *>(d_stats);
     A.n_points = (unsigned)n_points;
     hipStream_t st = ofx_stream(stream);
-    if (d_stats) OFX_HIP(hipMemsetAsync(d_stats, 0, (size_t)pairs * kStats * sizeof(int64_t), st));
+    if (d_stats) OFX_TRY(ofx_zero_words(d_stats, (size_t)pairs * kStats, st));
     const unsigned need = ((unsigned)n_points + kWaves - 1) / kWaves, blocks = need < kMaxBlocks ? need : kMaxBlocks;
     switch (prm->window >> 1) {
     case 1: return launch<1>(A, blocks, st);

@@ -36,6 +36,9 @@ static inline hipStream_t ofx_stream(void *s) { return reinterpret_cast<hipStrea
 
 static inline int ofx_div_up(int a, int b) { return (a + b - 1) / b; }
 
+// zeroes `words` 64-bit words at d_words (8-byte aligned) by a launch on the stream (zero_words.hip: why it is no memset)
+int ofx_zero_words(void *d_words, size_t words, hipStream_t st);
+
 // roctx range around a stage of the session (ofx_core.cpp; active with OFX_ROCTX=1, see there)
 void ofx_range_push(const char *name);
 void ofx_range_pop(void);
@@ -136,7 +139,7 @@ int ofx_check_sample_pyramid(int w, int h, int levels, int level, const char *wh
 // n <= OFX_STREAM_MAX_BATCH pairs of one w x h level in ONE launch.  Pair i reads prev[i] / next[i] (u8 planes, each with its own
 // pitch >= w), flow[i] (w x h interleaved float32, 8-byte aligned) and uv[i] (two floats on the device; NULL = no shift), and
 // writes the image at dst[i] (rows dst_pitch apart, bytes beyond column w - 1 untouched; NULL = none) and ADDS its four sums to
-// stats[i] (8-byte aligned; NULL = none), which the launch function zeroes on the stream first, consecutive slots by one memset.  dst_dwords: every dst and
+// stats[i] (8-byte aligned; NULL = none), which the launch function zeroes on the stream first, consecutive slots by one launch.  dst_dwords: every dst and
 // dst_pitch is 4-byte aligned, whole quads are stored as one dword.  Every argument is checked before anything is enqueued.
 struct ofx_motion_batch {
     const uint8_t *prev[OFX_STREAM_MAX_BATCH], *next[OFX_STREAM_MAX_BATCH];
@@ -153,7 +156,7 @@ int ofx_motion_batch_launch(const ofx_motion_batch *a, void *stream);
 // n <= OFX_STREAM_MAX_BATCH pairs of one w x h level in ONE launch.  Pair i reads fwd[i] and bwd[i] (w x h interleaved float32,
 // 8-byte aligned) and writes the classes at mask[i] (rows mask_pitch apart, bytes beyond column w - 1 untouched; NULL = none), e at
 // err[i] (w floats per row, 4-byte aligned; NULL = none) and ADDS its four counts to stats[i] (8-byte aligned; NULL = none), which
-// the launch function zeroes on the stream first, consecutive slots by one memset.  A pair needs one output at least.  The launch
+// the launch function zeroes on the stream first, consecutive slots by one launch.  A pair needs one output at least.  The launch
 // function works out by itself whether whole quads go out as one dword (every mask and mask_pitch 4-byte aligned) and as four
 // floats (every err 16-byte aligned, w a multiple of 4).  Every argument is checked before anything is enqueued.
 struct ofx_consistency_batch {

@@ -139,7 +139,7 @@ inline int check_batch(const char *who, int n, int w, int h, int bpp, std::initi
     return OFX_OK;
 }
 
-// zero the pairs' stats slots (`words` 64-bit words each) on the stream, one memset per run of consecutive slots (a ring that
+// zero the pairs' stats slots (`words` 64-bit words each) on the stream, one launch per run of consecutive slots (a ring that
 // wraps: two); a pair without a slot is skipped
 inline int zero_stats(unsigned long long *const *stats, int n, size_t words, void *stream)
 {
@@ -150,7 +150,7 @@ inline int zero_stats(unsigned long long *const *stats, int n, size_t words, voi
             continue;
         }
         while (e < n && stats[e] == stats[i] + words * (size_t)(e - i)) ++e;
-        OFX_HIP(hipMemsetAsync(stats[i], 0, (size_t)(e - i) * words * sizeof(unsigned long long), ofx_stream(stream)));
+        OFX_TRY(ofx_zero_words(stats[i], (size_t)(e - i) * words, ofx_stream(stream)));
         i = e;
     }
     return OFX_OK;

@@ -340,11 +340,11 @@ extern "C" int ofx_texture_features(const ofx_texture_desc *items, int n, int wi
     default: OFX_TRY(launch_strength<11>(A, blocks, n, st)); break;
     }
     if (sel_blocks) {
-        for (int i = 0; i < n;) { // one memset per run of consecutive stats slots
+        for (int i = 0; i < n;) { // one zeroing launch per run of consecutive stats slots
             int e = i + 1;
             if (items[i].d_stats) {
                 while (e < n && items[e].d_stats == items[i].d_stats + 4 * (e - i)) ++e;
-                OFX_HIP(hipMemsetAsync(items[i].d_stats, 0, (size_t)(e - i) * 4 * sizeof(int64_t), st));
+                OFX_TRY(ofx_zero_words(items[i].d_stats, (size_t)(e - i) * 4, st));
             }
             i = e;
         }

@@ -262,7 +262,7 @@ extern "C" int ofx_warp_mosaic(const ofx_mosaic_desc *items, int n, void *stream
     }
     hipStream_t st = ofx_stream(stream);
     for (int i = 0; i < n; ++i)
-        if (items[i].d_counts) OFX_HIP(hipMemsetAsync(items[i].d_counts, 0, kBins * sizeof(int64_t), st));
+        if (items[i].d_counts) OFX_TRY(ofx_zero_words(items[i].d_counts, kBins, st));
     if (n == 1)
         launch_for<1>(A, n, max_sources, max_quads, st);
     else if (n <= 4)

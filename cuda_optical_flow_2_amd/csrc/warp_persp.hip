@@ -107,7 +107,7 @@ extern "C" int ofx_warp_perspective(const ofx_warp_persp_desc *items, int n, voi
     }
     hipStream_t st = ofx_stream(stream);
     for (int i = 0; i < n; ++i)
-        if (items[i].d_outside) OFX_HIP(hipMemsetAsync(items[i].d_outside, 0, sizeof(int64_t), st));
+        if (items[i].d_outside) OFX_TRY(ofx_zero_words(items[i].d_outside, 1, st));
     hipLaunchKernelGGL(warp_persp_kernel, dim3((max_quads + kThreads - 1) / kThreads, n), dim3(kThreads), 0, st, A);
     OFX_HIP(hipGetLastError());
     return OFX_OK;

@@ -15,6 +15,21 @@
  *   - "d_" pointers are DEVICE pointers, "h_" pointers are HOST pointers.
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream).  Device
  *     entry points only enqueue work; they never synchronise or allocate.
+ *   - a device entry point (every stateless call: what takes `stream` and no
+ *     session) may be called while its stream is capturing (hipStreamBeginCapture,
+ *     any mode).  It then records only kernel nodes on that stream -- the zeroing
+ *     of its stats, d_outside, d_counts and tracker counters is a launch of the
+ *     library's own, no memset node -- and nothing runs until the graph is
+ *     launched.  Host arrays (descriptors, tables, models, parameters, times) are
+ *     fixed at capture: they are read before the call returns, as ever; device
+ *     buffers are read at every replay, so a replay on other frames, fields,
+ *     points or matches at the same addresses is the call on those.  `stream`
+ *     must not be NULL when capturing.  A call that is refused (OFX_E_INVALID)
+ *     records nothing and leaves the capture open.  What returns data to the
+ *     host synchronises and cannot be captured: ofx_session_get_flow_host, the
+ *     status reads (ofx_session_corner_status, ofx_session_pair_status) and
+ *     ofx_session_timing_read / _read_kind.  The session's own calls: see
+ *     "capturing a session's pair" at ofx_session_run_flow.
  *   - "3ch" images are HWC interleaved u8, 3 bytes per pixel, tightly packed
  *     (the reference's layout, main.cu:95-104).  "1ch" planes are u8 with a row
  *     pitch in bytes that is a multiple of 4 and >= w.  A plane pointer is 4-byte
@@ -1155,7 +1170,16 @@ int ofx_session_build_pyramid(ofx_session *s, void *stream);
 /* Level k of the next frame's pyramid from level k-1, own rows only. */
 int ofx_session_downsample_level(ofx_session *s, int level, void *stream);
 /* All levels against the previous frame's pyramid (main.cu:256-262) in three launches: ofx_session_corner_flows,
- * then ofx_session_run_levels (one multi-level shift launch, one multi-level LK launch). */
+ * then ofx_session_run_levels (one multi-level shift launch, one multi-level LK launch).
+ * Capturing a session's pair: on the plain single-stream path (no shard, no borrowed frames, timing not armed) the sequence
+ * set_frame_device, build_pyramid, swap, set_frame_device, build_pyramid, run_flow may be recorded into one graph on `stream`,
+ * with refinement iterations as well, AFTER one such pair has run live: a session makes the packed plan of a launch shape with
+ * an allocation and a blocking copy the first time it meets the shape, which a capture does not allow.  The host state (which
+ * image set is `prev`, what has been loaded) is consulted and changed when the calls are made, not at a replay: the graph holds
+ * the addresses of the capture, reads the two frame buffers anew at every replay and leaves the flow where ofx_session_flow
+ * pointed when it was recorded.  Not covered, and not to be captured: the staged path with its aux stream
+ * (ofx_session_stage_frame .. solve_staged), the stream pipeline (ofx_session_stream_*), and whatever returns data to the host
+ * (Conventions). */
 int ofx_session_run_flow(ofx_session *s, void *stream);
 int ofx_session_corner_flows(ofx_session *s, void *stream);
 int ofx_session_run_levels(ofx_session *s, void *stream);

@@ -1,5 +1,6 @@
 """The schedules of tests/test_gpu_call_order.py: a recipe of tests/call_order_cases.py on a caller's stream behind several
-milliseconds of other work, its inputs valid only between the harness's copy and its refill, with no host synchronisation anywhere.
+milliseconds of other work, its inputs valid only between the harness's copy and its refill, with no host synchronisation anywhere;
+and the schedule of tests/test_gpu_graph_capture.py (Captured): the same copy, call and snapshot recorded into a graph and replayed.
 Run as a program it measures, per recipe, the call's host time and the busy work the never-synchronises test puts in front of it:
     python tests/call_order.py [output file, default profiles/call_order_times.txt]"""
 import os
@@ -70,6 +71,51 @@ def enqueue(torch, r, lane, call_stream="lane", rounds=BUSY_ROUNDS):
         for i in r.ins:
             i.fill()
         return {k: t.clone() for k, t in r.outputs().items()}
+
+
+# ---- the capture schedule of tests/test_gpu_graph_capture.py ------------------------------------------------------------------------------
+class Captured:
+    """A graph of one single-stream chain on the lane's stream: per recipe the load() copies of its staged clean inputs, its call on
+    lane.ptr, and the copies of its outputs into the snapshot tensors `snaps`, which are allocated here, before the capture.  Nothing
+    else is recorded, nothing runs while it is; `also` (a function of no arguments) is called inside the capture, before the first
+    recipe.  rcs: what the calls returned."""
+
+    def __init__(self, torch, recipes, lane, also=None):
+        self.torch, self.recipes, self.lane = torch, list(recipes), lane
+        self.snaps = [{k: torch.zeros_like(t) for k, t in r.outputs().items()} for r in self.recipes]
+        self.graph = torch.cuda.CUDAGraph()
+        self.rcs, self.errors = [], []
+        torch.cuda.synchronize()
+        try:
+            with torch.cuda.graph(self.graph, stream=lane.stream, capture_error_mode="global"):
+                if also is not None:
+                    also()
+                for r, snap in zip(self.recipes, self.snaps):
+                    for i in r.ins + r.loads:
+                        i.load()
+                    rc = r.launch(lane.ptr)
+                    self.rcs.append(rc)
+                    self.errors.append(r.lib().ofx_last_error() if rc else b"")
+                    for k, t in r.outputs().items():
+                        snap[k].copy_(t)
+        except RuntimeError as e:
+            raise AssertionError(f"{[r.name for r in self.recipes]}: the capture failed ({e}); the calls returned {self.rcs} {self.errors}") from e
+        torch.cuda.synchronize()
+        assert self.rcs == [0] * len(self.recipes), (self.rcs, self.errors)
+
+    def replay(self, before=None):
+        """`before` (live work on the lane's stream), the replay behind it, one synchronisation; returns the snapshots"""
+        with self.torch.cuda.stream(self.lane.stream):
+            if before is not None:
+                before()
+            self.graph.replay()
+        self.torch.cuda.synchronize()
+        return self.snaps
+
+
+def untouched(r):
+    """whether every output of r still holds 0x5A in every byte"""
+    return all(bool((g.flat == FILL).all()) for g in r.outs.values())
 
 
 def call_host_time(torch, r, lane, repeats=5):

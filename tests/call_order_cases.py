@@ -10,7 +10,13 @@ A recipe has
                     0x5A all around) and the work / stats / scratch buffers (`works`); share=<a staged recipe> reuses that recipe's
                     work, stats, counter and in-place buffers
     launch(stream)  builds descriptors and tables afresh, calls the library and overwrites every host array it passed with 0xFF
-    outputs()       {name: tensor} to snapshot;  read(snapshot) -> {name: array}, having checked the bytes around every output"""
+    outputs()       {name: tensor} to snapshot;  read(snapshot) -> {name: array}, having checked the bytes around every output
+    branches()      what of `reach` another case of the same row must reach as well
+
+variant(name) is recipe(name) with other device data: the same geometry, pitches, models, parameters, times and seeds -- everything
+the host passes is identical --, other frames, fields, points, matches and status arrays.  It is what a captured call may see change
+between two replays (tests/test_gpu_graph_capture.py): stage_variant() puts its clean inputs on the device, load_variant() copies
+them into the recipe's own staged `clean` buffers, from which every load() -- live or recorded -- fills the buffers the call reads."""
 import copy
 import ctypes as C
 import functools
@@ -27,6 +33,8 @@ import interp_ref as IR
 import klt_ref as K
 import lk_abi_cases as LK
 import median_ref as M
+import mosaic_cases as MC
+import mosaic_ref as MZ
 import motion_ref as MR
 import sampled_ref as SR
 import texture_ref as T
@@ -159,10 +167,34 @@ class Recipe:
             out[k] = got.reshape(self.want[k].shape) if k in self.want else got
         return out
 
-    def check(self, snap, what=""):
+    def branches(self):
+        return {}
+
+    def want_over(self, prev):
+        """`want` of this call made on outputs that hold the results of prev, a recipe of the same geometry"""
+        return self.want
+
+    def check(self, snap, what="", want=None):
         got = self.read(snap)
-        for k, w in self.want.items():
+        for k, w in (self.want if want is None else want).items():
             same(got[k], w, f"{what or self.name}: {k}")
+
+    def stage_variant(self, torch, v):
+        """after stage(): device copies of the clean inputs of v, a recipe of this one's geometry, and of this one's own (v's buffers
+        are dropped)"""
+        v.stage(torch)
+        mine, theirs = self.ins + self.loads, v.ins + v.loads
+        assert len(mine) == len(theirs), (self.name, v.name)
+        for a, b in zip(mine, theirs):
+            assert a.clean.shape == b.clean.shape and a.clean.dtype == b.clean.dtype, (self.name, v.name)
+        self.clean_of = {True: [b.clean for b in theirs], False: [a.clean.clone() for a in mine]}
+        v.ins, v.loads, v.outs, v.works = [], [], {}, []
+
+    def load_variant(self, on=True):
+        """the variant's clean inputs (on=False: this recipe's own again) into the staged `clean` buffers, which every load() reads --
+        a load() recorded in a graph as well: copies on the current stream, nothing is allocated"""
+        for a, clean in zip(self.ins + self.loads, self.clean_of[on]):
+            a.clean.copy_(clean)
 
 
 def work(torch, nbytes):
@@ -191,6 +223,12 @@ class Fit(Recipe):
             self.want[f"mask{i}"] = r[2].reshape(1, 1, -1)
         self.reach = dict(tiles=max(-(-len(it[0]) // FIT_TILE) for it in items), groups=-(-H // FIT_GROUP),
                           info=[r[1].tolist() for r in res], n=[len(it[0]) for it in items], status=[it[2] is not None for it in items])
+
+    def branches(self):
+        r = self.reach
+        return dict(tiles=r["tiles"], groups=r["groups"], n=r["n"], status=r["status"], code=[i[0] for i in r["info"]], refits=[i[6] for i in r["info"]],
+                    usable=[0 < i[1] < n for i, n in zip(r["info"], r["n"])], inliers=[0 < i[5] < i[1] for i in r["info"]],
+                    mask=[0 < int(self.want[f"mask{k}"].sum()) < self.want[f"mask{k}"].size for k in range(len(self.items))])
 
     def work_bytes(self):
         prm = L.FitParams(self.model, *self.prm)
@@ -273,6 +311,10 @@ class Warp(Recipe):
         self.want["outside"] = np.array(outside, np.int64).reshape(len(items), 1, 1)
         self.reach = dict(outside=outside, pixels=[it[1][0] * it[1][1] for it in items], channels=[1 if it[0].ndim == 2 else 3 for it in items])
 
+    def branches(self):
+        r = self.reach
+        return dict(pixels=r["pixels"], channels=r["channels"], some=[0 < n < px for n, px in zip(r["outside"], r["pixels"])])
+
     def stage(self, torch, share=None):
         self.ins, self.outs = [], {}
         for i, (src, (w, h), m, border, fill) in enumerate(self.items):
@@ -309,6 +351,88 @@ INSIDE_P = (0.9, 0.0, 0.25, 0.0, 0.9, 0.5, 1e-4, 2e-4, 1.0)
 FAR = (1.0, 0.0, 40.0, 0.0, 1.0, 20.0)                          # most of the output is outside
 
 
+# ---- frame mosaic -----------------------------------------------------------------------------------------------------------------------
+# (w, h, channels, sources, border, fill, d_which given, d_counts given): five items, which take the 16-item instance of
+# csrc/warp_mosaic.hip, with up to six sources, which take its 9-source instance
+MOSAIC_GEOM = [(67, 45, 3, 5, "replicate", 37, True, True), (33, 17, 1, 5, "constant", 201, True, False), (70, 20, 1, 6, "replicate", 0, False, True),
+               (9, 8, 3, 2, "constant", 90, False, False), (45, 33, 1, 1, "constant", 5, True, True)]
+COUNTS_LEFT = np.frombuffer(bytes([FILL]) * 8, np.int64)[0]        # a d_counts slot of an item that gave NULL
+
+
+def mosaic_sources(kind, w, h, ch, S, seed):
+    """(srcs, models) of one item.  'ladder': mosaic_cases.ladder, its images redrawn from `seed`; 'steps': S sources of the output's
+    size, source k 2 (S - k) pixels and a quarter to the right and a pixel and a half up or down, so that each covers two columns more
+    than the one before it and together they cover most of the output; 'edge': the same sources far to the right: source k covers the
+    output's columns 0 .. k + 1 and nothing else"""
+    if kind == "ladder":
+        _, srcs, models, _ = MC.ladder(w, h, S, ch)
+        return [MC.image(s.shape[1], s.shape[0], ch, seed + 7 * k + S) for k, s in enumerate(srcs)], models
+    srcs = [MC.image(w, h, ch, seed + 31 + k) for k in range(S)]
+    if kind == "steps":
+        turn = [0.003 if k == 3 else 0.0 for k in range(S)]
+        models = [(np.cos(a), -np.sin(a), 2.0 * (S - k) + 0.25, np.sin(a), np.cos(a), 1.5 if k % 2 else -1.5, 0.0, 0.0, 1.0) for k, a in enumerate(turn)]
+    else:
+        models = [(1.0, 0.0, float(w - 2 - k), 0.0, 1.0, 0.25, 0.0, 0.0, 1.0) for k in range(S)]
+    return srcs, models
+
+
+def mosaic_items(kind, seed=0):
+    return [mosaic_sources(kind, w, h, ch, S, seed) + ((w, h), border, fill, which, counts) for w, h, ch, S, border, fill, which, counts in MOSAIC_GEOM]
+
+
+class Mosaic(Recipe):
+    """ofx_warp_mosaic on items (srcs, models, (w, h), border, fill, d_which given, d_counts given).  d_counts has a slot per item:
+    the slot of an item that gave NULL keeps its 0x5A."""
+    entry = "ofx_warp_mosaic"
+
+    def __init__(self, name, items):
+        super().__init__()
+        self.name, self.items = name, items
+        counts = []
+        for i, (srcs, models, size, border, fill, which, cnt) in enumerate(items):
+            dst, wh, cn = MZ.mosaic(srcs, models, size, border, fill)
+            self.want[f"dst{i}"] = dst.reshape(1, size[1], -1)
+            if which:
+                self.want[f"which{i}"] = wh.reshape(1, size[1], size[0])
+            counts.append(cn)
+        self.want["counts"] = np.stack([c if it[6] else np.full(10, COUNTS_LEFT, np.int64) for c, it in zip(counts, items)]).reshape(len(items), 1, 10)
+        self.reach = dict(counts=[c.tolist() for c in counts], pixels=[it[2][0] * it[2][1] for it in items], sources=[len(it[0]) for it in items],
+                          channels=[1 if it[0][0].ndim == 2 else 3 for it in items], which=[it[5] for it in items], given=[it[6] for it in items])
+
+    def branches(self):
+        r = self.reach
+        return dict(pixels=r["pixels"], sources=r["sources"], channels=r["channels"], which=r["which"], given=r["given"],
+                    nobody=[c[9] > 0 for c in r["counts"]], first=[c[0] > 0 for c in r["counts"]], later=[sum(c[1:9]) > 0 for c in r["counts"]])
+
+    def stage(self, torch, share=None):
+        self.ins, self.table, self.outs = [], [], {}
+        for i, (srcs, models, (w, h), border, fill, which, cnt) in enumerate(self.items):
+            ch = 3 if srcs[0].ndim == 3 else 1
+            row = [In.plane(torch, s.reshape(s.shape[0], ch * s.shape[1]), ch * s.shape[1] + 2 * (i + k) + 5, 1 + 2 * ((i + k) % 3), 0xEE) for k, s in enumerate(srcs)]
+            self.ins += row
+            self.table.append(row)
+            self.outs[f"dst{i}"] = Guarded(np.uint8, 1, h, ch * w, ch * w + 3 * i + 7, 1 + 2 * (i % 2) + (i % 4 == 3))
+            if which:
+                self.outs[f"which{i}"] = Guarded(np.uint8, 1, h, w, w + i + 3, 1 + i % 4) if share is None else share.outs[f"which{i}"]
+        self.outs["counts"] = Guarded(np.int64, len(self.items), 1, 10, 10, 1) if share is None else share.outs["counts"]
+        self.works = []        # (d_which and d_counts are outputs: they are compared)
+
+    def launch(self, stream):
+        descs = (L.MosaicDesc * len(self.items))()
+        for i, (srcs, models, (w, h), border, fill, which, cnt) in enumerate(self.items):
+            d, ch = descs[i], 3 if srcs[0].ndim == 3 else 1
+            for k, (src, m) in enumerate(zip(srcs, models)):
+                s, p = d.source[k], self.table[i][k]
+                s.d_src, s.src_pitch, s.sw, s.sh, s.model = p.ptr, p.pitch, src.shape[1], src.shape[0], (C.c_double * 9)(*m)
+            dst = self.outs[f"dst{i}"]
+            d.n_sources, d.d_dst, d.dst_pitch, d.w, d.h, d.channels, d.border, d.fill = len(srcs), dst.ptr, dst.pitch, w, h, ch, WP.BORDERS[border], fill
+            d.d_which, d.which_pitch = (self.outs[f"which{i}"].ptr, self.outs[f"which{i}"].pitch) if which else (None, -1)
+            d.d_counts = self.outs["counts"].slot(i) if cnt else None
+        rc = self.lib().ofx_warp_mosaic(descs, len(self.items), stream)
+        wipe(descs)
+        return rc
+
+
 # ---- flow median, prolongation --------------------------------------------------------------------------------------------------------
 class Median(Recipe):
     entry = "ofx_flow_median"
@@ -320,6 +444,9 @@ class Median(Recipe):
         for i, (kind, w, h, r) in enumerate(items):
             self.want[f"field{i}"] = np.array(M.want(kind, w, h, r))
         self.reach = dict(tiles=[(-(-w // 256), -(-h // 16)) for _, w, h, _ in items])
+
+    def branches(self):
+        return dict(self.reach, radius=[it[3] for it in self.items])
 
     def stage(self, torch, share=None):
         self.ins = [In(torch, M.field_case(kind, w, h), 2 + 2 * i, 64) for i, (kind, w, h, r) in enumerate(self.items)]
@@ -337,11 +464,17 @@ class Median(Recipe):
 class Prolong(Recipe):
     entry = "ofx_flow_prolong"
 
-    def __init__(self, name, kind, coarse, fine):
+    def __init__(self, name, kind, coarse, fine, flip=False):
         super().__init__()
         self.name, self.kind, self.coarse, self.fine = name, kind, coarse, fine
         self.field = D.coarse_case(kind, *coarse)
+        if flip:          # the same values, each at the opposite pixel
+            self.field = np.ascontiguousarray(self.field[::-1, ::-1])
         self.want["fine"] = D.prolong(self.field, fine[0], fine[1], D.P_SCALE, D.P_MAX_PX)
+        self.reach = dict(nonfinite=int((~np.isfinite(self.field)).sum()), huge=int((np.abs(self.field) > 1e6).sum()))
+
+    def branches(self):
+        return {k: v > 0 for k, v in self.reach.items()}
 
     def stage(self, torch, share=None):
         self.ins = [In(torch, self.field, 2, 64)]
@@ -385,6 +518,11 @@ class Track(Recipe):
                 self.want[f"plane{f}_{k}"] = self.pyr[f][k]
         alive = start[1] == 0
         self.reach = dict(tracked=int((status[alive] == 0).sum()), lost=int((status[alive] != 0).sum()), n=len(pts))
+
+    def branches(self):
+        r = self.reach
+        return dict(n=r["n"], tracked=r["tracked"] > 0, lost=r["lost"] > 0, frozen=int((self.start[1] != 0).sum()) > 0,
+                    sad=[bool((self.want["sad"] >= 0).any()), bool((self.want["sad"] == -1).any())], alive_at_the_end=bool(self.want["stats"][-1, 0] > 0))
 
     def stage(self, torch, share=None):
         w, h, levels = TRACK_SHAPE
@@ -459,6 +597,15 @@ class Features(Recipe):
         self.want = dict(want, stats=stats, points=points, count=np.array([occupied], np.int32))
         self.reach = dict(cells=int(stats[0]), occupied=int(stats[1]), blocks=(-(-w // (256 - 2 * (FEAT_WIN // 2))), -(-h // T.STRIP)))
 
+    def branches(self):
+        r = self.reach
+        return dict(cells=r["cells"], blocks=r["blocks"], some=0 < r["occupied"] < r["cells"])
+
+    def want_over(self, prev):
+        points = prev.want["points"].copy()          # entries beyond the count are left alone: they keep prev's
+        points[:self.reach["occupied"]] = self.want["points"][:self.reach["occupied"]]
+        return dict(self.want, points=points)
+
     def stage(self, torch, share=None):
         assert (share is None) == (self.over is None)
         self.ins = [In.plane(torch, self.img, pad4(self.w) + 4, 8, 0xEE)]
@@ -489,11 +636,18 @@ UV = (3.7, -2.2)
 class Displacement(Recipe):
     entry = "ofx_flow_displacement"
 
-    def __init__(self, name, w, h, kind="nonfinite"):
+    def __init__(self, name, w, h, kind="nonfinite", flip=False):
         super().__init__()
         self.name, self.w, self.h = name, w, h
         self.flow = IR.flow_case(kind, w, h)
+        if flip:          # the same values, each at the opposite pixel
+            self.flow = np.ascontiguousarray(self.flow[::-1, ::-1])
         self.want["disp"] = IR.displacement(self.flow, UV, IR.ITER_SCALE)
+        self.reach = dict(nonfinite=int((~np.isfinite(self.flow)).sum()), huge=int((np.abs(self.flow) > 1e6).sum()),
+                          nonfinite_out=int((~np.isfinite(self.want["disp"])).sum()))
+
+    def branches(self):
+        return {k: v > 0 for k, v in self.reach.items()}
 
     def stage(self, torch, share=None):
         self.ins = [In(torch, self.flow, 2, 64), In(torch, np.array(UV, F32), 1)]
@@ -515,6 +669,9 @@ class Interp(Recipe):
         self.want["frames"] = np.concatenate([r[0] for r in ref]).reshape(len(pairs) * len(self.times), h, -1)
         self.want["stats"] = np.stack([r[1] for r in ref]).reshape(len(pairs), 1, -1)
         self.reach = dict(classes=self.want["stats"].reshape(-1, 4)[:, 1:].sum(0).tolist())
+
+    def branches(self):
+        return dict(classes=[c > 0 for c in self.reach["classes"]], pairs=len(self.pairs), times=self.times.tolist())
 
     def stage(self, torch, share=None):
         w, h, c = self.w, self.h, 3 if self.colour else 1
@@ -560,6 +717,9 @@ class Consistency(Recipe):
         self.want = dict(mask=np.stack([r[0] for r in ref]), err=np.stack([r[1] for r in ref]), stats=np.stack([r[2] for r in ref]).reshape(len(pairs), 1, 4))
         self.reach = dict(classes=self.want["stats"].reshape(-1, 4)[:, 1:].sum(0).tolist())
 
+    def branches(self):
+        return dict(classes=[c > 0 for c in self.reach["classes"]], pairs=len(self.pairs), host=(float(self.scale), float(self.alpha), float(self.beta)))
+
     def stage(self, torch, share=None):
         n, w, h = len(self.pairs), self.w, self.h
         self.ins = [In(torch, f[j], 2 + 2 * j, 64) for f in self.fields for j in (0, 1)]
@@ -588,6 +748,9 @@ class Motion(Recipe):
         mc, stats = MR.motion(self.prev, self.next, self.flow, UV, self.scale)
         self.want = dict(mc=mc.reshape(1, h, w), stats=stats.reshape(1, 1, 4))
         self.reach = dict(not_warped=int(stats[3]))
+
+    def branches(self):
+        return dict(some=0 < self.reach["not_warped"] < self.w * self.h, host=float(self.scale))
 
     def stage(self, torch, share=None):
         w, h = self.w, self.h
@@ -622,6 +785,10 @@ class Sampled(Recipe):
         self.want = dict(composed=Cf, arrows=SR.arrows(Cf, ARROW_RES), points=pts, status=st)
         alive = start[1] == 0
         self.reach = dict(moved=int((st[alive] == 0).sum()), lost=int((st[alive] != 0).sum()))
+
+    def branches(self):
+        return dict(moved=self.reach["moved"] > 0, lost=self.reach["lost"] > 0, n=len(self.start[0]), frozen=int((self.start[1] != 0).sum()),
+                    not_drawn=bool((self.want["arrows"][..., 2] == -1).any()))
 
     def stage(self, torch, share=None):
         W, H, Lv, lv = SAMPLED
@@ -680,6 +847,9 @@ class LkPair(Recipe):
             flows = orc.flow_pair(synth.to_3ch(self.frames[0]), synth.to_3ch(self.frames[1]), self.L, self.win, mode, exact_sums=True)[0]
         self.want = {f"flow{k}": np.ascontiguousarray(flows[k], F32) for k in range(self.L)}
         self.reach = dict(nonfinite=int(sum((~np.isfinite(f)).sum() for f in flows)))
+
+    def branches(self):
+        return dict(nonfinite=self.reach["nonfinite"] > 0)
 
     def stage(self, torch, share=None):
         w, h, Lv = self.w, self.h, self.L
@@ -810,8 +980,42 @@ MAKERS = {
     "lk-pair-lk_float": lambda: LkPair("lk-pair-lk_float", "lk_float"),
     "lk-pair-compat_cpu": lambda: LkPair("lk-pair-compat_cpu", "compat_cpu"),
     "frontend": lambda: Frontend("frontend", *SIZE, 21),
+    "mosaic": lambda: Mosaic("mosaic", mosaic_items("ladder")),
 }
 NAMES = list(MAKERS)
+
+# recipe(name) on other device data: everything the host passes is the same
+VARIANTS = {
+    "fit-translation": lambda: _fit("translation", item_seed=7),
+    "fit-similarity": lambda: _fit("similarity", item_seed=7),
+    "fit-affine": lambda: _fit("affine", item_seed=7),
+    "fit-homography": lambda: _fit("homography", item_seed=7),
+    "warp-affine": lambda: Warp("warp-affine", warp_items(False, _rot(64, 48), (1.0, 0.0, -33 / 32, 0.0, 1.0, -31 / 32), seed=3)),
+    "warp-perspective": lambda: Warp("warp-perspective", warp_items(True, _rot(64, 48, (1e-3, -5e-4, 1.0)), (1.0, 0.0, -33 / 32, 0.0, 1.0, -31 / 32), seed=3)),
+    "tracker": lambda: Track("tracker", track_frames(seed=5)[::-1], track_start(seed=3), 1),
+    "features": lambda: Features("features", T.make_input("noise", 97, 61)),
+    "median": lambda: Median("median", [("ties", 67, 45, 2), ("salted", 67, 45, 2)]),
+    "prolong": lambda: Prolong("prolong", "salted", (33, 17), (67, 35), flip=True),
+    "displacement": lambda: Displacement("displacement", *SIZE, flip=True),
+    "interp": lambda: Interp("interp", *SIZE, [("borders", 4), ("nonfinite", 5)], False),
+    "interp-colour": lambda: Interp("interp-colour", *SIZE, [("borders", 4), ("nonfinite", 5)], True),
+    "consistency": lambda: Consistency("consistency", *SIZE, [("borders", 4), ("nonfinite", 5)]),
+    "motion": lambda: Motion("motion", *SIZE, 5),
+    "sampled": lambda: Sampled("sampled", 12, sampled_start(seed=6), 3),
+    "lk-pair-lk_float": lambda: LkPair("lk-pair-lk_float", "lk_float", swap=True),
+    "lk-pair-compat_cpu": lambda: LkPair("lk-pair-compat_cpu", "compat_cpu", swap=True),
+    "frontend": lambda: Frontend("frontend", *SIZE, 22),
+    "mosaic": lambda: Mosaic("mosaic", mosaic_items("ladder", seed=100)),
+}
+assert list(VARIANTS) == NAMES
+
+
+@functools.lru_cache(maxsize=None)
+def variant(name):
+    """the variant of the table's row, its referee's answer computed once"""
+    v = VARIANTS[name]()
+    v.name = name + " (variant)"
+    return v
 
 
 @functools.lru_cache(maxsize=None)
@@ -828,6 +1032,7 @@ OTHERS = {
     "warp-perspective": lambda: Warp("warp-perspective-b", warp_items(True, (0.9, 0.35, -1.7, -0.2, 1.05, 0.6, -2e-3, 1e-3, 1.0), _rot(64, 48), seed=3)),
     "tracker": lambda: Track("tracker-b", track_frames(seed=5)[::-1], track_start(seed=3), 4),
     "median": lambda: Median("median-b", [("noise", 67, 45, 1), ("smooth", 67, 45, 2)]),
+    "mosaic": lambda: Mosaic("mosaic-b", mosaic_items("steps", seed=50)),
 }
 
 
@@ -885,6 +1090,8 @@ CHAINS = {
     "motion": lambda: [Motion("reuse-motion-1", *SIZE, 3), Motion("reuse-motion-2", *SIZE, 4, "borders")],
     "sampled": _sampled_chain,
     "lk-pair-lk_float": lambda: [LkPair("reuse-lk-pair-1", "lk_float"), LkPair("reuse-lk-pair-2", "lk_float", swap=True)],
+    # the d_counts slots and the d_which planes shared: few pixels covered, then most
+    "mosaic": lambda: [Mosaic("reuse-mosaic-1", mosaic_items("edge")), Mosaic("reuse-mosaic-2", mosaic_items("steps", seed=3))],
 }
 
 

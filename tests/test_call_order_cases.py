@@ -100,7 +100,7 @@ def test_calls_that_share_buffers_have_different_answers(name):
     chain = CC.chain(name)
     assert len(chain) >= 2 and len({r.entry for r in chain}) == 1
     for a, b in zip(chain, chain[1:]):
-        for k in ("stats", "outside", "info", "model", "status", "points", "count", "cells", "flow0"):      # what lies in a shared buffer
+        for k in ("stats", "outside", "info", "model", "status", "points", "count", "cells", "flow0", "counts", "which0", "which1", "which4"):      # what lies in a shared buffer
             if k in a.want and k in b.want:
                 assert a.want[k].tobytes() != b.want[k].tobytes(), f"{name}: {a.name} and {b.name} agree in {k}"
         assert CC.differs(a.want, b.want)
@@ -146,3 +146,122 @@ def test_the_second_feature_image_is_smaller_and_keeps_the_firsts_surroundings()
     assert int(b.want["count"][0]) < int(a.want["count"][0])
     k = int(b.want["count"][0])
     assert np.array_equal(b.want["points"][k:int(a.want["count"][0])], a.want["points"][k:int(a.want["count"][0])]), "the first call's points stay"
+
+
+# ---- the frame mosaic -------------------------------------------------------------------------------------------------------------------
+def test_the_mosaic_takes_the_widest_instances_and_meets_every_bin():
+    for r in (CC.recipe("mosaic"), CC.other("mosaic")):
+        assert len(r.items) == 5 > 4, "more than four items: the 16-item instance"
+        assert max(r.reach["sources"]) == 6 > 5 and min(r.reach["sources"]) == 1, "more than five sources: the 9-source instance"
+        assert len({(it[2], r.reach["channels"][i]) for i, it in enumerate(r.items)}) == 5 and set(r.reach["channels"]) == {1, 3}
+        assert {(w, g) for w, g in zip(r.reach["which"], r.reach["given"])} == {(True, True), (True, False), (False, True), (False, False)}
+        assert all(sum(c) == px for c, px in zip(r.reach["counts"], r.reach["pixels"]))
+        assert any(c[9] > 0 for c in r.reach["counts"]), "a pixel that nobody covers"
+        assert any(sum(c[1:9]) > 0 for c in r.reach["counts"]) and any(c[5] > 0 for c in r.reach["counts"]), "a source that is not the first, and the sixth"
+        assert 67 * 45 > 256 * 4, "more than one block of 256 quads"
+        # the slots of the items that gave no d_counts keep their 0x5A
+        for i, given in enumerate(r.reach["given"]):
+            assert (r.want["counts"][i, 0].tolist() == r.reach["counts"][i]) == given
+            assert given or (r.want["counts"][i].view(np.uint8) == CC.FILL).all()
+        assert sorted(k for k in r.want if k.startswith("which")) == [f"which{i}" for i, w in enumerate(r.reach["which"]) if w]
+    r = CC.recipe("mosaic")
+    assert all(c[9] > 0 for c in r.reach["counts"]), "the ladder leaves its last band to nobody"
+    for k in ("which0", "which1", "which4"):
+        assert set(np.unique(r.want[k])) >= {0, 255}
+
+
+def test_the_mosaic_chain_goes_from_few_pixels_covered_to_most():
+    a, b = CC.chain("mosaic")
+    assert [it[2:] for it in a.items] == [it[2:] for it in b.items], "the same sizes, borders, fills and outputs: the buffers are shared"
+    for ca, cb, px, S in zip(a.reach["counts"], b.reach["counts"], a.reach["pixels"], a.reach["sources"]):
+        assert 0 < px - ca[9] < px // 3 and px - cb[9] > px // 2, (ca, cb, px)     # less than a third, then more than half
+        assert S == 1 or (ca[1] > 0 and cb[1] > 0), "a source that is not the first, in both calls"
+        assert all(x != y for x, y in zip(ca, cb) if x or y), "every bin that either call fills differs: a bin that is not zeroed again shows"
+
+
+class _Buffer:
+    """what Mosaic.launch asks of a staged input or output"""
+
+    def __init__(self, ptr, pitch):
+        self.ptr, self.pitch = ptr, pitch
+
+    def slot(self, i):
+        return self.ptr + 80 * i
+
+
+class _Library:
+    def ofx_warp_mosaic(self, descs, n, stream):
+        self.descs, self.n, self.stream, self.seen = descs, n, stream, bytes(descs)
+        return 0
+
+
+def _mosaic_call(r):
+    """r.launch against a library that records: (the descriptors as the library saw them, their bytes after the call)"""
+    lib = _Library()
+    r.lib = lambda: lib
+    r.table, r.outs, at = [], {}, 0x1000
+    for i, (srcs, models, (w, h), border, fill, which, cnt) in enumerate(r.items):
+        ch = r.reach["channels"][i]
+        r.table.append([_Buffer(at + 0x100 * k + 1, ch * s.shape[1] + 5 + k) for k, s in enumerate(srcs)])
+        r.outs[f"dst{i}"] = _Buffer(at + 0x1000 + 3, ch * w + 7)
+        r.outs[f"which{i}"] = _Buffer(at + 0x2000 + 1, w + 3)
+        at += 0x10000
+    r.outs["counts"] = _Buffer(0x900008, 10)
+    try:
+        assert r.launch(0x77) == 0 and lib.n == len(r.items) and lib.stream == 0x77
+    finally:
+        del r.lib, r.table
+        r.outs = {}
+    return (CC.L.MosaicDesc * lib.n).from_buffer_copy(lib.seen), bytes(lib.descs)
+
+
+def test_the_mosaic_launch_builds_its_descriptors_and_wipes_them():
+    r = CC.recipe("mosaic")
+    seen, after = _mosaic_call(r)
+    assert set(after) == {0xFF}, "the host array is overwritten as soon as the call has returned"
+    for i, (d, (srcs, models, (w, h), border, fill, which, cnt)) in enumerate(zip(seen, r.items)):
+        assert (d.n_sources, d.w, d.h, d.channels, d.fill) == (len(srcs), w, h, r.reach["channels"][i], fill)
+        assert (d.d_which is not None) == which and (d.d_counts is not None) == cnt and (which or d.which_pitch == -1)
+        assert d.d_counts in (None, 0x900008 + 80 * i) and (d.d_counts or 0) % 8 == 0
+        for k, (s, m) in enumerate(zip(srcs, models)):
+            assert (d.source[k].sw, d.source[k].sh) == (s.shape[1], s.shape[0]) and list(d.source[k].model) == [float(x) for x in m]
+            assert d.source[k].d_src % 2 == 1, "an odd address"
+    # the variant hands the library the very same bytes
+    assert bytes(_mosaic_call(CC.variant("mosaic"))[0]) == bytes(seen)
+
+
+# ---- the variants -----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", CC.NAMES)
+def test_a_variant_has_another_answer_and_reaches_the_same_branches(name):
+    r, v = CC.recipe(name), CC.variant(name)
+    assert v is not r and type(v) is type(r) and v.entry == r.entry
+    assert set(v.want) == set(r.want) and all(v.want[k].shape == r.want[k].shape and v.want[k].dtype == r.want[k].dtype for k in r.want), "the same geometry"
+    assert CC.differs(r.want, v.want), f"{name}: the variant's answer is the recipe's: a replay that read nothing anew would pass"
+    assert r.branches() == v.branches(), (name, r.branches(), v.branches())       # (what the recipe reaches: the tests above)
+    # the call made on outputs that hold the variant's results: only the feature points beyond the count keep anything of them
+    over = r.want_over(v)
+    assert set(over) == set(r.want) and all(over[k] is r.want[k] for k in r.want if (name, k) != ("features", "points"))
+    if name == "features":
+        n, m = r.reach["occupied"], v.reach["occupied"]
+        assert n < m, "the variant finds more points: some of them stay behind the recipe's"
+        assert np.array_equal(over["points"][:n], r.want["points"][:n]) and np.array_equal(over["points"][n:], v.want["points"][n:])
+        assert not np.array_equal(over["points"], r.want["points"])
+
+
+def test_the_variants_pass_the_same_host_arguments():
+    """what the constructors keep of the host's side, row by row"""
+    for name in CC.NAMES:
+        r, v = CC.recipe(name), CC.variant(name)
+        for attr in ("model", "prm", "pair0", "levels", "w", "h", "border", "max_points", "coarse", "fine", "colour", "pair", "mode", "L", "win", "modes"):
+            assert getattr(r, attr, None) == getattr(v, attr, None), (name, attr)
+        for attr in ("times",):
+            assert np.array_equal(getattr(r, attr, 0), getattr(v, attr, 0)), (name, attr)
+    for name in ("fit-affine", "fit-homography"):
+        for a, b in zip(CC.recipe(name).items, CC.variant(name).items):
+            assert (len(a[0]), a[2] is None, a[3], a[4]) == (len(b[0]), b[2] is None, b[3], b[4]), "n, status given, pair, frame size"
+    for name in ("warp-affine", "warp-perspective"):
+        assert [it[1:] for it in CC.recipe(name).items] == [it[1:] for it in CC.variant(name).items], "sizes, models, borders, fills"
+    assert [it[1:] for it in CC.recipe("median").items] == [it[1:] for it in CC.variant("median").items], "w, h, radius"
+    assert [len(f) for f in (CC.recipe("tracker").frames, CC.variant("tracker").frames)] == [3, 3]
+    assert [len(r.start[0]) for r in (CC.recipe("tracker"), CC.variant("tracker"), CC.recipe("sampled"), CC.variant("sampled"))] == [40] * 4
+    assert [it[1:] for it in CC.recipe("mosaic").items] == [it[1:] for it in CC.variant("mosaic").items], "models, sizes, borders, fills, outputs"
