@@ -71,6 +71,12 @@ __device__ __forceinline__ void solve_tail_exact(double a, double b, double d, d
 // them; the choice is per pixel (a lane's result never depends on its neighbours in the wave), which keeps sharded and
 // tiled runs bit-identical to whole-frame ones.  The test for it costs one compare per pixel: solve_fast reports the lanes
 // with det == 0 as a wave mask (scalar registers) and the caller branches on it.
+// A pixel whose numerator cancels takes the replay's path as well, so the 1-ulp bound holds at every pixel: where d xt == b yt
+// exactly (a window with texture on one side of a vertical edge) this formulation returns 0 and the reference its rounding
+// noise, 1e-14 px and 6e8 float ulps away.  The test is |nu| < 2^-22 |d xt| (and |nv| < 2^-22 |a yt|): it holds wherever
+// |nu| < 2^-24 (|d xt| + |b yt|) -- then |b yt| <= |d xt| + |nu| -- which is 8 times the 2^-27 above; two multiplies and two
+// compares per pixel, the lanes join the same mask.  Measured on MI355X, 4K, 5 iterations, lk_float_fast: 2.115 ms per tick of 8
+// pairs against 1.957 before (the same test on the high words with integer compares: 2.193).
 template <int MODE>
 __device__ __forceinline__ void solve_operands(int sxx, int syy, int sxy, int sxt, int syt, double &a, double &b, double &d, double &xt,
                                                double &yt, double &det)
@@ -102,15 +108,17 @@ __device__ __forceinline__ void solve_operands(int sxx, int syy, int sxy, int sx
 //   kRcpIn    taken from a kRcpOut solve of the same three sums: neither det nor the reciprocal is computed.
 enum { kRcpOwn = 0, kRcpOut = 1, kRcpIn = 2 };
 
-// returns the wave mask of the lanes whose determinant is zero (their u, v are not the reference's yet: solve_fix_singular);
+// returns the wave mask of the lanes whose determinant is zero or whose numerator cancels (their u, v are not the reference's yet:
+// solve_fix_singular);
 // kRcpIn reads that off p, which is NaN there and nowhere else
 template <int RCP>
 __device__ __forceinline__ unsigned long long solve_fast_rcp(int sxx, int syy, int sxy, int sxt, int syt, double &p, float &u, float &v)
 {
     double a, b, d, xt, yt, det;
     solve_operands<OFX_MODE_LK_FLOAT>(sxx, syy, sxy, sxt, syt, a, b, d, xt, yt, det);
-    const double nu = __builtin_fma(b, yt, -(d * xt));
-    const double nv = __builtin_fma(b, xt, -(a * yt));
+    const double dxt = d * xt, ayt = a * yt;
+    const double nu = __builtin_fma(b, yt, -dxt);
+    const double nv = __builtin_fma(b, xt, -ayt);
     if constexpr (RCP != kRcpIn) {
         p = __builtin_amdgcn_rcp(det);
         const double e = __builtin_fma(-det, p, 1.0);
@@ -118,8 +126,9 @@ __device__ __forceinline__ unsigned long long solve_fast_rcp(int sxx, int syy, i
     }
     u = (float)(nu * p);
     v = (float)(nv * p);
-    if constexpr (RCP == kRcpIn) return __ballot(p != p);
-    else return __ballot(det == 0.0);
+    const bool cancels = __builtin_fabs(nu) < 0x1p-22 * __builtin_fabs(dxt) || __builtin_fabs(nv) < 0x1p-22 * __builtin_fabs(ayt);
+    if constexpr (RCP == kRcpIn) return __ballot(p != p || cancels);
+    else return __ballot(det == 0.0 || cancels);
 }
 
 __device__ __forceinline__ unsigned long long solve_fast(int sxx, int syy, int sxy, int sxt, int syt, float &u, float &v)
@@ -128,14 +137,17 @@ __device__ __forceinline__ unsigned long long solve_fast(int sxx, int syy, int s
     return solve_fast_rcp<kRcpOwn>(sxx, syy, sxy, sxt, syt, p, u, v);
 }
 
-// the rare path behind solve_fast: the lanes of `zero` take the replay's result
+// the rare path behind solve_fast: the lanes of its mask (det == 0, or a numerator that cancels) take the replay's result
 __device__ __forceinline__ void solve_fix_singular(int sxx, int syy, int sxy, int sxt, int syt, float &u, float &v)
 {
     double a, b, d, xt, yt, det;
     solve_operands<OFX_MODE_LK_FLOAT>(sxx, syy, sxy, sxt, syt, a, b, d, xt, yt, det);
     float eu, ev;
     solve_tail_exact<OFX_MODE_LK_FLOAT>(a, b, d, xt, yt, det, eu, ev);
-    if (det == 0.0) {
+    const double dxt = d * xt, ayt = a * yt;
+    const bool cancels = __builtin_fabs(__builtin_fma(b, yt, -dxt)) < 0x1p-22 * __builtin_fabs(dxt) ||
+                         __builtin_fabs(__builtin_fma(b, xt, -ayt)) < 0x1p-22 * __builtin_fabs(ayt);
+    if (det == 0.0 || cancels) {
         u = eu;
         v = ev;
     }

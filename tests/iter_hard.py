@@ -238,8 +238,9 @@ _BY_ID = {c.id: c for c in A_CASES + C_CASES}
 # that level 2 (116 x 34) still holds flat 11 x 11 windows
 D_CASES = [_BY_ID["A-win9"], _BY_ID["A-win15"], _BY_ID[f"C-win9-w{_P9 + 1}-it5-B2"], _BY_ID[f"C-win5-w{pair_out_w(2) + 1}-it4-B2"],
            _case("D-3level", "stream", 464, 136, 3, 9, 5, 1, seam_x=_P9, block=(56, 120), corner=48)]
-# E: lk_float_fast step by step
-E_CASES = [_BY_ID[f"A-win{win}"] for win in (3, 9, 15, 23)] + [_BY_ID[f"C-win9-w{_P9 + 1}-it5-B2"], _BY_ID[f"C-win5-w{pair_out_w(2) + 1}-it4-B2"]]
+# E: lk_float_fast step by step: every window pair at a time (the fast ITER 3, 2 and 1 of every radius; the windows that were here
+# first come first), and two streamed cases
+E_CASES = [_BY_ID[f"A-win{win}"] for win in (3, 9, 15, 23, 5, 7, 11, 13, 17, 19, 21)] + [_BY_ID[f"C-win9-w{_P9 + 1}-it5-B2"], _BY_ID[f"C-win5-w{pair_out_w(2) + 1}-it4-B2"]]
 # B: tiny and degenerate shapes, synth.random_pair, no census
 B_SHAPES = [(5, 3, 3), (2, 2, 9), (1, 1, 3), (9, 4, 23), (37, 21, 5)]
 

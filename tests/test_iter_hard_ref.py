@@ -54,10 +54,38 @@ C-win15-w241-it5-B2         1   3124     55     72    904     98    216    862  
 D-3level                    0  29460    575    740   1510    357   1087    858  2024
 D-3level                    1   4944     16    113    529    320    263    471     -
 D-3level                    2    424     48     65    295    183    218    651     -
+T3 of tests/lk_instances.py (the tick that also warps, two iterations, one column past a tile at level 1; B = 2 at the even radii):
+C-win3-w249-it2-B1          0   7652     28     24    332    137     59    468   210
+C-win3-w249-it2-B1          1   1603     10     13    106     65     33    233    53
+C-win5-w241-it2-B2          0   7294     27      6    250     94     40    418   287
+C-win5-w241-it2-B2          1   1440     10      7    105     38     35    207    63
+C-win7-w241-it2-B1          0   6944     23     18    212    126     52    442   360
+C-win7-w241-it2-B1          1   1293     10     16    124     71     40    245    69
+C-win9-w233-it2-B2          0   6602     14     21    164    108     58    419   429
+C-win9-w233-it2-B2          1   1159     10     16    194     40     43    209    71
+C-win11-w241-it2-B1         0   6268     17     24    177    110     64    447   494
+C-win11-w241-it2-B1         1   1029     14     18    204     64     47    250    69
+C-win13-w241-it2-B2         0   5942     16     27    136     65     70    404   555
+C-win13-w241-it2-B2         1    903     13     17    211     26     50    215    63
+C-win15-w241-it2-B1         0   5624     18     30    135     86     76    432   612
+C-win15-w241-it2-B1         1    781     14     19    230     70     55    262    53
+C-win17-w233-it2-B2         0   5344     18     31    154     86     80    416   665
+C-win17-w233-it2-B2         1    663     15     19    217     20     58    208    39
+C-win19-w233-it2-B1         0   5068     18     32    158    121     84    464   714
+C-win19-w233-it2-B1         1    549     17     21    224     65     63    282    21
+C-win21-w233-it2-B2         0   4796     20     33    156     79     88    411   759
+C-win21-w233-it2-B2         1    450     18     21    228     24     64    229    10
+C-win23-w233-it2-B1         0   4528     21     34    147    150     92    484   800
+C-win23-w233-it2-B1         1    369     18     23    228     85     65    281     9
+(with B = 2 at the odd radii instead, pair 4 of window 23 has no tap clamped at sx < 0 on level 0: the batch sizes are the
+other way round.)  Every pair of T3 and of T0 (the plain tick, one iteration, lk_float and compat_cpu, windows up to 25x25) has
+non-finite flows at both levels.
 guarded share of level 0 (min_det 5e9): A-win9 0.102, A-win15 0.060, C-win9-w233-it5-B2 0.242-0.244, C-win5-w241-it4-B2 0.444-0.455, D-3level 0.134-0.135
 D-3level, both pairs: pixel 0 of levels 1 and 2 guarded, (nan, nan) unguarded; the shifted level-0 next image differs from the
 unguarded run's in 41872..41881 of 63104 pixels
 values under lk_solve.h's exception: A-win3 1 of 66732, A-win9 0 of 64588, A-win15 0 of 64588, A-win23 0 of 62444, C-win9-w233-it5-B2 0 of 1230240, C-win5-w241-it4-B2 1 of 954360
+... A-win5 1 of 66732, and 0 for A-win7, 11, 13, 17, 19 and 21; T3: C-win3-w249-it2-B1 2 of 164340 (1.2e-5), 0 for the windows 5x5 .. 23x23 (153780 ..
+318120 values each)
 """
 import numpy as np
 import pytest
@@ -65,6 +93,7 @@ import pytest
 from cuda_optical_flow_2_amd import synth
 from conftest import assert_same
 import iter_hard as ih
+import lk_instances as li
 
 
 def _ids(cases):
@@ -147,7 +176,7 @@ def test_warp_census_counts_what_the_warp_does(oracle):
     assert c["last_col"] == 2 * h + 1 and c["last_row"] == 2 * w + 1
 
 
-CENSUS_CASES = ih.A_CASES + ih.C_CASES + [ih.D_CASES[-1]]
+CENSUS_CASES = ih.A_CASES + ih.C_CASES + [ih.D_CASES[-1]] + li.T3_CASES
 
 
 @pytest.fixture(scope="module")
@@ -169,6 +198,8 @@ def test_census_of_the_unguarded_cases(oracle, report, case):
     frames = ih.case_frames(case)
     for pair in range(1, len(frames)):
         chain = ih.oracle_chain(oracle, frames[pair - 1], frames[pair], case.levels, case.win, case.iters)
+        if case in li.T3_CASES:     # what tests/test_gpu_lk_instances.py compares: non-finite flows at both levels of every pair
+            assert all(not np.isfinite(lv["flows"][-1]).all() for lv in chain), f"{case.id} pair {pair}: a level without non-finite flows"
         if pair == 1:
             for k, want in enumerate(oracle.flow_pair_iter(frames[0], frames[1], case.levels, case.win, case.iters)):
                 assert_same(chain[k]["flows"][-1], want, f"{case.id}: the chain ends in flow_pair_iter's level {k}")
@@ -212,7 +243,62 @@ def test_census_of_the_guarded_cases(oracle, report, case):
             assert differ > 0, f"{case.id} pair {pair}: the guard does not change the shift"
 
 
-@pytest.mark.parametrize("case", ih.E_CASES, ids=_ids(ih.E_CASES))
+@pytest.mark.parametrize("win", range(3, 26, 2))
+def test_every_pair_of_the_plain_tick_cases_has_non_finite_flows(oracle, win):
+    """T0 of tests/lk_instances.py (one iteration, lk_float up to 23x23, compat_cpu up to 25x25; lk_float_fast is compared with
+    lk_float's oracle): every pair, both levels -- in compat_cpu too.  The four pairs of B = 2 include the two of B = 1."""
+    cases = [t for t in li.T0_CASES if t.case.win == win]
+    assert {(t.mode, t.deep) for t in cases} == {(m, d) for m in (("lk_float", "compat_cpu", "lk_float_fast") if win <= 23 else ("compat_cpu",)) for d in (-1, 1)}
+    assert {t.case.B for t in cases} == {1, 2} and len({(t.case.w, t.case.h, t.case.levels) for t in cases}) == 1
+    c = max((t.case for t in cases), key=lambda c: c.B)
+    frames = ih.case_frames(c)
+    for mode in sorted({"lk_float" if t.mode == "lk_float_fast" else t.mode for t in cases}):
+        for pair in range(1, len(frames)):
+            flows = oracle.flow_pair(synth.to_3ch(frames[pair - 1]), synth.to_3ch(frames[pair]), c.levels, win, mode, exact_sums=True)[0]
+            for k in range(c.levels):
+                assert not np.isfinite(flows[k]).all(), f"window {win} {mode}: pair {pair} level {k} is finite throughout"
+
+
+def _tap_rows_outside(orc, flow, h, rows, buf):
+    """the pixels of rows [rows) whose warp (orc_warp_bilinear_u8's arithmetic, as iter_hard.warp_census) takes a tap from a row
+    outside [buf) of a level of h rows: what a row window's launch reports in its status word (csrc/lk_body.h, LkArgs::warp_status)"""
+    s = np.float32(orc.ITER_SCALE)
+    yy = np.arange(h, dtype=np.float32)[:, None]
+    big = np.float32(1e9)
+    with np.errstate(invalid="ignore", over="ignore"):
+        sx, sy = s * flow[..., 0], yy + s * flow[..., 1]
+        warped = (sx >= -big) & (sx <= big) & (sy >= -big) & (sy <= big)      # (sx without its column: |x| is far below 1e9)
+        cy = np.clip(np.where(warped, sy, 0), 0, np.float32(h - 1))
+    y0 = cy.astype(np.int64)
+    y1 = np.minimum(y0 + 1, h - 1)
+    return int((warped & ((y0 < buf[0]) | (y1 >= buf[1])))[rows[0]: rows[1]].sum())
+
+
+@pytest.mark.parametrize("c", li.T5_CASES, ids=_ids(li.T5_CASES))
+def test_row_window_cases_stay_inside_their_rows(oracle, c):
+    """T5 of tests/lk_instances.py asserts a status word of 0 on every rank.  On the oracle's chain of every pair: the flow that
+    enters the warp of iteration j + 1 takes no tap from a row outside a rank's buffer, on the rows that rank warps (its own
+    rows and (radius + 1) * (iters - j) more either side: csrc/session_stream.cpp, iter_passes), and pixel 0 of level 1 -- the
+    shift vector of level 0 -- is finite and small against the margin of 8 rows."""
+    frames = li.rows_frames(c)
+    reach = (c.win >> 1) + 1
+    for pair in range(1, len(frames)):
+        chain = ih.oracle_chain(oracle, frames[pair - 1], frames[pair], c.levels, c.win, c.iters)
+        corner = chain[c.levels - 1]["flows"][0][0, 0]
+        assert np.isfinite(corner).all() and (np.abs(corner) <= 2).all(), f"{c.id} pair {pair}: pixel 0 of level {c.levels - 1} is {corner.tolist()}"
+        for k, lv in enumerate(chain):
+            for j, f in enumerate(lv["flows"][:-1], 1):
+                for pl in li.shard_plans(c):
+                    ext = reach * (c.iters - j)
+                    rows = (max(pl.own[k][0] - ext, pl.buf[k][0]), min(pl.own[k][1] + ext, pl.buf[k][1]))
+                    n = _tap_rows_outside(oracle, f, c.h >> k, rows, pl.buf[k])
+                    assert n == 0, f"{c.id} pair {pair} level {k}, the warp of iteration {j + 1}: {n} pixels of rank {pl.rank} reach beyond its rows"
+
+
+FAST_CASES = ih.E_CASES + li.T3_CASES     # what goes through iter_hard.check_fast_step
+
+
+@pytest.mark.parametrize("case", FAST_CASES, ids=_ids(FAST_CASES))
 def test_exempt_share_of_the_fast_cases(oracle, report, case):
     """Along the oracle's own chain: the pixel-steps that csrc/lk_solve.h's exception covers (iter_hard.fast_exempt) are at most
     1e-3 of a case's pixel-steps -- the step-by-step comparison of lk_float_fast is a 1-ulp test, not a test of the exception."""
