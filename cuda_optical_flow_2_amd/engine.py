@@ -2013,3 +2013,163 @@ def video_stabilize_filled(frames, model: str = "similarity", smooth: Optional[i
     if N:
         outside, borrowed = counts[:, MOSAIC_MAX_SOURCES].clone(), counts[:, 1:MOSAIC_MAX_SOURCES].sum(dim=1)
     return out, models, info, outside, borrowed
+
+
+# ---- temporal noise filter --------------------------------------------------------------------------------------------------------
+
+TEMPORAL_MAX_NEIGHBOURS = 4                            # OFX_TEMPORAL_MAX_NEIGHBOURS
+
+
+def temporal_weights(sigma: float) -> np.ndarray:
+    """The weight table of the temporal noise filter for a noise of standard deviation sigma (grey levels), uint16 [256]:
+    w[i] = rint(256 exp(-t^2 / (2 (0.75 sigma)^2))) with t = max(0, i - 1.5 sigma), in float64.  i is the rounded mean absolute
+    difference of two 3 x 3 patches: two patches of one scene point differ by about 1.13 sigma on average, so a difference up to
+    1.5 sigma counts fully, and the weight is gone about 2 sigma above that."""
+    sigma = float(sigma)
+    assert np.isfinite(sigma) and sigma > 0.0, "sigma: a positive number"
+    t = np.maximum(0.0, np.arange(256, dtype=np.float64) - 1.5 * sigma)
+    return np.rint(256.0 * np.exp(-(t * t) / (2.0 * (0.75 * sigma) ** 2))).astype(np.uint16)
+
+
+def _temporal_params(weights, centre_weight):
+    from .lib import TemporalParams
+
+    table = temporal_weights(weights) if np.isscalar(weights) else np.asarray(weights)
+    assert table.shape == (256,) and np.all(table >= 0) and np.all(table <= 256), "weights: a sigma, or 256 integers in 0 .. 256"
+    prm = TemporalParams()
+    prm.weights = (C.c_uint16 * 256)(*[int(v) for v in table])
+    prm.centre_weight, prm.reserved = int(centre_weight), 0
+    return prm
+
+
+def _temporal_descs(items):
+    """the ofx_temporal_desc array of items (centre, planes, fields, dst, stats): centre, dst and the 1 .. 4 planes uint8 CUDA tensors
+    [h, w] or [h, w, 3] whose pixels are contiguous (rows any distance apart), fields float32 CUDA tensors [h, w, 2], tightly packed,
+    stats an int64 CUDA tensor of eight entries or None.  It holds addresses only: the tensors must outlive its use."""
+    from .lib import TemporalDesc
+
+    descs = (TemporalDesc * len(items))()
+    for i, (centre, planes, fields, dst, stats) in enumerate(items):
+        d = descs[i]
+        ch = 3 if centre.dim() == 3 else 1
+        h, w = int(centre.shape[0]), int(centre.shape[1])
+        assert 1 <= len(planes) <= TEMPORAL_MAX_NEIGHBOURS and len(fields) == len(planes), "1 .. 4 neighbours, a field each"
+        for t in [centre, dst] + list(planes):
+            assert t.dim() == centre.dim() and tuple(t.shape) == tuple(centre.shape), "centre, neighbours and destination: one shape"
+            assert (t.stride(1) == ch or w == 1) and (ch == 1 or (t.shape[2] == 3 and t.stride(2) == 1)), "pixels must be contiguous"
+        for k, (plane, field) in enumerate(zip(planes, fields)):
+            assert tuple(field.shape) == (h, w, 2) and field.stride(2) == 1 and (field.stride(1) == 2 or w == 1) and (field.stride(0) == 2 * w or h == 1), \
+                "fields: float32 [h, w, 2], tightly packed"
+            s = d.neighbour[k]
+            s.d_plane, s.pitch, s.pad, s.d_field = plane.data_ptr(), int(plane.stride(0)), 0, field.data_ptr()
+        d.n_neighbours, d.w, d.h, d.channels = len(planes), w, h, ch
+        d.d_centre, d.centre_pitch, d.d_dst, d.dst_pitch = centre.data_ptr(), int(centre.stride(0)), dst.data_ptr(), int(dst.stride(0))
+        if stats is not None:
+            assert stats.numel() == 8 and stats.is_contiguous()
+            d.d_stats = stats.data_ptr()
+    return descs
+
+
+def _temporal_launch(items, prm):
+    """ofx_temporal_filter on the items of _temporal_descs, one launch"""
+    check(_lib.load().ofx_temporal_filter(_temporal_descs(items), len(items), C.byref(prm), _stream_ptr()), "ofx_temporal_filter")
+
+
+def temporal_filter(centre, neighbours, fields, weights, centre_weight: int = 256, return_stats: bool = False):
+    """A frame averaged with its motion-compensated neighbours, each weighted per pixel by the patch test ("temporal noise filter"
+    in include/ofx.h; ofx_temporal_filter, one launch).  centre: uint8 [H, W] or [H, W, 3]; neighbours: 1 .. 4 images like it;
+    fields: float32 [H, W, 2] each, the displacement in pixels centre -> neighbour on the centre's grid; all host arrays or all
+    CUDA tensors.  weights: uint16 [256] with entries <= 256, indexed by the rounded mean absolute difference of the 3 x 3 patches,
+    or a float sigma for temporal_weights(sigma); centre_weight: 1 .. 256.  Returns the filtered frame and, with return_stats,
+    int64 [8]: (pixels, pixels where neighbour 0 / 1 / 2 / 3 is not usable, pixels left as they were for want of any weight, sum of
+    |out - centre|, sum of the weights given).  Arrays in give arrays out, CUDA tensors give CUDA tensors.
+    One neighbouring frame on either side of a field; no recursive filter, no planar colour."""
+    import torch
+
+    neighbours, fields = list(neighbours), list(fields)
+    assert 1 <= len(neighbours) <= TEMPORAL_MAX_NEIGHBOURS and len(fields) == len(neighbours), "1 .. 4 neighbours, a field each"
+    every = [centre] + neighbours + fields
+    on_device = all(isinstance(s, torch.Tensor) and s.is_cuda for s in every)
+    assert on_device or not any(isinstance(s, torch.Tensor) for s in every), "all host arrays or all CUDA tensors"
+    up = lambda s, dt: (s if on_device else torch.from_numpy(np.ascontiguousarray(s, dt)).cuda()).contiguous()
+    c = up(centre, np.uint8)
+    planes = [up(s, np.uint8) for s in neighbours]
+    flds = [up(s, np.float32) for s in fields]
+    assert c.dtype == torch.uint8 and (c.dim() == 2 or (c.dim() == 3 and c.shape[2] == 3)), "centre: uint8 [H, W] or [H, W, 3]"
+    assert all(p.dtype == torch.uint8 for p in planes) and all(f.dtype == torch.float32 for f in flds)
+    dst = torch.empty_like(c)
+    stats = torch.empty(8, dtype=torch.int64, device=c.device) if return_stats else None
+    _temporal_launch([(c, planes, flds, dst, stats)], _temporal_params(weights, centre_weight))
+    res = [dst] + ([stats] if return_stats else [])
+    if not on_device:
+        torch.cuda.synchronize()
+        res = [t.cpu().numpy() for t in res]
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+def _denoise_rings(frames, fwd, bwd, weights, centre_weight, return_stats):
+    """Every frame of a clip filtered with its two neighbours from the clip's two level-0 displacement rings in the convention of
+    _interpolate_rings: fwd[p] is the displacement frame p -> p+1, and bwd, in the REVERSED run's order, holds frame p+1 -> p in
+    bwd[N-2-p].  Frame f takes frame f-1 with bwd[N-1-f] and then frame f+1 with fwd[f]; the first and the last frame have one
+    neighbour.  Up to 16 frames per ofx_temporal_filter launch, frames read in place, fields straight out of the rings."""
+    import torch
+
+    N, H, W = _clip_shape(frames)
+    prm = _temporal_params(weights, centre_weight)
+    out = torch.empty(tuple(frames.shape), dtype=torch.uint8, device=frames.device)
+    stats = torch.empty((N, 8), dtype=torch.int64, device=frames.device) if return_stats else None
+    for f0 in range(0, N, 16):
+        items = []
+        for f in range(f0, min(f0 + 16, N)):
+            near = ([(frames[f - 1], bwd[N - 1 - f])] if f >= 1 else []) + ([(frames[f + 1], fwd[f])] if f + 1 < N else [])
+            items.append((frames[f], [p for p, _ in near], [d for _, d in near], out[f], stats[f] if return_stats else None))
+        _temporal_launch(items, prm)
+    return (out, stats) if return_stats else out
+
+
+def _denoise_result(out, fwd, bwd, return_stats, return_displacements):
+    res = (out if isinstance(out, tuple) else (out,)) + ((fwd, bwd) if return_displacements else ())
+    return res[0] if len(res) == 1 else res
+
+
+def video_denoise(frames, levels: int, window: int, sigma, mode: str = "lk_float", iters: int = 1, min_det: float = 0.0,
+                  batch: Optional[int] = None, centre_weight: int = 256, return_stats: bool = False, return_displacements: bool = False):
+    """Temporal noise reduction of a grey clip: every frame averaged with the previous and the next one along the motion, by
+    "temporal noise filter" of include/ofx.h.  The clip goes through the stream pipeline twice with a level-0 displacement ring, as
+    it is and in reverse frame order, exactly as in video_interpolate; the frames then go through ofx_temporal_filter, up to 16 per
+    launch, read in place, with the fields straight out of the two rings.
+
+    frames: uint8 CUDA tensor [N, H, W], N >= 2, unit column stride.  sigma: the noise's standard deviation in grey levels
+    (temporal_weights(sigma) is the table), or a table uint16 [256].  Returns the filtered clip, uint8 [N, H, W]; return_stats
+    appends int64 [N, 8] (temporal_filter's, per frame; the end frames have one neighbour), return_displacements the two rings as
+    video_interpolate does.  One frame on either side: a longer reach needs composed fields; no recursive filter; not a stage of
+    the stream pipeline itself."""
+    assert frames.dim() == 3, "video_denoise: grey clips only, uint8 [N, H, W] (a colour clip [N, H, W, 3] goes through video_denoise_dense)"
+    frames, N, H, W = _interp_clip(frames, 2)
+    rings = []
+    for order in (None, range(N - 1, -1, -1)):
+        ring = _ring_for(N, H, W, 0, frames.device, None)
+        _run_clip(frames, levels, window, mode, iters, min_det, batch, None, None, False,
+                  lambda s, ring=ring: s.stream_displacement(ring, 0), order=order)
+        rings.append(ring)
+    out = _denoise_rings(frames, rings[0], rings[1], sigma, centre_weight, return_stats)
+    return _denoise_result(out, rings[0], rings[1], return_stats, return_displacements)
+
+
+def video_denoise_dense(frames, levels: int, window: int, sigma, iters: int = 3, min_det: float = 1.0, max_px: Optional[float] = None,
+                        median: int = 0, mode: str = "lk_float", centre_weight: int = 256, return_stats: bool = False,
+                        return_displacements: bool = False):
+    """video_denoise with the displacements of the coarse-to-fine dense flow (_dense_ring at level 0, forwards and in reverse frame
+    order, as video_interpolate_dense), for a grey clip [N, H, W] or an interleaved colour clip [N, H, W, 3]; a colour clip gets
+    its flow from the channel average, made on the device, and all three channels of a pixel share one geometry and one set of
+    weights.  median as video_displacement_dense's; the other arguments and the results as video_denoise's."""
+    if frames.dim() == 4:
+        frames, N, H, W = _interp_clip_colour(frames, 2)
+        grey = _grey_clip(frames)
+    else:
+        frames, N, H, W = _interp_clip(frames, 2)
+        grey = frames
+    fwd = _dense_ring(grey, list(range(N)), levels, window, iters, min_det, max_px, 0, mode, None, median)
+    bwd = _dense_ring(grey, list(range(N - 1, -1, -1)), levels, window, iters, min_det, max_px, 0, mode, None, median)
+    out = _denoise_rings(frames, fwd, bwd, sigma, centre_weight, return_stats)
+    return _denoise_result(out, fwd, bwd, return_stats, return_displacements)

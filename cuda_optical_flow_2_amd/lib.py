@@ -112,6 +112,26 @@ class MosaicDesc(C.Structure):
                 ("which_pitch", C.c_int), ("d_counts", C.c_void_p)]
 
 
+OFX_TEMPORAL_MAX_NEIGHBOURS = 4
+
+
+class TemporalNeighbour(C.Structure):
+    """ofx_temporal_neighbour (include/ofx.h, "temporal noise filter")"""
+    _fields_ = [("d_plane", C.c_void_p), ("pitch", C.c_int), ("pad", C.c_int), ("d_field", C.c_void_p)]
+
+
+class TemporalDesc(C.Structure):
+    """ofx_temporal_desc (include/ofx.h, "temporal noise filter")"""
+    _fields_ = [("neighbour", TemporalNeighbour * OFX_TEMPORAL_MAX_NEIGHBOURS), ("n_neighbours", C.c_int), ("w", C.c_int), ("h", C.c_int),
+                ("channels", C.c_int), ("d_centre", C.c_void_p), ("centre_pitch", C.c_int), ("dst_pitch", C.c_int), ("d_dst", C.c_void_p),
+                ("d_stats", C.c_void_p)]
+
+
+class TemporalParams(C.Structure):
+    """ofx_temporal_params (include/ofx.h, "temporal noise filter")"""
+    _fields_ = [("weights", C.c_uint16 * 256), ("centre_weight", C.c_int), ("reserved", C.c_int)]
+
+
 class LkDesc(C.Structure):
     """ofx_lk_desc (include/ofx.h): one level of an ofx_lk_levels / ofx_corner_flows launch"""
     _fields_ = [("d_prev", C.c_void_p), ("d_next", C.c_void_p), ("geom", Geom), ("d_flow", C.c_void_p), ("flow_row0", C.c_int),
@@ -223,6 +243,7 @@ _SIGS = {
     "ofx_warp_affine": [C.POINTER(WarpAffineDesc), _i, _vp],
     "ofx_warp_perspective": [C.POINTER(WarpPerspDesc), _i, _vp],
     "ofx_warp_mosaic": [C.POINTER(MosaicDesc), _i, _vp],
+    "ofx_temporal_filter": [C.POINTER(TemporalDesc), _i, C.POINTER(TemporalParams), _vp],
     "ofx_homography_compose": [_vp, _vp, _vp],
     "ofx_homography_invert": [_vp, _vp],
     "ofx_homography_normalize": [_vp, _vp],

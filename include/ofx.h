@@ -979,6 +979,70 @@ typedef struct ofx_mosaic_desc {
 } ofx_mosaic_desc;
 int ofx_warp_mosaic(const ofx_mosaic_desc *items, int n, void *stream);
 
+/* ---- temporal noise filter -----------------------------------------------------------
+ * Every other consumer of a displacement field makes new frames from it or judges the motion.  This one improves the frames the
+ * motion was measured on: a pixel is averaged with the pixels that show the same scene point in its neighbouring frames, each
+ * neighbour weighted per pixel by how well its 3 x 3 surroundings agree with the centre's (the patch test), because an average
+ * along a wrong vector is worse than no filter.  THE definition (tests/temporal_ref.py restates it in NumPy); after one float32
+ * product and one rounding per component it is all integers:
+ *
+ * INPUTS: a centre plane c of w x h pixels, u8, `channels` C in {1, 3} interleaved, pitch >= C w, any alignment; n_neighbours S in
+ *   1 .. OFX_TEMPORAL_MAX_NEIGHBOURS neighbours, neighbour k a plane n_k of the same w, h and C with a pitch of its own and a field
+ *   D_k: interleaved float32 (u, v), w x h, tightly packed, 8-byte aligned, IN PIXELS, on c's grid -- neighbour k at x + D_k(x) shows
+ *   what c shows at x: "pixel displacement" of the pair c -> n_k.  weights: uint16 [256] on the host, every entry <= 256, copied
+ *   into the launch; centre_weight wc in 1 .. 256.  A neighbour plane may be c itself or the plane of another neighbour; nothing
+ *   may overlap the destination.
+ * POSITION of neighbour k for pixel (x, y), with (u, v) = D_k(y, x): DEFINED when u and v are finite and |u|, |v| <= 1048576.0f (a
+ *   NaN fails).  qx = 32 x + (int64) rintf(32.0f * u), ties to even; qy likewise.  The product is an exact scaling, and a denormal
+ *   rounds to 0 whether it is kept or flushed: the definition does not depend on the denormal mode.  USABLE when defined and
+ *   0 <= qx <= 32 (w - 1) and 0 <= qy <= 32 (h - 1).
+ * PATCH     for (i, j) in {-1, 0, 1}^2 the neighbour's patch value N_k(i, j, ch) is VALUE of "affine frame warp" at the position
+ *   (clamp(qx + 32 i, 0, 32 (w - 1)), clamp(qy + 32 j, 0, 32 (h - 1))); where nothing clamps, the fraction is the same for all nine,
+ *   so they need 4 x 4 taps.  The centre's patch is c(clamp(x + i, 0, w - 1), clamp(y + j, 0, h - 1), ch).  SAD_k = sum |N_k - c|
+ *   over the 9 C values;  m_k = min(255, (SAD_k + 4) / 9) for C = 1 and min(255, (SAD_k + 13) / 27) for C = 3, integer division:
+ *   the rounded mean absolute difference.  w_k = weights[m_k] when the neighbour is usable at this pixel, else 0.
+ * VALUE     per channel  num = wc c + sum_k w_k N_k(0, 0, ch);  den = wc + sum_k w_k;  out = (2 num + den) / (2 den), integer
+ *   division, exact; den <= 1280, so it all fits 32 bits.  The geometry, the SADs and the weights are formed once per pixel and
+ *   applied to every channel.
+ * STATS     d_stats (may be NULL; 8-byte aligned): int64 [8], zeroed by the call on the stream first.  [0] w h;  [1 + k] pixels
+ *   where neighbour k is not usable (0 for k >= S);  [5] pixels with sum_k w_k = 0 (the output is c);  [6] sum |out - c| over pixels
+ *   and channels;  [7] sum over pixels of sum_k w_k.  Integers: they depend on no order, tile or batch.
+ * Consequences: all-zero weights give a copy of c, byte for byte; zero fields with n_k = c give c; a whole-pixel field makes
+ * N_k(0, 0) a shifted copy of n_k exactly; appending a neighbour whose weight is 0 everywhere changes nothing but [1 + k]; no tap
+ * reads outside the (h - 1) pitch + C w bytes of a plane or the w h 8 bytes of a field, whatever the fields hold; the bytes of a
+ * destination row beyond column C w - 1 stay untouched.
+ * Not here: a radius above one frame on either side of a field (it needs composed fields; the caller may pass them), a recursive
+ * filter, planar colour.
+ *
+ * ofx_temporal_filter: 1 <= n <= OFX_STREAM_MAX_BATCH items of any sizes, channel counts and neighbour counts in ONE launch (plus
+ * the memsets of the stats).  The descriptors embed everything: no host pointer has to stay alive.  Neighbours k >= S are not
+ * looked at.  Refused with OFX_E_INVALID and a message naming the call, the item and, for a neighbour, the neighbour, before
+ * anything is enqueued: null items or prm; n out of range, n_neighbours outside 1 .. 4; a null plane or field among the first S, a
+ * null d_centre or d_dst; channels not 1 or 3; w or h outside 1 .. 2^16, w h >= 2^28, a plane of 2^31 bytes or more; a pitch below
+ * its row; a field or d_stats not 8-byte aligned; a weight above 256, centre_weight outside 1 .. 256, a non-zero reserved word;
+ * d_dst overlapping any input plane, field or d_stats. */
+#define OFX_TEMPORAL_MAX_NEIGHBOURS 4
+typedef struct ofx_temporal_neighbour {
+    const uint8_t *d_plane;
+    int pitch, pad;
+    const float *d_field;
+} ofx_temporal_neighbour;
+typedef struct ofx_temporal_desc {
+    ofx_temporal_neighbour neighbour[OFX_TEMPORAL_MAX_NEIGHBOURS];
+    int n_neighbours;
+    int w, h, channels;
+    const uint8_t *d_centre;
+    int centre_pitch, dst_pitch;
+    uint8_t *d_dst;
+    int64_t *d_stats; /* may be NULL */
+} ofx_temporal_desc;
+typedef struct ofx_temporal_params {
+    uint16_t weights[256];
+    int centre_weight;
+    int reserved; /* 0 */
+} ofx_temporal_params;
+int ofx_temporal_filter(const ofx_temporal_desc *items, int n, const ofx_temporal_params *prm, void *stream);
+
 /* ---- layout helpers ------------------------------------------------------ */
 int ofx_extract_ch0(const uint8_t *d_src3, uint8_t *d_dst1, int w, int h, int dst_pitch, void *stream);
 int ofx_replicate_3ch(const uint8_t *d_src1, int src_pitch, uint8_t *d_dst3, int w, int h, void *stream);
