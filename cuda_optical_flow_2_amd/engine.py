@@ -2083,7 +2083,8 @@ def temporal_filter(centre, neighbours, fields, weights, centre_weight: int = 25
     or a float sigma for temporal_weights(sigma); centre_weight: 1 .. 256.  Returns the filtered frame and, with return_stats,
     int64 [8]: (pixels, pixels where neighbour 0 / 1 / 2 / 3 is not usable, pixels left as they were for want of any weight, sum of
     |out - centre|, sum of the weights given).  Arrays in give arrays out, CUDA tensors give CUDA tensors.
-    One neighbouring frame on either side of a field; no recursive filter, no planar colour."""
+    A field per neighbour: a neighbour two frames away takes a chained field (displacement_chain, chain_ring; denoise_rings(reach=2)
+    does so for a clip).  No recursive filter, no planar colour."""
     import torch
 
     neighbours, fields = list(neighbours), list(fields)
@@ -2127,8 +2128,113 @@ def _denoise_rings(frames, fwd, bwd, weights, centre_weight, return_stats):
     return (out, stats) if return_stats else out
 
 
-def _denoise_result(out, fwd, bwd, return_stats, return_displacements):
-    res = (out if isinstance(out, tuple) else (out,)) + ((fwd, bwd) if return_displacements else ())
+# ---- displacement chain ----------------------------------------------------------------------------------------------------------
+
+CHAIN_MAX_LINKS = 4                                    # OFX_CHAIN_MAX_LINKS
+
+
+def _chain_launch(items):
+    """ofx_displacement_chain on items (link addresses, w, h, dst, mask or None, stats or None), one launch: dst a float32 CUDA
+    tensor [h, w, 2], mask uint8 [h, w] with contiguous pixels, stats int64 [4].  It passes addresses: the tensors must outlive it."""
+    from .lib import ChainDesc
+
+    descs = (ChainDesc * len(items))()
+    for d, (links, w, h, dst, mask, stats) in zip(descs, items):
+        assert 2 <= len(links) <= CHAIN_MAX_LINKS, "2 .. 4 links"
+        for k, ptr in enumerate(links):
+            d.d_link[k] = ptr
+        d.n_links, d.w, d.h, d.d_dst = len(links), w, h, dst.data_ptr()
+        if mask is not None:
+            d.d_mask, d.mask_pitch = mask.data_ptr(), max(int(mask.stride(0)), w)
+        if stats is not None:
+            d.d_stats = stats.data_ptr()
+    check(_lib.load().ofx_displacement_chain(descs, len(items), _stream_ptr()), "ofx_displacement_chain")
+
+
+def displacement_chain(links, return_mask: bool = False, return_stats: bool = False):
+    """The displacement of a frame towards the frame len(links) frames on, from the displacements of the consecutive pairs between
+    them ("displacement chain" in include/ofx.h; ofx_displacement_chain, one launch): D_ac(x) = D_ab(x) + D_bc(x + D_ab(x)), folded
+    over 2 .. 4 links.  links: float32 [H, W, 2] each, in pixels, link j the displacement of frame j -> frame j + 1 on frame j's
+    grid; all host arrays or all CUDA tensors.  Returns the chained field, float32 [H, W, 2] -- where the path leaves the frame or
+    is not defined, both components are the NaN 0x7fc00000, which the temporal filter and the frame interpolation treat as not
+    defined -- and, with return_mask, uint8 [H, W] (0 ok, 2 leaves the frame, 3 undefined), with return_stats, int64 [4]: (pixels,
+    pixels of class 2, of class 3, of class 0).  Arrays in give arrays out, CUDA tensors give CUDA tensors."""
+    import torch
+
+    links = list(links)
+    assert 2 <= len(links) <= CHAIN_MAX_LINKS, "2 .. 4 links"
+    on_device = all(isinstance(s, torch.Tensor) and s.is_cuda for s in links)
+    assert on_device or not any(isinstance(s, torch.Tensor) for s in links), "all host arrays or all CUDA tensors"
+    # (a copy of a host array: the caller's may be read-only)
+    flds = [(s if on_device else torch.from_numpy(np.array(s, dtype=np.float32, order="C")).cuda()).contiguous() for s in links]
+    h, w = int(flds[0].shape[0]), int(flds[0].shape[1])
+    assert all(f.dtype == torch.float32 and tuple(f.shape) == (h, w, 2) for f in flds), "links: float32 [H, W, 2], one size"
+    dst = torch.empty_like(flds[0])
+    mask = torch.empty((h, w), dtype=torch.uint8, device=dst.device) if return_mask else None
+    stats = torch.empty(4, dtype=torch.int64, device=dst.device) if return_stats else None
+    _chain_launch([([f.data_ptr() for f in flds], w, h, dst, mask, stats)])
+    res = [dst] + ([mask] if return_mask else []) + ([stats] if return_stats else [])
+    if not on_device:
+        torch.cuda.synchronize()
+        res = [t.cpu().numpy() for t in res]
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+def chain_ring(ring, span: int):
+    """The displacements over `span` frames of a ring of consecutive pairs: ring a float32 CUDA tensor [P, H, W, 2], tightly packed,
+    ring[p] the displacement of frame p -> p + 1 (a ring of a REVERSED run chains the same way: it is a run of consecutive pairs
+    too); span in 2 .. 4 <= P.  Returns [P - span + 1, H, W, 2]: entry p is the chain of ring[p .. p + span - 1], the displacement
+    of frame p -> p + span.  Up to 16 entries per ofx_displacement_chain launch, the links read in place out of the ring."""
+    import torch
+
+    assert isinstance(ring, torch.Tensor) and ring.is_cuda and ring.dtype == torch.float32 and ring.dim() == 4 and ring.shape[3] == 2 and ring.is_contiguous(), \
+        "ring: a float32 CUDA tensor [P, H, W, 2], tightly packed"
+    span = int(span)
+    P, H, W = int(ring.shape[0]), int(ring.shape[1]), int(ring.shape[2])
+    assert 2 <= span <= CHAIN_MAX_LINKS and span <= P, "span: 2 .. 4 and at most the ring's pairs"
+    out = torch.empty((P - span + 1, H, W, 2), dtype=torch.float32, device=ring.device)
+    slot = _slot_ptrs(ring)
+    for p0 in range(0, P - span + 1, 16):
+        _chain_launch([(slot[p:p + span], W, H, out[p], None, None) for p in range(p0, min(p0 + 16, P - span + 1))])
+    return out
+
+
+def denoise_rings(frames, fwd, bwd, sigma, reach: int = 1, centre_weight: int = 256, return_stats: bool = False):
+    """Every frame of a clip filtered with its neighbours up to `reach` frames away, from the clip's two level-0 displacement rings
+    in the convention of _denoise_rings (fwd[p]: frame p -> p+1; bwd[N-2-p]: frame p+1 -> p) -- what
+    video_denoise(..., return_displacements=True) returns.  frames: uint8 CUDA tensor [N, H, W] or [N, H, W, 3]; sigma: the noise's
+    standard deviation in grey levels, or a table uint16 [256].  reach=1 is _denoise_rings.  reach=2 (N >= 3) chains the rings first
+    (fwd2 = chain_ring(fwd, 2): frame p -> p+2; bwd2 = chain_ring(bwd, 2): bwd2[N-3-p] is frame p+2 -> p), and frame f takes, in
+    this order and skipping what lies outside the clip, frame f-1 with bwd[N-1-f], f+1 with fwd[f], f-2 with bwd2[N-1-f] and f+2
+    with fwd2[f]: the stats slots 1 and 2 keep their meaning for interior frames, and where a chained vector is not defined the
+    neighbour is not usable.  Returns the filtered clip and, with return_stats, int64 [N, 8] (temporal_filter's, per frame)."""
+    assert reach in (1, 2), "reach: 1 or 2 frames on either side"
+    if reach == 1:
+        return _denoise_rings(frames, fwd, bwd, sigma, centre_weight, return_stats)
+    return _denoise_reach2(frames, fwd, bwd, chain_ring(fwd, 2), chain_ring(bwd, 2), sigma, centre_weight, return_stats)
+
+
+def _denoise_reach2(frames, fwd, bwd, fwd2, bwd2, weights, centre_weight, return_stats):
+    """denoise_rings(reach=2) on the rings and their two-link chains"""
+    import torch
+
+    N, H, W = _clip_shape(frames)
+    assert N >= 3 and int(fwd2.shape[0]) == N - 2 == int(bwd2.shape[0]), "reach 2: three frames or more"
+    prm = _temporal_params(weights, centre_weight)
+    out = torch.empty(tuple(frames.shape), dtype=torch.uint8, device=frames.device)
+    stats = torch.empty((N, 8), dtype=torch.int64, device=frames.device) if return_stats else None
+    for f0 in range(0, N, 16):
+        items = []
+        for f in range(f0, min(f0 + 16, N)):
+            near = ([(frames[f - 1], bwd[N - 1 - f])] if f >= 1 else []) + ([(frames[f + 1], fwd[f])] if f + 1 < N else []) + \
+                   ([(frames[f - 2], bwd2[N - 1 - f])] if f >= 2 else []) + ([(frames[f + 2], fwd2[f])] if f + 2 < N else [])
+            items.append((frames[f], [p for p, _ in near], [d for _, d in near], out[f], stats[f] if return_stats else None))
+        _temporal_launch(items, prm)
+    return (out, stats) if return_stats else out
+
+
+def _denoise_result(out, fwd, bwd, return_stats, return_displacements, chained=()):
+    res = (out if isinstance(out, tuple) else (out,)) + ((fwd, bwd) + tuple(chained) if return_displacements else ())
     return res[0] if len(res) == 1 else res
 
 
@@ -2142,8 +2248,8 @@ def video_denoise(frames, levels: int, window: int, sigma, mode: str = "lk_float
     frames: uint8 CUDA tensor [N, H, W], N >= 2, unit column stride.  sigma: the noise's standard deviation in grey levels
     (temporal_weights(sigma) is the table), or a table uint16 [256].  Returns the filtered clip, uint8 [N, H, W]; return_stats
     appends int64 [N, 8] (temporal_filter's, per frame; the end frames have one neighbour), return_displacements the two rings as
-    video_interpolate does.  One frame on either side: a longer reach needs composed fields; no recursive filter; not a stage of
-    the stream pipeline itself."""
+    video_interpolate does.  One frame on either side here; two with engine.denoise_rings(frames, fwd, bwd, sigma, reach=2) on the
+    returned rings, which chains them (engine.chain_ring).  No recursive filter; not a stage of the stream pipeline itself."""
     assert frames.dim() == 3, "video_denoise: grey clips only, uint8 [N, H, W] (a colour clip [N, H, W, 3] goes through video_denoise_dense)"
     frames, N, H, W = _interp_clip(frames, 2)
     rings = []
@@ -2158,11 +2264,14 @@ def video_denoise(frames, levels: int, window: int, sigma, mode: str = "lk_float
 
 def video_denoise_dense(frames, levels: int, window: int, sigma, iters: int = 3, min_det: float = 1.0, max_px: Optional[float] = None,
                         median: int = 0, mode: str = "lk_float", centre_weight: int = 256, return_stats: bool = False,
-                        return_displacements: bool = False):
+                        return_displacements: bool = False, reach: int = 1):
     """video_denoise with the displacements of the coarse-to-fine dense flow (_dense_ring at level 0, forwards and in reverse frame
     order, as video_interpolate_dense), for a grey clip [N, H, W] or an interleaved colour clip [N, H, W, 3]; a colour clip gets
     its flow from the channel average, made on the device, and all three channels of a pixel share one geometry and one set of
-    weights.  median as video_displacement_dense's; the other arguments and the results as video_denoise's."""
+    weights.  median as video_displacement_dense's; the other arguments and the results as video_denoise's.  reach=2 (N >= 3)
+    filters every frame with up to two frames on either side, as denoise_rings(reach=2) does, through the rings chained over two
+    frames ("displacement chain" in include/ofx.h); return_displacements then appends fwd2 and bwd2 after fwd and bwd."""
+    assert reach in (1, 2), "reach: 1 or 2 frames on either side"
     if frames.dim() == 4:
         frames, N, H, W = _interp_clip_colour(frames, 2)
         grey = _grey_clip(frames)
@@ -2171,5 +2280,9 @@ def video_denoise_dense(frames, levels: int, window: int, sigma, iters: int = 3,
         grey = frames
     fwd = _dense_ring(grey, list(range(N)), levels, window, iters, min_det, max_px, 0, mode, None, median)
     bwd = _dense_ring(grey, list(range(N - 1, -1, -1)), levels, window, iters, min_det, max_px, 0, mode, None, median)
+    if reach == 2:
+        fwd2, bwd2 = chain_ring(fwd, 2), chain_ring(bwd, 2)
+        out = _denoise_reach2(frames, fwd, bwd, fwd2, bwd2, sigma, centre_weight, return_stats)
+        return _denoise_result(out, fwd, bwd, return_stats, return_displacements, (fwd2, bwd2))
     out = _denoise_rings(frames, fwd, bwd, sigma, centre_weight, return_stats)
     return _denoise_result(out, fwd, bwd, return_stats, return_displacements)

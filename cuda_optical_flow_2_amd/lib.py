@@ -132,6 +132,15 @@ class TemporalParams(C.Structure):
     _fields_ = [("weights", C.c_uint16 * 256), ("centre_weight", C.c_int), ("reserved", C.c_int)]
 
 
+OFX_CHAIN_MAX_LINKS = 4
+
+
+class ChainDesc(C.Structure):
+    """ofx_chain_desc (include/ofx.h, "displacement chain")"""
+    _fields_ = [("d_link", C.c_void_p * OFX_CHAIN_MAX_LINKS), ("n_links", C.c_int), ("w", C.c_int), ("h", C.c_int), ("mask_pitch", C.c_int),
+                ("d_dst", C.c_void_p), ("d_mask", C.c_void_p), ("d_stats", C.c_void_p)]
+
+
 class LkDesc(C.Structure):
     """ofx_lk_desc (include/ofx.h): one level of an ofx_lk_levels / ofx_corner_flows launch"""
     _fields_ = [("d_prev", C.c_void_p), ("d_next", C.c_void_p), ("geom", Geom), ("d_flow", C.c_void_p), ("flow_row0", C.c_int),
@@ -244,6 +253,7 @@ _SIGS = {
     "ofx_warp_perspective": [C.POINTER(WarpPerspDesc), _i, _vp],
     "ofx_warp_mosaic": [C.POINTER(MosaicDesc), _i, _vp],
     "ofx_temporal_filter": [C.POINTER(TemporalDesc), _i, C.POINTER(TemporalParams), _vp],
+    "ofx_displacement_chain": [C.POINTER(ChainDesc), _i, _vp],
     "ofx_homography_compose": [_vp, _vp, _vp],
     "ofx_homography_invert": [_vp, _vp],
     "ofx_homography_normalize": [_vp, _vp],

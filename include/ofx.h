@@ -1011,8 +1011,8 @@ int ofx_warp_mosaic(const ofx_mosaic_desc *items, int n, void *stream);
  * N_k(0, 0) a shifted copy of n_k exactly; appending a neighbour whose weight is 0 everywhere changes nothing but [1 + k]; no tap
  * reads outside the (h - 1) pitch + C w bytes of a plane or the w h 8 bytes of a field, whatever the fields hold; the bytes of a
  * destination row beyond column C w - 1 stay untouched.
- * Not here: a radius above one frame on either side of a field (it needs composed fields; the caller may pass them), a recursive
- * filter, planar colour.
+ * Not here: a reach above one frame per field -- a neighbour two frames away takes a composed field, which "displacement chain"
+ * below makes (engine.denoise_rings(reach=2) feeds all four slots that way); a recursive filter; planar colour.
  *
  * ofx_temporal_filter: 1 <= n <= OFX_STREAM_MAX_BATCH items of any sizes, channel counts and neighbour counts in ONE launch (plus
  * the memsets of the stats).  The descriptors embed everything: no host pointer has to stay alive.  Neighbours k >= S are not
@@ -1042,6 +1042,61 @@ typedef struct ofx_temporal_params {
     int reserved; /* 0 */
 } ofx_temporal_params;
 int ofx_temporal_filter(const ofx_temporal_desc *items, int n, const ofx_temporal_params *prm, void *stream);
+
+/* ---- displacement chain -----------------------------------------------------------------
+ * Every producer of a displacement field here gives the field of two CONSECUTIVE frames, and every consumer takes "a field in
+ * pixels on the first frame's grid".  This is the operator between them for frames that are further apart: the concatenation of
+ * two fields, D_ac(x) = D_ab(x) + D_bc(x + D_ab(x)) -- follow the first vector, read the second field bilinearly there, add --
+ * folded over up to OFX_CHAIN_MAX_LINKS fields.  It has the gather of "forward-backward consistency", but it writes a field
+ * instead of judging one.  THE definition (tests/chain_ref.py restates it in NumPy):
+ *
+ * INPUTS: n_links L in 2 .. OFX_CHAIN_MAX_LINKS fields D_0 .. D_{L-1}, each interleaved (u, v) float32, w x h, tightly packed,
+ *   8-byte aligned, IN PIXELS: D_j is the displacement of frame j -> frame j + 1 on frame j's grid ("pixel displacement").  All
+ *   fields of an item have the same size.
+ * Every float32 operation is rounded once, nothing is fused, denormals are kept.
+ * STEP   for pixel (x, y): A_0 = D_0(y, x).  For j = 1 .. L - 1, with (u, v) = A_{j-1}:
+ *   1. px = (float)x + u, py = (float)y + v.
+ *   2. unless |px| <= 1e9 && |py| <= 1e9 (a NaN fails): class 3, UNDEFINED.  Stop.
+ *   3. else if px < 0 || px > (float)(w-1) || py < 0 || py > (float)(h-1): class 2, LEAVES -- the path leaves the frame.  Nothing
+ *      is clamped and D_j is not read.  Stop.
+ *   4. else x0, y0, fx, fy, x1 = min(x0+1, w-1), y1 = min(y0+1, h-1) exactly as in steps 4 and 5 of "forward-backward
+ *      consistency": in the last column the right tap IS the pixel itself, whatever lies behind it in memory; likewise in the
+ *      last row.  Per component of D_j, with b00 = D_j(y0,x0), b01 = D_j(y0,x1), b10 = D_j(y1,x0), b11 = D_j(y1,x1):
+ *        a = b00 + fx*(b01 - b00);  c = b10 + fx*(b11 - b10);  r = a + fy*(c - a)
+ *   5. A_j = (u + r_u, v + r_v).  Unless both components satisfy |.| <= FLT_MAX: class 3.  Stop.
+ *   A pixel that gets through every link has class 0, OK.
+ * OUTPUTS
+ *   dst    a float32 field like the inputs: A_{L-1} for class 0.  For classes 2 and 3 BOTH components are the bit pattern
+ *          0x7fc00000; the output never holds an Inf or any other NaN.  "temporal noise filter" and "frame interpolation" treat
+ *          such a vector as not defined.
+ *   mask   (may be absent) u8, rows mask_pitch >= w apart: the class.  Bytes beyond column w - 1 are left untouched.
+ *   stats  (may be absent; 8-byte aligned) int64 [4] = [w h, pixels of class 2, of class 3, of class 0], zeroed by the call on the
+ *          stream first: a slot needs no initialisation and carries nothing from one call to the next.  Integers: they depend on
+ *          no order, tile or batch.
+ * Consequences: a chain of L links equals L - 1 two-link calls folded from the left, chain(chain(D_0, D_1), D_2) .., bit for bit,
+ * the dead pixels included (a 0x7fc00000 vector fails step 2 and stays what it is); whole-pixel constant fields add exactly
+ * wherever the path stays inside; no tap reads outside the w h 8 bytes of a field, whatever the fields hold; an OK vector is finite.
+ * In place: d_dst may be exactly d_link[0] -- D_0 is read only at the pixel itself, by the thread that writes it, before the write.
+ * Not here: the inverse of a field, and chains of more than OFX_CHAIN_MAX_LINKS links in one call (fold them).
+ *
+ * ofx_displacement_chain: 1 <= n <= OFX_STREAM_MAX_BATCH items of any sizes and link counts in ONE launch (plus the memsets of the
+ * stats).  The descriptors embed everything: no host pointer has to stay alive.  Links k >= n_links are not looked at.  Refused
+ * with OFX_E_INVALID and a message naming the call, the item and, for a link, the link, before anything is enqueued: null items; n
+ * out of range; n_links outside 2 .. 4; a null link among the first L, a null d_dst; w or h < 1, w h >= 2^28; a link, d_dst or
+ * d_stats not 8-byte aligned; mask_pitch < w when d_mask is given; within an item, d_dst overlapping a link (other than being
+ * exactly link 0), d_mask overlapping a link, and d_dst, d_mask and d_stats overlapping each other. */
+#define OFX_CHAIN_MAX_LINKS 4
+#define OFX_CHAIN_OK 0
+#define OFX_CHAIN_LEAVES 2
+#define OFX_CHAIN_UNDEFINED 3
+typedef struct ofx_chain_desc {
+    const float *d_link[OFX_CHAIN_MAX_LINKS];
+    int n_links, w, h, mask_pitch;
+    float *d_dst;
+    uint8_t *d_mask;  /* may be NULL */
+    int64_t *d_stats; /* may be NULL; 4 values, overwritten */
+} ofx_chain_desc;
+int ofx_displacement_chain(const ofx_chain_desc *items, int n, void *stream);
 
 /* ---- layout helpers ------------------------------------------------------ */
 int ofx_extract_ch0(const uint8_t *d_src3, uint8_t *d_dst1, int w, int h, int dst_pitch, void *stream);
