@@ -1014,13 +1014,14 @@ int ofx_warp_mosaic(const ofx_mosaic_desc *items, int n, void *stream);
  * Not here: a reach above one frame per field -- a neighbour two frames away takes a composed field, which "displacement chain"
  * below makes (engine.denoise_rings(reach=2) feeds all four slots that way); a recursive filter; planar colour.
  *
- * ofx_temporal_filter: 1 <= n <= OFX_STREAM_MAX_BATCH items of any sizes, channel counts and neighbour counts in ONE launch (plus
- * the memsets of the stats).  The descriptors embed everything: no host pointer has to stay alive.  Neighbours k >= S are not
- * looked at.  Refused with OFX_E_INVALID and a message naming the call, the item and, for a neighbour, the neighbour, before
- * anything is enqueued: null items or prm; n out of range, n_neighbours outside 1 .. 4; a null plane or field among the first S, a
- * null d_centre or d_dst; channels not 1 or 3; w or h outside 1 .. 2^16, w h >= 2^28, a plane of 2^31 bytes or more; a pitch below
- * its row; a field or d_stats not 8-byte aligned; a weight above 256, centre_weight outside 1 .. 256, a non-zero reserved word;
- * d_dst overlapping any input plane, field or d_stats. */
+ * ofx_temporal_filter: 1 <= n <= OFX_STREAM_MAX_BATCH items of any sizes, channel counts and neighbour counts in ONE launch, behind
+ * the launches of the library's own kernel that zero the stats on the same stream: one per item that gave d_stats, no memset
+ * (Conventions: a call records kernel nodes only).  The descriptors embed everything: no host pointer has to stay alive.
+ * Neighbours k >= S are not looked at.  Refused with OFX_E_INVALID and a message naming the call, the item and, for a neighbour,
+ * the neighbour, before anything is enqueued: null items or prm; n out of range, n_neighbours outside 1 .. 4; a null plane or field
+ * among the first S, a null d_centre or d_dst; channels not 1 or 3; w or h outside 1 .. 2^16, w h >= 2^28, a plane of 2^31 bytes or
+ * more; a pitch below its row; a field or d_stats not 8-byte aligned; a weight above 256, centre_weight outside 1 .. 256, a
+ * non-zero reserved word; d_dst overlapping any input plane, field or d_stats. */
 #define OFX_TEMPORAL_MAX_NEIGHBOURS 4
 typedef struct ofx_temporal_neighbour {
     const uint8_t *d_plane;
@@ -1079,12 +1080,14 @@ int ofx_temporal_filter(const ofx_temporal_desc *items, int n, const ofx_tempora
  * In place: d_dst may be exactly d_link[0] -- D_0 is read only at the pixel itself, by the thread that writes it, before the write.
  * Not here: the inverse of a field, and chains of more than OFX_CHAIN_MAX_LINKS links in one call (fold them).
  *
- * ofx_displacement_chain: 1 <= n <= OFX_STREAM_MAX_BATCH items of any sizes and link counts in ONE launch (plus the memsets of the
- * stats).  The descriptors embed everything: no host pointer has to stay alive.  Links k >= n_links are not looked at.  Refused
- * with OFX_E_INVALID and a message naming the call, the item and, for a link, the link, before anything is enqueued: null items; n
- * out of range; n_links outside 2 .. 4; a null link among the first L, a null d_dst; w or h < 1, w h >= 2^28; a link, d_dst or
- * d_stats not 8-byte aligned; mask_pitch < w when d_mask is given; within an item, d_dst overlapping a link (other than being
- * exactly link 0), d_mask overlapping a link, and d_dst, d_mask and d_stats overlapping each other. */
+ * ofx_displacement_chain: 1 <= n <= OFX_STREAM_MAX_BATCH items of any sizes and link counts in ONE launch, behind the launches of
+ * the library's own kernel that zero the stats on the same stream: one per run of d_stats slots that follow one another in memory
+ * in the items' order, no memset (Conventions: a call records kernel nodes only); the slot of an item that gave none is not
+ * touched, wherever it lies.  The descriptors embed everything: no host pointer has to stay alive.  Links k >= n_links are not
+ * looked at.  Refused with OFX_E_INVALID and a message naming the call, the item and, for a link, the link, before anything is
+ * enqueued: null items; n out of range; n_links outside 2 .. 4; a null link among the first L, a null d_dst; w or h < 1, w h >=
+ * 2^28; a link, d_dst or d_stats not 8-byte aligned; mask_pitch < w when d_mask is given; within an item, d_dst overlapping a link
+ * (other than being exactly link 0), d_mask overlapping a link, and d_dst, d_mask and d_stats overlapping each other. */
 #define OFX_CHAIN_MAX_LINKS 4
 #define OFX_CHAIN_OK 0
 #define OFX_CHAIN_LEAVES 2

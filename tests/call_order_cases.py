@@ -23,6 +23,8 @@ import functools
 
 import numpy as np
 
+import chain_cases as KC
+import chain_ref as KR
 import consistency_ref as CR
 import dense_ref as D
 import fit_motion_ref as FR
@@ -37,6 +39,8 @@ import mosaic_cases as MC
 import mosaic_ref as MZ
 import motion_ref as MR
 import sampled_ref as SR
+import temporal_cases as TC
+import temporal_ref as TR
 import texture_ref as T
 import warp_affine_ref as WA
 import warp_persp_ref as WP
@@ -940,6 +944,259 @@ class Frontend(Recipe):
         return rc
 
 
+# ---- displacement chain ---------------------------------------------------------------------------------------------------------------
+# (w, h, links, mask: None / "loose" / "odd", d_stats given, in place): six items, ONE launch of the batched grid
+CHAIN_GEOM = [(257, 40, 3, "odd", True, False), (67, 33, 2, "loose", False, True), (130, 9, 4, None, True, False), (5, 3, 2, "odd", True, True),
+              (1, 1, 2, None, False, False), (67, 33, 4, "loose", True, False)]
+CHAIN_KINDS = ["borders", "nonfinite", "edge", "inverse", "integers", "overflow"]
+
+
+def chain_items(seed=0, turn=0):
+    """the table's items (links, mask, stats given, in place), item i with kind i + turn"""
+    return [(KC.links(CHAIN_KINDS[(i + turn) % len(CHAIN_KINDS)], w, h, n, seed), mask, given, there) for i, (w, h, n, mask, given, there) in enumerate(CHAIN_GEOM)]
+
+
+class Chain(Recipe):
+    """ofx_displacement_chain on items (links, mask, stats given, in place).  The stats slots are consecutive in memory (ONE Guarded
+    without a gap between its slots), item i at slot slots[i]: zero_stats merges slots that follow one another into one launch, and
+    the slot of an item that gave NULL keeps its 0x5A.  An in-place item has ONE Guarded that is link 0 and d_dst, loaded with
+    link 0 through InOut; with carried, nothing is loaded: link 0 is what the call before left there.
+    The table's 1 x 1 item leaves the frame whatever the seed (only a link 0 of exactly zero stays): its dst is the dead vector in the
+    row, the variant and the second instance alike, so it never tells the three apart in a replay or between two calls in flight.
+    What it holds is the store of a one-pixel item (the guard bytes around it) and its stats slot, which was not given and keeps
+    its 0x5A; tests/test_call_order_cases.py asserts that it is the dead vector in all three."""
+    entry = "ofx_displacement_chain"
+
+    def __init__(self, name, items, slots=None, carried=False):
+        super().__init__()
+        self.name, self.items, self.carried = name, items, carried
+        self.slots = list(range(len(items))) if slots is None else list(slots)
+        res = [KR.chain(list(links)) for links, _, _, _ in items]
+        stats = np.full((len(items), 1, 4), COUNTS_LEFT, np.int64)
+        for i, ((links, mask, given, there), (dst, cls, st)) in enumerate(zip(items, res)):
+            h, w, _ = links[0].shape
+            self.want[f"dst{i}"] = dst.reshape(1, h, 2 * w)
+            if mask is not None:
+                self.want[f"mask{i}"] = cls.reshape(1, h, w)
+            if given:
+                stats[self.slots[i], 0] = st
+        self.want["stats"] = stats
+        self.end = res[0][0]
+        self.reach = dict(sizes=[it[0][0].shape[1::-1] for it in items], links=[len(it[0]) for it in items], masks=[it[1] for it in items],
+                          given=[it[2] for it in items], there=[it[3] for it in items], stats=[r[2].tolist() for r in res])
+
+    def branches(self):
+        r = self.reach
+        return dict(sizes=r["sizes"], links=r["links"], masks=r["masks"], given=r["given"], there=r["there"], slots=self.slots,
+                    classes=[[c > 0 for c in s[1:]] for s in r["stats"]])
+
+    def stage(self, torch, share=None):
+        self.ins, self.loads, self.rows, self.outs = [], [], [], {}
+        for i, (links, mask, given, there) in enumerate(self.items):
+            h, w, _ = links[0].shape
+            row = [None if there and k == 0 else In(torch, f, 2 if (i + k) % 3 else 6) for k, f in enumerate(links)]     # 8 or 24 bytes in: never 16
+            self.ins += [t for t in row if t is not None]
+            self.rows.append(row)
+            if share is None:
+                self.outs[f"dst{i}"] = Guarded(np.float32, 1, h, 2 * w, 2 * w, 2 + 4 * (i % 2))
+                if mask is not None:
+                    self.outs[f"mask{i}"] = Guarded(np.uint8, 1, h, w, (w + 11) & ~3, 4) if mask == "loose" else Guarded(np.uint8, 1, h, w, (w + 5) | 1, 1 + 2 * (i % 2))
+            else:
+                self.outs.update({k: share.outs[k] for k in (f"dst{i}", f"mask{i}") if k in self.want})
+            if there and not self.carried:
+                self.loads.append(InOut(torch, self.outs[f"dst{i}"], links[0]))
+        self.outs["stats"] = Guarded(np.int64, len(self.items), 1, 4, 4, 1, 4) if share is None else share.outs["stats"]
+        self.works = []
+
+    def launch(self, stream):
+        descs = (L.ChainDesc * len(self.items))()
+        for i, (links, mask, given, there) in enumerate(self.items):
+            d, dst = descs[i], self.outs[f"dst{i}"]
+            h, w, _ = links[0].shape
+            for k, t in enumerate(self.rows[i]):
+                d.d_link[k] = dst.ptr if t is None else t.ptr
+            d.n_links, d.w, d.h, d.d_dst = len(links), w, h, dst.ptr
+            d.d_mask, d.mask_pitch = (self.outs[f"mask{i}"].ptr, self.outs[f"mask{i}"].pitch) if mask is not None else (None, -1)
+            d.d_stats = self.outs["stats"].slot(self.slots[i]) if given else None
+        rc = self.lib().ofx_displacement_chain(descs, len(self.items), stream)
+        wipe(descs)
+        return rc
+
+
+# ---- temporal noise filter ------------------------------------------------------------------------------------------------------------
+# (w, h, channels, neighbours, field kind, same, own, d_stats given): six items, which take the 16-item instance of csrc/temporal.hip
+TEMPORAL_GEOM = [(131, 9, 1, 4, "special", False, False, True), (67, 9, 3, 2, "ramp", False, False, True), (5, 3, 1, 1, "edge", False, False, False),
+                 (67, 9, 1, 3, "random", True, False, True), (3, 2, 3, 2, "whole", False, True, False), (131, 9, 3, 3, "random", False, False, True)]
+
+
+def temporal_items(table, wc, base=0, rows=range(len(TEMPORAL_GEOM))):
+    """temporal_cases.case(...) + (stats given,) of the table's rows, the item at position i of the call with seed base + 2 i"""
+    out = []
+    for pos, row in enumerate(rows):
+        w, h, ch, S, kind, same_, own, given = TEMPORAL_GEOM[row]
+        out.append(TC.case(w, h, ch, S, kind, table, wc, seed=base + 2 * pos, same=same_, own=own) + (given,))
+    return out
+
+
+class Temporal(Recipe):
+    """ofx_temporal_filter on items (name, centre, planes, fields, table, centre weight, stats given), one table for the call.  A plane
+    that IS the centre or an earlier plane (the same array) is staged once.  Pitches are odd, so that the rows of a plane start at
+    every address mod 4.  The stats slot of an item that gave NULL keeps its 0x5A."""
+    entry = "ofx_temporal_filter"
+
+    def __init__(self, name, items):
+        super().__init__()
+        self.name, self.items = name, items
+        self.weights, self.wc = np.asarray(items[0][4]), int(items[0][5])
+        with np.errstate(all="ignore"):
+            res = [TR.temporal_filter(c, planes, fields, self.weights, self.wc) for _, c, planes, fields, _, _, _ in items]
+        stats = np.full((len(items), 1, 8), COUNTS_LEFT, np.int64)
+        for i, (it, (out, st)) in enumerate(zip(items, res)):
+            self.want[f"dst{i}"] = out.reshape(1, out.shape[0], -1)
+            if it[6]:
+                stats[i, 0] = st
+        self.want["stats"] = stats
+        self.reach = dict(sizes=[it[1].shape[1::-1] for it in items], channels=[3 if it[1].ndim == 3 else 1 for it in items], neighbours=[len(it[2]) for it in items],
+                          given=[it[6] for it in items], stats=[r[1].tolist() for r in res], same=[len(it[2]) > 1 and it[2][1] is it[2][0] for it in items],
+                          own=[it[2][0] is it[1] for it in items])
+
+    def branches(self):
+        r = self.reach
+        px = [w * h for w, h in r["sizes"]]
+        return dict(sizes=r["sizes"], channels=r["channels"], neighbours=r["neighbours"], given=r["given"], same=r["same"], own=r["own"],
+                    table=self.weights.tolist(), wc=self.wc, instance=1 if len(self.items) == 1 else 16,
+                    some=[[0 < u < p for u in s[1:1 + S]] for s, p, S in zip(r["stats"], px, r["neighbours"])], filled=[[v > 0 for v in s[5:]] for s in r["stats"]])
+
+    def stage(self, torch, share=None):
+        self.ins, self.staged, self.outs = [], [], {}
+        for i, (_, centre, planes, fields, _, _, given) in enumerate(self.items):
+            h, w = centre.shape[:2]
+            ch = 3 if centre.ndim == 3 else 1
+            made = {}
+
+            def plane_of(a, k):
+                if id(a) not in made:
+                    made[id(a)] = In.plane(torch, a.reshape(h, ch * w), (ch * w + 4 + 2 * ((i + k) % 3)) | 1, 1 + (i + k) % 4, 0xEE)
+                    self.ins.append(made[id(a)])
+                return made[id(a)]
+
+            cen = plane_of(centre, 0)
+            nbs = [plane_of(p, 1 + k) for k, p in enumerate(planes)]
+            flds = [In(torch, f, 2 if (i + k) % 3 else 6) for k, f in enumerate(fields)]
+            self.ins += flds
+            self.staged.append((cen, nbs, flds))
+            self.outs[f"dst{i}"] = Guarded(np.uint8, 1, h, ch * w, ch * w + 3 * i + 7, 1 + 2 * (i % 2) + (i % 4 == 3)) if share is None else share.outs[f"dst{i}"]
+        self.outs["stats"] = Guarded(np.int64, len(self.items), 1, 8, 8, 1) if share is None else share.outs["stats"]
+        self.works = []
+
+    def launch(self, stream):
+        descs = (L.TemporalDesc * len(self.items))()
+        for i, (_, centre, planes, fields, _, _, given) in enumerate(self.items):
+            d, (cen, nbs, flds), dst = descs[i], self.staged[i], self.outs[f"dst{i}"]
+            for k, (p, f) in enumerate(zip(nbs, flds)):
+                s = d.neighbour[k]
+                s.d_plane, s.pitch, s.pad, s.d_field = p.ptr, p.pitch, 0, f.ptr
+            d.n_neighbours, d.w, d.h, d.channels = len(planes), centre.shape[1], centre.shape[0], 3 if centre.ndim == 3 else 1
+            d.d_centre, d.centre_pitch, d.d_dst, d.dst_pitch = cen.ptr, cen.pitch, dst.ptr, dst.pitch
+            d.d_stats = self.outs["stats"].slot(i) if given else None
+        prm = temporal_params(self.weights, self.wc)
+        rc = self.lib().ofx_temporal_filter(descs, len(self.items), C.byref(prm), stream)
+        wipe(descs, prm)
+        return rc
+
+
+def temporal_params(table, wc):
+    prm = L.TemporalParams()
+    prm.weights = (C.c_uint16 * 256)(*[int(v) for v in table])
+    prm.centre_weight, prm.reserved = int(wc), 0
+    return prm
+
+
+# ---- the two together: engine.denoise_rings(reach=2) by ABI calls -------------------------------------------------------------------------
+DENOISE = (5, 67, 33, 10)           # (frames, w, h, sigma of the noise)
+
+
+def denoise_rings(seed):
+    """(fwd, bwd) float32 [4, h, w, 2] of the pan of temporal_cases.pan_clip (frame p shows the texture 3 p to the right and 2 p down:
+    a pixel of frame p is found (3, 2) to the left and up in frame p + 1, and as far to the right and down in frame p - 1) plus
+    N(0, 0.3); NaN in 3 % of fwd[1], +Inf in 3 % of bwd[2]: every two-link chain through them has vectors that are not defined"""
+    N, w, h, _ = DENOISE
+    rng = np.random.default_rng(900 + seed)
+    fwd = (np.array([-3.0, -2.0]) + rng.normal(0.0, 0.3, (N - 1, h, w, 2))).astype(F32)
+    bwd = (np.array([3.0, 2.0]) + rng.normal(0.0, 0.3, (N - 1, h, w, 2))).astype(F32)
+    fwd[1][rng.random((h, w, 2)) < 0.03] = np.nan
+    bwd[2][rng.random((h, w, 2)) < 0.03] = np.inf
+    return fwd, bwd
+
+
+class Denoise(Recipe):
+    """engine.denoise_rings(reach=2) on a five-frame clip by ABI calls: ONE ofx_displacement_chain of six two-link items, which read
+    their links in place out of the two rings and write fwd2[0 .. 2] and bwd2[0 .. 2], then ONE ofx_temporal_filter of the five
+    frames, each with its neighbours in the engine's order (f - 1, f + 1, f - 2, f + 2, what lies outside the clip skipped), the far
+    fields pointing into the slots the chain is still writing when the filter is enqueued."""
+    entry = "ofx_temporal_filter"
+
+    def __init__(self, name, channels, seed, table=None, wc=256):
+        super().__init__()
+        N, w, h, sigma = DENOISE
+        self.name, self.channels, self.wc = name, channels, wc
+        self.weights = TR.weights_for(float(sigma)) if table is None else np.asarray(table)
+        self.frames = TC.pan_clip(N, w, h, channels, sigma, seed)[0]
+        self.fwd, self.bwd = denoise_rings(seed)
+        with np.errstate(all="ignore"):
+            res = KR.denoise_rings(self.frames, self.fwd, self.bwd, self.weights, 2, wc)
+        self.want = dict(fwd2=KR.chain_ring(self.fwd, 2).reshape(N - 2, h, 2 * w), bwd2=KR.chain_ring(self.bwd, 2).reshape(N - 2, h, 2 * w),
+                         frames=np.stack([r[0] for r in res]).reshape(N, h, channels * w), stats=np.stack([r[1] for r in res]).reshape(N, 1, 8))
+        self.reach = dict(stats=[r[1].tolist() for r in res], chains=[KR.chain([ring[p], ring[p + 1]])[2].tolist() for ring in (self.fwd, self.bwd) for p in range(N - 2)])
+
+    def branches(self):
+        r = self.reach
+        return dict(channels=self.channels, table=self.weights.tolist(), wc=self.wc, neighbours=[[v > 0 for v in s[1:5]] for s in r["stats"]],
+                    filled=[[v > 0 for v in s[5:]] for s in r["stats"]], chains=[[v > 0 for v in c[1:]] for c in r["chains"]])
+
+    def stage(self, torch, share=None):
+        N, w, h, _ = DENOISE
+        row = self.channels * w
+        self.planes = [In.plane(torch, f.reshape(h, row), (row + 4 + 2 * (i % 3)) | 1, 1 + i % 4, 0xEE) for i, f in enumerate(self.frames)]
+        self.rings = [In(torch, self.fwd, 2), In(torch, self.bwd, 6)]
+        self.ins = self.planes + self.rings
+        if share is None:
+            self.outs = dict(fwd2=Guarded(np.float32, N - 2, h, 2 * w, 2 * w, 2), bwd2=Guarded(np.float32, N - 2, h, 2 * w, 2 * w, 2),
+                             frames=Guarded(np.uint8, N, h, row, row + 9, 3), stats=Guarded(np.int64, N, 1, 8, 8, 1))
+        else:
+            self.outs = dict(share.outs)
+        self.works = []
+
+    def launch(self, stream):
+        N, w, h, _ = DENOISE
+        o, field = self.outs, 8 * w * h
+        chains = (L.ChainDesc * (2 * (N - 2)))()
+        for j, (ring, out) in enumerate(zip(self.rings, (o["fwd2"], o["bwd2"]))):
+            for p in range(N - 2):
+                d = chains[(N - 2) * j + p]
+                d.d_link[0], d.d_link[1] = ring.ptr + p * field, ring.ptr + (p + 1) * field
+                d.n_links, d.w, d.h, d.mask_pitch, d.d_dst, d.d_mask, d.d_stats = 2, w, h, -1, out.slot(p), None, None
+        rc = self.lib().ofx_displacement_chain(chains, len(chains), stream)
+        wipe(chains)
+        if rc:
+            return rc
+        fwd, bwd = (r.ptr for r in self.rings)
+        descs = (L.TemporalDesc * N)()
+        for f in range(N):
+            near = ([(f - 1, bwd + (N - 1 - f) * field)] if f >= 1 else []) + ([(f + 1, fwd + f * field)] if f + 1 < N else []) + \
+                   ([(f - 2, o["bwd2"].slot(N - 1 - f))] if f >= 2 else []) + ([(f + 2, o["fwd2"].slot(f))] if f + 2 < N else [])
+            d = descs[f]
+            for k, (g, at) in enumerate(near):
+                s = d.neighbour[k]
+                s.d_plane, s.pitch, s.pad, s.d_field = self.planes[g].ptr, self.planes[g].pitch, 0, at
+            d.n_neighbours, d.w, d.h, d.channels = len(near), w, h, self.channels
+            d.d_centre, d.centre_pitch, d.d_dst, d.dst_pitch, d.d_stats = self.planes[f].ptr, self.planes[f].pitch, o["frames"].slot(f), o["frames"].pitch, o["stats"].slot(f)
+        prm = temporal_params(self.weights, self.wc)
+        rc = self.lib().ofx_temporal_filter(descs, N, C.byref(prm), stream)
+        wipe(descs, prm)
+        return rc
+
+
 # ---- the registry -----------------------------------------------------------------------------------------------------------------------
 SIZE = (67, 45)
 MODELS = ("translation", "similarity", "affine")
@@ -981,6 +1238,10 @@ MAKERS = {
     "lk-pair-compat_cpu": lambda: LkPair("lk-pair-compat_cpu", "compat_cpu"),
     "frontend": lambda: Frontend("frontend", *SIZE, 21),
     "mosaic": lambda: Mosaic("mosaic", mosaic_items("ladder")),
+    "chain": lambda: Chain("chain", chain_items()),
+    "temporal": lambda: Temporal("temporal", temporal_items("random", 37)),
+    "temporal-one": lambda: Temporal("temporal-one", temporal_items("random", 37, rows=[0])),
+    "denoise-reach2": lambda: Denoise("denoise-reach2", 1, 0),
 }
 NAMES = list(MAKERS)
 
@@ -1006,6 +1267,10 @@ VARIANTS = {
     "lk-pair-compat_cpu": lambda: LkPair("lk-pair-compat_cpu", "compat_cpu", swap=True),
     "frontend": lambda: Frontend("frontend", *SIZE, 22),
     "mosaic": lambda: Mosaic("mosaic", mosaic_items("ladder", seed=100)),
+    "chain": lambda: Chain("chain", chain_items(seed=1)),
+    "temporal": lambda: Temporal("temporal", temporal_items("random", 37, base=50)),
+    "temporal-one": lambda: Temporal("temporal-one", temporal_items("random", 37, base=50, rows=[0])),
+    "denoise-reach2": lambda: Denoise("denoise-reach2", 1, 1),
 }
 assert list(VARIANTS) == NAMES
 
@@ -1033,6 +1298,10 @@ OTHERS = {
     "tracker": lambda: Track("tracker-b", track_frames(seed=5)[::-1], track_start(seed=3), 4),
     "median": lambda: Median("median-b", [("noise", 67, 45, 1), ("smooth", 67, 45, 2)]),
     "mosaic": lambda: Mosaic("mosaic-b", mosaic_items("steps", seed=50)),
+    # the stats slots in descending order: no two follow one another, every slot is a zeroing launch of its own
+    "chain": lambda: Chain("chain-b", chain_items(seed=3, turn=1), slots=range(len(CHAIN_GEOM) - 1, -1, -1)),
+    "temporal": lambda: Temporal("temporal-b", temporal_items("sigma 10", 256, base=20)),
+    "denoise-reach2": lambda: Denoise("denoise-reach2-b", 3, 2),
 }
 
 
@@ -1072,6 +1341,20 @@ def _features_chain():
     return [first, Features("reuse-features-2", T.make_input("noise", 49, 33), over=first)]
 
 
+def _chain_fold():
+    """the left fold of four links, in place: the first call chains links 0 and 1 on the shared buffer, which it loads with link 0;
+    the next two chain what the buffer holds with links 2 and 3.  One mask and one stats slot for all three."""
+    links = KC.links("borders", 257, 40, 4)
+    fold = [Chain("reuse-chain-1", [(links[:2], "odd", True, True)])]
+    for j in (2, 3):
+        h, w, _ = links[0].shape
+        fold.append(Chain(f"reuse-chain-{j}", [((fold[-1].end.reshape(h, w, 2), links[j]), "odd", True, True)], carried=True))
+    return fold
+
+
+TEMPORAL_REUSE = [("all 256", 1, 0), ("all 0", 256, 7), ("sigma 10", 256, 13)]        # (table, centre weight, base seed) of the three calls
+
+
 CHAINS = {
     "fit-translation": lambda: _fit_chain("translation"),
     "fit-similarity": lambda: _fit_chain("similarity"),
@@ -1092,6 +1375,10 @@ CHAINS = {
     "lk-pair-lk_float": lambda: [LkPair("reuse-lk-pair-1", "lk_float"), LkPair("reuse-lk-pair-2", "lk_float", swap=True)],
     # the d_counts slots and the d_which planes shared: few pixels covered, then most
     "mosaic": lambda: [Mosaic("reuse-mosaic-1", mosaic_items("edge")), Mosaic("reuse-mosaic-2", mosaic_items("steps", seed=3))],
+    "chain": _chain_fold,
+    # rows 0, 3 and 5 of the table: destination planes and stats slots shared; full weight, no weight at all, a sigma's table
+    "temporal": lambda: [Temporal(f"reuse-temporal-{j + 1}", temporal_items(table, wc, base=base, rows=[0, 3, 5])) for j, (table, wc, base) in enumerate(TEMPORAL_REUSE)],
+    "denoise-reach2": lambda: [Denoise("reuse-denoise-1", 1, 0), Denoise("reuse-denoise-2", 1, 1, TC.tables()["random"], 37)],
 }
 
 

@@ -5,6 +5,7 @@ milliseconds of other work, reads inputs that hold poison before and after their
 soon as it returns, and is compared with its referee by the bits after one synchronisation at the very end."""
 import threading
 
+import numpy as np
 import pytest
 
 import call_order as CO
@@ -37,6 +38,37 @@ def test_a_call_runs_in_order_on_the_callers_stream(torch, lanes, name):
     snap = CO.enqueue(torch, r, lanes[0])
     torch.cuda.synchronize()
     r.check(snap)
+
+
+def test_the_engine_denoises_in_order_on_the_callers_stream(torch, lanes):
+    """engine.denoise_rings(reach=2) inside torch.cuda.stream(side stream), on the inputs of the row "denoise-reach2" and the schedule
+    of a.: the engine takes its stream from torch's current one, enqueues two chain calls and the filter on their outputs without a
+    synchronisation, and frees fwd2 and bwd2 while the filter is still pending.  Frames and stats are the recipe's, by the bits."""
+    from cuda_optical_flow_2_amd import engine
+
+    r, lane = CC.recipe("denoise-reach2"), lanes[0]
+    N, w, h, sigma = CC.DENOISE
+    clean = [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in (r.frames, r.fwd, r.bwd)]
+    bufs = [torch.empty_like(c) for c in clean]
+
+    def poison():
+        bufs[0].fill_(0xEE)
+        for b in bufs[1:]:
+            b.fill_(CC.NAN)
+
+    poison()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(lane.stream):
+        lane.a = CO.busy(torch, lane.a, CO.BUSY_ROUNDS)
+        for b, c in zip(bufs, clean):
+            b.copy_(c)
+        out, stats = engine.denoise_rings(bufs[0], bufs[1], bufs[2], float(sigma), reach=2, return_stats=True)
+        poison()
+        got = out.clone(), stats.clone()
+        del out, stats
+    torch.cuda.synchronize()
+    CC.same(got[0].cpu().numpy().reshape(N, h, w), r.want["frames"], "engine.denoise_rings(reach=2) on a side stream: frames")
+    CC.same(got[1].cpu().numpy().reshape(N, 1, 8), r.want["stats"], "engine.denoise_rings(reach=2) on a side stream: stats")
 
 
 # ---- b. the harness sees a misplaced launch -------------------------------------------------------------------------------------------
