@@ -5,7 +5,8 @@ process of tests/test_gpu_deep_iter.py.  Not a test module and not a conftest.
 
 OFX_ITER_DMA is read once per process, at the first LK launch (csrc/lk_level.hip, lk_switches), so the deep form is reached at small
 shapes only by a process that was STARTED with it.  This one refuses to start otherwise, runs the cases of GROUP on the GPU, stores
-every flow array under a readable key in OUT.npz and prints "deep ok".  It compares nothing and calls no oracle: the parent does,
+every flow array under a readable key in OUT.npz and prints "deep ok".  Together the groups reach all 88 instances of the deep
+family (A: lk_float ITER 3, 2, 1; E: the fast ones; R: ITER 4 and the ITER 1 behind it, both solves; every radius each).  It compares nothing and calls no oracle: the parent does,
 on the CPU.  The first exception ends it with a non-zero status.
 
 The case lists below are read by the parent and by tests/test_deep_plan.py (which shows on the host that the launches they make
@@ -20,6 +21,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 import iter_hard as ih   # noqa: E402
+import lk_instances as li   # noqa: E402
 
 _P9 = ih.pair_out_w(4)
 _ALL = {c.id: c for c in ih.A_CASES + ih.C_CASES + ih.D_CASES}
@@ -39,8 +41,9 @@ C_CASES = [_ALL[i] for i in (f"C-win9-w{_P9 + 1}-it5-B2", f"C-win3-w{ih.pair_out
                              f"C-win11-w{ih.tile_out_w(5) + 1}-it4-B1", f"C-win15-w{ih.tile_out_w(7) + 1}-it5-B2")]
 # D: the determinant guard (ih.MIN_DET)
 D_CASES = [_ALL[i] for i in ("A-win9", "A-win15", f"C-win9-w{_P9 + 1}-it5-B2", "D-3level")]
-# E: lk_float_fast, sessions of 1 .. iters iterations (test_fast_solve_step_by_step)
-E_CASES = [_ALL[i] for i in ("A-win3", "A-win9", "A-win23", f"C-win5-w{ih.pair_out_w(2) + 1}-it4-B2")]
+# E: lk_float_fast, sessions of 1 .. iters iterations (test_fast_solve_step_by_step): every window pair at a time -- the fast ITER 3,
+# 2 and 1 of every radius -- and one streamed case
+E_CASES = [c for c in ih.E_CASES if c.kind == "pair"] + [_ALL[f"C-win5-w{ih.pair_out_w(2) + 1}-it4-B2"]]
 # dense: Session.run_flow_dense, whose levels below the top are single-level launches: ITER 2 (add + warp), then ITER 1
 # (w, h, levels, window, frames of test_gpu_dense._frames, iters, min_det, max_px)
 DENSE_RUNS = [(264, 80, 3, 9, kind, iters, min_det, max_px) for kind in ("hard", "smooth") for iters in (1, 3) for min_det in (0.0, 1.0)
@@ -49,8 +52,16 @@ DENSE_RUNS = [(264, 80, 3, 9, kind, iters, min_det, max_px) for kind in ("hard",
 # test_sharded_streamed_iterations_equal_the_unsharded_path, logical ranks on one device.  Smooth frames: the huge flows of the hard
 # ones leave a shard's rows and rightly set the status word.
 ROWS = dict(w=640, h=480, levels=3, win=9, iters=3, ranks=3, B=2, warp_margin=8)
+# R: row windows of every window, both solves: the cases of tests/test_gpu_lk_instances.py's T5 (three logical ranks, cuts at least
+# R + 2 rows deep at both levels, three iterations).  Under the switch the tick (WOUT 5) stays plain; the ITER 4 and ITER 1 launches
+# behind it are deep.
+R_CASES = list(li.T5_CASES)
+R_MODES = tuple(li.T5_MODES)
+# Rstrips: a row window under the strip settings of "strips": one strip per tile column (the row table refreshed on a buffer that
+# ends inside the level) and strips of one row
+R_STRIP_CASES = [c for c in R_CASES if c.win in (9, 23)]
 
-GROUPS = ("A", "strips", "B", "C", "D", "E", "dense", "rows")
+GROUPS = ("A", "strips", "B", "C", "D", "E", "dense", "rows", "R", "Rstrips")
 
 
 def key(*parts):
@@ -151,15 +162,13 @@ def run_dense(eng, out):
             out[key(dense_key(run), f"level{k}")] = got[k]
 
 
-def run_rows(eng, out):
+def _rank_rows(eng, out, prefix, c, mode, frames):
+    """the logical ranks of c (an lk_instances.Rows) on one device, the way tests/test_gpu_lk_instances.py::_ranks runs them: every
+    rank's rows of every pair and level under prefix/rankR/pairP/levelK, the ranks' status words under prefix/status"""
     import torch
-    from cuda_optical_flow_2_amd.parallel import ShardPlan
 
-    c = ROWS
-    w, h, L, win, iters, R, B = c["w"], c["h"], c["levels"], c["win"], c["iters"], c["ranks"], c["B"]
-    frames = [torch.from_numpy(f).cuda() for f in rows_frames()]
-    ranks = [eng.Session(w, h, L, win, "lk_float", shard=ShardPlan(w, h, L, win, r, R, iters=iters, warp_margin=c["warp_margin"]), local_corner=True,
-                         stream_batch=B, iters=iters, strict=False) for r in range(R)]
+    L, B = c.levels, c.B
+    ranks = [eng.Session(c.w, c.h, L, c.win, mode, shard=pl, local_corner=True, stream_batch=B, iters=c.iters, strict=False) for pl in li.shard_plans(c)]
     seen = 0
     for s in ranks:
         s.stream_begin()
@@ -170,7 +179,7 @@ def run_rows(eng, out):
             for p in range(max(seen + 1, done - B + 1), done + 1):
                 for r, s in enumerate(ranks):
                     for k in range(L):
-                        out[key("rows", f"rank{r}", f"pair{p}", f"level{k}")] = s.flow_of(p, k)[0].cpu().numpy()
+                        out[key(prefix, f"rank{r}", f"pair{p}", f"level{k}")] = s.flow_of(p, k)[0].cpu().numpy()
             seen = done
     for f in frames:
         snap([s.stream_submit(f) for s in ranks][0])
@@ -180,10 +189,38 @@ def run_rows(eng, out):
             break
         snap(d)
     torch.cuda.synchronize()
-    out[key("rows", "status")] = np.array([s.corner_status() for s in ranks], np.int64)
+    out[key(prefix, "status")] = np.array([s.corner_status() for s in ranks], np.int64)
     for s in ranks:
         s.close()
-    assert seen == len(frames) - 1, f"{seen} pairs of {len(frames) - 1} came out"
+    assert seen == len(frames) - 1, f"{prefix}: {seen} pairs of {len(frames) - 1} came out"
+
+
+def run_rows(eng, out):
+    import torch
+
+    _rank_rows(eng, out, "rows", li.Rows(id="rows", **ROWS), "lk_float", [torch.from_numpy(f).cuda() for f in rows_frames()])
+
+
+def run_R(eng, out):
+    from test_gpu_iter_hard import _device_frames
+
+    for c in R_CASES:
+        frames = _device_frames(c, li.rows_frames(c))
+        for mode in R_MODES:
+            _rank_rows(eng, out, key("R", c.id, mode), c, mode, frames)
+
+
+def run_Rstrips(eng, out):
+    from test_gpu_iter_hard import _device_frames
+
+    try:
+        for c in R_STRIP_CASES:
+            frames = _device_frames(c, li.rows_frames(c))
+            for ms in MIN_STRIPS:
+                os.environ["OFX_LK_MIN_STRIP"] = str(ms)
+                _rank_rows(eng, out, key("Rstrips", c.id, f"strip{ms}"), c, "lk_float", frames)
+    finally:
+        os.environ.pop("OFX_LK_MIN_STRIP", None)
 
 
 def main(argv):

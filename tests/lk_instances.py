@@ -8,7 +8,9 @@ instance of
     stream_kernel   112 = lk_inst_stream_{c,f,fast}.hip (WOUT 0, plain and deep; compat_cpu at radii 1..12, lk_float at 1..11)
                           + lk_inst_stream_{fw,fastw}.hip (WOUT 3) + lk_inst_stream_{fwr,fastwr}.hip (WOUT 5), plain only
     lk_level_kernel  57 = compat_cpu and lk_float with and without sums, lk_float_fast without
-    lk_iter_kernel   88 = ITER 1..4, lk_float and lk_float_fast, plain (the deep forms: tests/deep_child.py, at fewer radii)
+    lk_iter_kernel   88 = ITER 1..4, lk_float and lk_float_fast, plain; and the same 88 in the deep-fetch form (DMA = true), reached in
+                          child processes started with OFX_ITER_DMA=1: tests/deep_child.py, whose groups A, E and R run T5 and the
+                          cases of iter_hard at every radius (the census: tests/test_deep_plan.py)
 
 The geometry is that of tests/iter_hard.py (_c, _case, hard_pair, tile_out_w, pair_out_w), not restated."""
 from collections import namedtuple
@@ -146,9 +148,9 @@ def levels_family():
            {(1, 1, 0, r) for r in radii("lk_float_fast")}
 
 
-def iter_family():
-    """{(MODE, FAST, ITER, deep = 0, radius)}: lk_inst_iter_{f,fast}{1,2,3,4}.hip, the plain form"""
-    return {(1, fast, it, 0, r) for fast in (0, 1) for it in (1, 2, 3, 4) for r in radii("lk_float")}
+def iter_family(deep=0):
+    """{(MODE, FAST, ITER, deep, radius)}: lk_inst_iter_{f,fast}{1,2,3,4}.hip, the plain form (deep = 0) or the deep-fetch one (1)"""
+    return {(1, fast, it, deep, r) for fast in (0, 1) for it in (1, 2, 3, 4) for r in radii("lk_float")}
 
 
-assert (len(stream_family()), len(levels_family()), len(iter_family())) == (112, 57, 88)
+assert (len(stream_family()), len(levels_family()), len(iter_family()), len(iter_family(deep=1))) == (112, 57, 88, 88)

@@ -7,6 +7,11 @@ process started with it (tests/deep_child.py, which only computes and stores); e
 references of tests/test_gpu_iter_hard.py and tests/test_gpu_dense.py.  tests/test_deep_plan.py shows on the host that the launches
 of these cases select the deep kernels.  At most two processes have the device open: this one and one child.
 
+Every instance of the deep family -- 2 solves x ITER 1..4 x 11 radii = 88 kernels -- is run by some group: lk_float ITER 3, 2, 1 by A,
+the fast ones by E (every window, step by step), ITER 4 and the ITER 1 behind it in both solves by R (the row windows of
+tests/lk_instances.py's T5: lk_float against the oracle, lk_float_fast against an unsharded session run HERE, in the plain form, which
+tests/test_gpu_lk_instances.py ties to the oracle); tests/test_deep_plan.py holds the census.
+
 A child that a signal ended (or that aborted, or ran into its limit) has faulted the device or hung on it: no further child is
 started after that, every later group fails at once.
 
@@ -23,6 +28,7 @@ from conftest import assert_same
 import deep_child as dc
 import dense_ref
 import iter_hard as ih
+import lk_instances as li
 from test_gpu_iter_hard import _device_frames, fast_steps_against_the_oracle
 from test_gpu_iteration_pairs import _stream
 
@@ -63,7 +69,8 @@ def _group(name):
     return fixture
 
 
-group_A, group_strips, group_C, group_D, group_E, group_dense, group_rows, group_B = (_group(g) for g in ("A", "strips", "C", "D", "E", "dense", "rows", "B"))
+group_A, group_strips, group_C, group_D, group_E, group_dense, group_rows, group_R, group_Rstrips, group_B = \
+    (_group(g) for g in ("A", "strips", "C", "D", "E", "dense", "rows", "R", "Rstrips", "B"))
 
 
 def _ids(cases):
@@ -118,7 +125,7 @@ def test_determinant_guard_with_iterations(oracle, group_D, case):
 
 @pytest.mark.parametrize("case", dc.E_CASES, ids=_ids(dc.E_CASES))
 def test_fast_solve_step_by_step(oracle, group_E, case):
-    """E.  lk_float_fast: test_gpu_iter_hard.py's step-by-step check on the child's sessions of 1 .. iters iterations."""
+    """E.  lk_float_fast: test_gpu_iter_hard.py's step-by-step check on the child's sessions of 1 .. iters iterations, every window."""
     runs = {j: _pairs(group_E, dc.key("E", case.id, f"iters{j}"), case) for j in range(1, case.iters + 1)}
     if case.kind == "stream":
         for j in runs:
@@ -153,6 +160,71 @@ def test_row_windows_of_logical_ranks(oracle, group_rows):
         for k in range(c["levels"]):
             got = np.concatenate([group_rows[dc.key("rows", f"rank{r}", f"pair{p}", f"level{k}")] for r in range(c["ranks"])], axis=0)
             assert_same(got, want[k], f"{c['ranks']} ranks: pair {p} level {k}")
+
+
+# ---- R: the row windows of every window ------------------------------------------------------------------------------------------
+_rows_want = {}     # {case id: {pair: the oracle's pyramid}}: shared by R and Rstrips, never written to again
+
+
+def _oracle_rows(oracle, c, frames):
+    if c.id not in _rows_want:
+        _rows_want[c.id] = {p: oracle.flow_pair_iter(frames[p - 1], frames[p], c.levels, c.win, c.iters) for p in range(1, len(frames))}
+    return _rows_want[c.id]
+
+
+def _ranks_together(got, prefix, c, n_frames):
+    """{pair: flow pyramid} of the ranks' rows under prefix, concatenated; every rank's status word must be 0 (that the ORACLE's
+    flows stay inside every rank's rows on these frames: tests/test_iter_hard_ref.py, test_row_window_cases_stay_inside_their_rows)"""
+    status = got[dc.key(prefix, "status")].tolist()
+    assert status == [0] * c.ranks, f"{prefix}: status {[hex(x) for x in status]}"
+    out = {}
+    for p in range(1, n_frames):
+        out[p] = [np.concatenate([got[dc.key(prefix, f"rank{r}", f"pair{p}", f"level{k}")] for r in range(c.ranks)], axis=0) for k in range(c.levels)]
+        for k in range(c.levels):
+            assert out[p][k].shape == (c.h >> k, c.w >> k, 2) and out[p][k].dtype == np.float32, f"{prefix}: pair {p} level {k} has shape {out[p][k].shape}"
+    return out
+
+
+@pytest.mark.parametrize("mode", dc.R_MODES)
+@pytest.mark.parametrize("c", dc.R_CASES, ids=[c.id for c in dc.R_CASES])
+def test_row_windows_of_every_window_deep(oracle, group_R, c, mode):
+    """R.  lk_iter_kernel<R, lk_float, FAST, ITER 4 / ITER 1, DMA = true> on the row windows of three logical ranks behind the plain
+    WOUT 5 tick.  lk_float: the oracle's three iterations, by the bits.  lk_float_fast: an unsharded lk_float_fast session of the same
+    frames run in THIS process, in the plain form, by the bits of the words (the two forms differ in how rows arrive, not in
+    arithmetic; the child alone would compare deep with deep)."""
+    assert "OFX_ITER_DMA" not in os.environ and "OFX_LK_DMA" not in os.environ, "with OFX_ITER_DMA or OFX_LK_DMA set this process's session would be deep as well"
+    frames = li.rows_frames(c)
+    got = _ranks_together(group_R, dc.key("R", c.id, mode), c, len(frames))
+    if mode == "lk_float":
+        want = _oracle_rows(oracle, c, frames)
+        for p in got:
+            for k in range(c.levels):
+                assert_same(got[p][k], want[p][k], f"{c.id} {mode} deep, {c.ranks} ranks: pair {p} level {k}")
+        return
+    import torch
+
+    if _stop:
+        pytest.fail(f"not run: {_stop[0]}")
+    assert torch.cuda.is_available(), "these tests need the MI355X"
+    from cuda_optical_flow_2_amd import engine as eng
+
+    want = _stream(eng, _device_frames(c, frames), c.w, c.h, c.levels, c.win, mode, c.iters, c.B)
+    for p in got:
+        for k in range(c.levels):
+            assert_same(got[p][k].view(np.uint32), want[p][k].view(np.uint32), f"{c.id} {mode}, deep ranks against the plain unsharded session: pair {p} level {k}")
+
+
+@pytest.mark.parametrize("min_strip", dc.MIN_STRIPS)
+@pytest.mark.parametrize("c", dc.R_STRIP_CASES, ids=[c.id for c in dc.R_STRIP_CASES])
+def test_row_windows_one_strip_and_strips_of_one_row_deep(oracle, group_Rstrips, c, min_strip):
+    """Rstrips.  OFX_LK_MIN_STRIP=1000: a wave marches a rank's whole tile column and refreshes its row table inside a buffer that
+    ends within the level; =1: strips of one row, which prime more rows than they take -- next to a buffer's first and last row too."""
+    frames = li.rows_frames(c)
+    got = _ranks_together(group_Rstrips, dc.key("Rstrips", c.id, f"strip{min_strip}"), c, len(frames))
+    want = _oracle_rows(oracle, c, frames)
+    for p in got:
+        for k in range(c.levels):
+            assert_same(got[p][k], want[p][k], f"{c.id} OFX_LK_MIN_STRIP={min_strip}, {c.ranks} ranks: pair {p} level {k}")
 
 
 # ---- the tick's deep form, in this process ----------------------------------------------------------------------------------------

@@ -14,7 +14,7 @@ import pytest
 import iter_hard as ih
 import lk_instances as li
 import lk_plan_ref as ref
-from test_deep_plan import ADD, ADD_WARP, case_launches
+from test_deep_plan import ADD, ADD_WARP, case_launches, rank_items
 from test_lk_plan import ROOT, compile_tool, item, line_of, parse
 
 CSRC = os.path.join(ROOT, "cuda_optical_flow_2_amd", "csrc")
@@ -41,11 +41,6 @@ def tick_pairs(B):
 
 def tick_line(c, mode, warp_out, hint, pairs):
     return "launch=tick mode=%d window=%d warp_out=%d hint=%d pyramid=%dx%d:%d:%d" % (li.MODE_ID[mode], c.win, warp_out, hint, c.w, c.h, c.levels, pairs)
-
-
-def rank_items(c, pl, pairs):
-    """a rank's items: the planes hold its buffer rows (test_deep_plan.rows_launches)"""
-    return [item(c.w >> k, c.h >> k, out=pl.own[k], rows=pl.buf[k], flow_row0=pl.buf[k][0]) for _ in range(pairs) for k in range(c.levels - 1, -1, -1)]
 
 
 def with_flags(items, aw):
